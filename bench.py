@@ -17,9 +17,15 @@ their status.  ``--scaling weak`` (default) gives every GPU B items;
 only collective on the data path is the one RCCL broadcast of the shared
 backgrounds; timing is the max over ranks.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+A plain run does only what the headline figure needs: set up, warm up, time
+the K steps, write ``--dump-outputs`` if asked, print the line.  ``--full``
+adds every other measurement (the copy-kernel ceiling, the streaming leg, the
+config-2 and config-5 legs, the CPU baselines); the ``--no-*`` options switch
+single ones of them off again.
+
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--full]
                   [--scaling weak|strong] [--workload pipe5|rotflip|video4k]
-                  [--no-cpu-baseline] [--dump-digests FILE] [--dry-run]
+                  [--no-cpu-baseline] [--dump-outputs DIR] [--dump-digests FILE] [--dry-run]
 """
 from __future__ import annotations
 
@@ -55,21 +61,26 @@ def parse(argv=None):
     ap.add_argument("--size", type=int, default=1024)
     ap.add_argument("--backgrounds", type=int, default=16)
     ap.add_argument("--workload", choices=["pipe5", "rotflip", "video4k"], default=None,
-                    help="pipe5 (default; with the rotflip and video4k legs unless --no-legs), or one workload alone")
+                    help="pipe5 (default; --full adds the rotflip and video4k legs unless --no-legs), or one workload "
+                         "alone")
     ap.add_argument("--frames", type=int, default=256,
                     help="video4k: 3840x2160 frames per GPU (weak) or in total (strong)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--rot-row-align", type=int, default=128,
                     help="rotflip: output row pitch alignment in bytes (A/B of the store alignment)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the copy-kernel ceiling, the pipe5 "
+                         "streaming leg, the rotflip and video4k legs and the CPU baselines (each has a --no-* "
+                         "option); a run without --full does none of them")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
     ap.add_argument("--cpu-sample", type=int, default=192)
-    ap.add_argument("--no-copy-ceiling", action="store_true")
+    ap.add_argument("--no-copy-ceiling", action="store_true", help="--full: skip the copy-kernel ceiling")
     ap.add_argument("--stream", action="store_true",
-                    help="pipe5: the streaming leg (the default; kept for scripts)")
+                    help="pipe5: the streaming leg (part of --full; kept for scripts)")
     ap.add_argument("--no-stream", action="store_true",
-                    help="pipe5: skip the streaming leg (a new plan per batch, planned on a host thread while the "
-                         "previous batch runs), which is otherwise timed after the resident step and reported "
-                         "beside it")
+                    help="pipe5 with --full: skip the streaming leg (a new plan per batch, planned on a host thread "
+                         "while the previous batch runs), which is otherwise timed after the resident step and "
+                         "reported beside it")
     ap.add_argument("--stream-default-priority", action="store_true",
                     help="--stream: launch the pipe on the default-priority stream (not a high-priority one)")
     ap.add_argument("--stream-lookahead", type=int, default=2,
@@ -80,14 +91,18 @@ def parse(argv=None):
     ap.add_argument("--pipe-ratio", type=float, default=1.0,
                     help="pipe5 with --pipe-parts: item range k holds a share proportional to ratio**k")
     ap.add_argument("--no-legs", action="store_true",
-                    help="pipe5: skip the config-2 (rotflip) and config-5 (video4k) legs that the default run "
-                         "times after the headline and reports under 'workloads'")
+                    help="pipe5 with --full: skip the config-2 (rotflip) and config-5 (video4k) legs that are "
+                         "otherwise timed after the headline and reported under 'workloads'")
     ap.add_argument("--frame-noise", type=int, default=0,
                     help="video4k: +-N LSB of uniform noise per channel on the synthetic frames (0 = flat frames)")
     ap.add_argument("--dist-backend", choices=["nccl", "gloo"], default="nccl",
                     help="gloo: CPU rehearsal of the N-rank path (tests)")
     ap.add_argument("--dump-digests", default=None,
                     help="rank 0 writes {global item: sha1 of its output} (outputs of every rank)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps rank 0 writes what the last of them computed (of its own items) as "
+                         "DIR/<name>.npy in float32/float64: a fixed, seeded sample of rows where the outputs are "
+                         "larger than the 48 MB kept")
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU only: plan, shard and broadcast, no kernels (launcher tests); digests are of the "
                          "per-item inputs and parameters")
@@ -249,6 +264,30 @@ def cpu_baseline(args):
     return cpu_pipe.measure(sample, size=args.size, workload=args.workload)
 
 
+DUMP_BUDGET = 48 << 20  # bytes of float32 samples that --dump-outputs keeps of one output
+
+
+def sample_rows(flat, starts, lens, seed: int):
+    """float32 host copy of rows of the uint8 device buffer `flat` (row r =
+    flat[starts[r] : starts[r] + lens[r]]), concatenated in row order: every
+    row when that fits DUMP_BUDGET, else the rows of a fixed permutation
+    (drawn from `seed`) that do."""
+    import numpy as np
+    import torch
+
+    starts, lens = np.asarray(starts, np.int64), np.asarray(lens, np.int64)
+    if len(lens) and (starts.min() < 0 or lens.min() < 0 or (starts + lens).max() > flat.numel()):
+        raise ValueError("sample_rows: a row lies outside the buffer")
+    if int(lens.sum()) * 4 > DUMP_BUDGET:
+        order = np.random.default_rng(seed).permutation(len(lens))
+        fit = int(np.searchsorted(np.cumsum(lens[order]), DUMP_BUDGET // 4, side="right"))
+        keep = np.sort(order[:fit])
+        starts, lens = starts[keep], lens[keep]
+    first = np.cumsum(lens) - lens
+    idx = np.repeat(starts - first, lens) + np.arange(int(lens.sum()), dtype=np.int64)
+    return flat.reshape(-1)[torch.from_numpy(idx).to(flat.device)].to(torch.float32).cpu().numpy()
+
+
 def _digest(*arrays) -> str:
     h = hashlib.sha1()
     for a in arrays:
@@ -261,7 +300,7 @@ def main(argv=None):
     args = parse(argv)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch(args.gpus, argv))
-    legs = args.workload is None and not args.no_legs and not args.dry_run and not args.dump_digests
+    legs = args.full and args.workload is None and not args.no_legs and not args.dry_run and not args.dump_digests
     if args.workload is None:
         args.workload = "pipe5"
 
@@ -278,7 +317,7 @@ def main(argv=None):
         for wl in ("rotflip", "video4k"):
             torch.cuda.empty_cache()
             a = copy.copy(args)
-            a.workload, a.batch = wl, None
+            a.workload, a.batch, a.dump_outputs = wl, None, None
             r = run_workload(a, rank, world, dev)
             if r is not None:
                 result["workloads"][wl] = leg_summary(r)
@@ -380,6 +419,10 @@ def run_workload(args, rank, world, dev):
                                                                                      args.pipe_ratio))]
                 algo = {"ipp_pipe_overlapped": sum(algo.values())}
         outputs = lambda: {start + i: _digest(out[i].cpu().numpy()) for i in range(B)}
+
+        def dump():   # rows of the B composites
+            return {"composites": sample_rows(out, np.arange(B * S, dtype=np.int64) * (3 * S),
+                                              np.full(B * S, 3 * S, np.int64), args.seed)}
         workload = "5-stage pipe: crop(64px)->rotate(NEAREST,expand,bbox)->flip->HSV mask(4 ref ranges)->LANCZOS+paste"
     elif args.workload == "video4k":
         from image_processor_pipeline_amd import video_chain
@@ -412,6 +455,16 @@ def run_workload(args, rank, world, dev):
                     crop = chain.out[i, :max(0, y1 - y0), :max(0, x1 - x0)].cpu().numpy() if x0 >= 0 else np.zeros(0)
                     res[start + i] = _digest(bbs[i], np.ascontiguousarray(crop))
                 return res
+
+            def dump():   # every bounding box, rows of the BGRA crops
+                bbs = chain.bbox.cpu().numpy().reshape(B, 4).astype(np.int64)
+                starts, lens = [], []
+                for i, (x0, y0, x1, y1) in enumerate(bbs):
+                    if x0 >= 0 and x1 > x0 and y1 > y0:
+                        starts.append((i * FH + np.arange(y1 - y0, dtype=np.int64)) * (4 * FW))
+                        lens.append(np.full(y1 - y0, 4 * (x1 - x0), np.int64))
+                cat = lambda v: np.concatenate(v) if v else np.zeros(0, np.int64)
+                return {"bbox": bbs.astype(np.float64), "crops": sample_rows(chain.out, cat(starts), cat(lens), args.seed)}
         workload = ("4K video chain: HSV mask (4 ref ranges) -> largest 8-connected component -> crop-fit, "
                     "fused, structured frames (blob + 0.5% specks)")
     else:
@@ -443,6 +496,12 @@ def run_workload(args, rank, world, dev):
                     img = np.lib.stride_tricks.as_strided(host[int(off):], (oh, ow, 4), (int(pitch), 4, 1))
                     res[start + i] = _digest(np.ascontiguousarray(img))
                 return res
+
+            def dump():   # rows of the B rotated RGBA canvases (without the pitch padding)
+                starts = [int(off) + np.arange(oh, dtype=np.int64) * int(pitch)
+                          for (oh, ow), off, pitch in zip(gplan.shapes, gplan.offsets, gplan.pitches)]
+                lens = [np.full(oh, 4 * ow, np.int64) for oh, ow in gplan.shapes]
+                return {"rotated": sample_rows(out, np.concatenate(starts), np.concatenate(lens), args.seed)}
         workload = "rotations+symmetry fused gather (NEAREST rotate, expand, bbox crop, flip)"
     plan_ms = (time.perf_counter() - t_plan) * 1e3
     if "plan_host_ms" in setup:   # planning proper, without making the synthetic sources
@@ -462,7 +521,7 @@ def run_workload(args, rank, world, dev):
         return None
 
     ceiling = None
-    if not args.no_copy_ceiling:
+    if args.full and not args.no_copy_ceiling:
         barrier(world, dev)
         ceiling = copy_ceiling(dev)
     stream = torch.cuda.current_stream(dev)
@@ -490,8 +549,14 @@ def run_workload(args, rank, world, dev):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    if args.dump_outputs and rank == 0:
+        # before anything below runs the kernels again: the last timed step's outputs
+        Path(args.dump_outputs).mkdir(parents=True, exist_ok=True)
+        for name, a in dump().items():
+            np.save(Path(args.dump_outputs) / f"{name}.npy", a)
+
     stream_res = None
-    if not args.no_stream and args.workload == "pipe5":
+    if args.full and not args.no_stream and args.workload == "pipe5":
         # Streaming: batch k of the timed run has its own plan (seed + k),
         # planned on a worker thread (host planner + device taps on a side
         # stream) while batch k-1 runs.  The clock starts with the pipeline
@@ -608,7 +673,7 @@ def run_workload(args, rank, world, dev):
         result["crop_reread_bytes_per_step"] = int(reread_bytes)
     if bg_copy is not None:
         result["bg_copy"] = bg_copy
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             result["cpu_baseline"] = cpu_baseline(args)
         except Exception as e:  # reported, never fatal to the GPU number

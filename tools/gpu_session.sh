@@ -24,10 +24,10 @@ if [ "$2" != prof ]; then
 tail -1 $OUT/pytest.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || { tail -20 $OUT/smoke.log; exit 22; }
 echo smoke ok
-timeout -k 10 600 python bench.py > $OUT/bench_pipe5.json.log 2>&1 || { tail -20 $OUT/bench_pipe5.json.log; exit 23; }
+timeout -k 10 600 python bench.py --full > $OUT/bench_pipe5.json.log 2>&1 || { tail -20 $OUT/bench_pipe5.json.log; exit 23; }
 tail -c 1500 $OUT/bench_pipe5.json.log
 [ "$2" = quick ] && exit 0
-timeout -k 10 400 python bench.py --workload video4k --frame-noise 2 --no-cpu-baseline > $OUT/bench_video4k_noise2.json.log 2>&1 || exit 25
+timeout -k 10 400 python bench.py --full --workload video4k --frame-noise 2 --no-cpu-baseline > $OUT/bench_video4k_noise2.json.log 2>&1 || exit 25
 tail -c 600 $OUT/bench_video4k_noise2.json.log
 [ "$2" = tests ] && exit 0
 fi
