@@ -139,6 +139,8 @@ SIGNATURES = {
     "ipp_ccl_scratch_layout": (_L, [_I, _I, _P]),
     "ipp_video_keep_largest": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _L, _P, _P, _P, _P, _P, _P]),
     "ipp_alpha_bbox": (_I, [_P, _P, _I, _I, _I, _P, _P]),
+    "ipp_alpha_bbox_min": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
+    "ipp_pipe_overlay_bbox": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "ipp_plan_lanczos": (_L, [_I, _D, _D, _I, _P, _L]),
     "ipp_plan_lanczos_ksize": (_I, [_D, _D, _I]),
     "ipp_plan_lanczos_batch": (_I, [_I, _P, _P, _P, _P, _L, _I]),

@@ -131,24 +131,34 @@ def keep_largest(imgs: Sequence[np.ndarray]) -> List[Optional[np.ndarray]]:
 
 
 def overlays(ovs: Sequence[np.ndarray], bgs: Sequence[np.ndarray], sizes: Sequence[Tuple[int, int]],
-             pos: Sequence[Tuple[int, int]]) -> List[np.ndarray]:
+             pos: Sequence[Tuple[int, int]], bbox_alpha_min: Optional[int] = None):
     """overlays.py:129-139 for a chunk: LANCZOS resize of each RGBA overlay
     to sizes[i] = (w, h) (RGBa round trip) and paste onto its RGB background
     at pos[i] — ipp_lanczos_h + ipp_lanczos_v + ipp_paste_blend, one launch
     each for the items resized on both axes; one-axis and identity resizes
-    (rare) take the per-image device path."""
-    from .device import paste_blend, resize_lanczos_rgba
+    (rare) take the per-image device path.  Returns the composites; with
+    ``bbox_alpha_min`` (1..255) it returns (composites, boxes): boxes[i] =
+    the box (x0, y0, x1, y1), in overlay coordinates, of the resized overlay's
+    pixels with alpha >= bbox_alpha_min, or None when there is none
+    (ipp_alpha_bbox_min, one more launch over the chunk's resized overlays)."""
+    from .device import alpha_bbox_min, alpha_bbox_min_packed, check_alpha_min, paste_blend, resize_lanczos_rgba
+    tight = bbox_alpha_min is not None
+    if tight:
+        bbox_alpha_min = check_alpha_min(bbox_alpha_min)
     n = len(ovs)
     if n == 0:
-        return []
+        return ([], []) if tight else []
     lib = N.load()
     both = [i for i in range(n) if sizes[i][0] != ovs[i].shape[1] and sizes[i][1] != ovs[i].shape[0]]
     res: List[Optional[np.ndarray]] = [None] * n
+    boxes: List[Optional[Tuple[int, int, int, int]]] = [None] * n
     for i in sorted(set(range(n)) - set(both)):
         rs = resize_lanczos_rgba(_rt.h2d(ovs[i]), *sizes[i])
+        if tight:
+            boxes[i] = alpha_bbox_min([rs], bbox_alpha_min)[0]
         res[i] = _rt.d2h(paste_blend(_rt.h2d(bgs[i]), rs, *pos[i]))
     if not both:
-        return res
+        return (res, boxes) if tight else res
     ov_buf, ooffs = _pack([ovs[i] for i in both])
     bg_buf, boffs = _pack([bgs[i] for i in both])
     dev = ov_buf.device
@@ -209,6 +219,9 @@ def overlays(ovs: Sequence[np.ndarray], bgs: Sequence[np.ndarray], sizes: Sequen
     N.check(lib.ipp_paste_blend(bg_buf.data_ptr(), rsb.data_ptr(), out.data_ptr(), pdd.data_ptr(), len(both),
                                 max(s[1] for s in out_shapes), max(s[0] for s in out_shapes), st), "ipp_paste_blend")
     _keep(thd, tvd, hdd, vdd, pdd, tmp, rsb, ov_buf, bg_buf)
+    if tight:
+        for i, b in zip(both, alpha_bbox_min_packed(rsb, roffs, rs_shapes, bbox_alpha_min)):
+            boxes[i] = b
     for i, c in zip(both, _unpack(out, coffs, out_shapes)):
         res[i] = c
-    return res
+    return (res, boxes) if tight else res

@@ -1,0 +1,223 @@
+// ipp_label.hip — boxes for the YOLO labels of pasted overlays
+// (overlays.py:141-149 writes one label per composite).
+//
+//   ipp_pipe_overlay_bbox: the tight box of each item's resized overlay in the
+//   fused pipe.  The resized overlay is never materialised there: its alpha
+//   exists only as T (the H pass's scratch) combined with the V-axis tap
+//   tiles.  The kernel is the V pass of ipp_pipe.hip's k_pipe_vblend_mfma
+//   restricted to channel 3: it reads dword 3 of each 16-B T group and the
+//   band's tap tile, and writes nothing but the boxes.
+//
+//   ipp_alpha_bbox_min: the same box on a materialised 2/4-channel image
+//   (the plugin path), ipp_alpha_bbox with a threshold.
+//
+// Both follow ipp_alpha_bbox's convention (ipp_gather.hip): the boxes are
+// pre-set to (INT_MAX, INT_MAX, -1, -1), every wave that saw a visible pixel
+// issues four device-scope atomics, and a finish kernel turns an untouched row
+// into (-1, -1, -1, -1).
+#include <climits>
+
+#include "ipp_device.h"
+
+namespace {
+
+typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int LBR = 16;  // rows of a V tap tile = composite rows of a band (ipp_pipe.hip VBR)
+
+__global__ void k_label_bbox_init(int32_t* bbox, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) {
+        bbox[4 * i + 0] = INT32_MAX;
+        bbox[4 * i + 1] = INT32_MAX;
+        bbox[4 * i + 2] = -1;
+        bbox[4 * i + 3] = -1;
+    }
+}
+
+__global__ void k_label_bbox_finish(int32_t* bbox, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n && bbox[4 * i + 2] < 0) bbox[4 * i + 0] = bbox[4 * i + 1] = -1;
+}
+
+// Wave-wide min/max of the lanes' boxes, then four atomics from lane 0.
+__device__ __forceinline__ void bbox_commit(int32_t* __restrict__ row, int xmin, int ymin, int xmax, int ymax) {
+    for (int off = 32; off > 0; off >>= 1) {
+        xmin = min(xmin, __shfl_xor(xmin, off));
+        ymin = min(ymin, __shfl_xor(ymin, off));
+        xmax = max(xmax, __shfl_xor(xmax, off));
+        ymax = max(ymax, __shfl_xor(ymax, off));
+    }
+    if ((threadIdx.x & 63) == 0 && xmax >= 0) {
+        atomicMin(&row[0], xmin);
+        atomicMin(&row[1], ymin);
+        atomicMax(&row[2], xmax + 1);
+        atomicMax(&row[3], ymax + 1);
+    }
+}
+
+// Block = one V tap tile (one 16-row composite band the overlay touches) of
+// one item; its four waves stride over the 16-column tiles.
+//
+// The band, tile, header, bias, tap block and T group addressing below
+// repeats ipp_pipe.hip's vblend_block, which is the source of truth: a change
+// of the tap tile or T layout there must be repeated here (tests/
+// test_gpu_labels.py compares the boxes with the resized overlay's alpha).
+//   A = the tile's taps, one byte plane per MFMA (lane l: row l&15, T rows
+//       16(l>>4)..+15 of the K step);
+//   B = 64 T rows × 16 overlay columns of alpha: dword 3 (byte offset 12) of
+//       the lane's four 16-B T groups;
+//   D lane l = column l&15, rows 4(l>>4)..+3.
+// One accumulator per tap byte plane over a runtime K loop (every nK the
+// planner emits; T is read once), the row bias in plane 0's initial value,
+// then the Horner step over the planes (planes3) — vblend_block's generic
+// form for channel 3 alone: 3 MFMAs per K step.
+__global__ void __launch_bounds__(256)
+k_pipe_overlay_bbox(const uint8_t* __restrict__ tmp, const int32_t* __restrict__ coefs,
+                    const ipp_pipe_desc* __restrict__ descs, FastDiv tiles_y, int alpha_min,
+                    int32_t* __restrict__ bbox) {
+    const uint32_t b = xcd_remap(blockIdx.x, gridDim.x);
+    const int im = (int)fdiv(b, tiles_y);
+    const int ty = (int)(b - (uint32_t)im * tiles_y.d);
+    const ipp_paste_desc p = descs[im].p;
+    // the overlay's bands [vb0, vb1) (paste_bands)
+    const int vb0 = (p.y >> 4) << 4;
+    const int vb1 = max(min(p.bg_h, ((p.y + p.ov_h + 15) >> 4) << 4), vb0);
+    const int y0 = vb0 + ty * LBR;
+    if (y0 >= vb1 || y0 >= p.bg_h) return;  // block-uniform
+    const int nrows = min(LBR, p.bg_h - y0);
+    const int oy_lo = max(0, y0 - p.y), oy_hi = min(p.ov_h, y0 + nrows - p.y);
+    if (oy_lo >= oy_hi) return;  // block-uniform
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+
+    const ipp_resample_desc v = descs[im].v;
+    const int phase = p.y & 15;
+    const int ntiles = (v.out_len + phase + 15) >> 4;
+    const int t = (y0 - p.y + phase) >> 4;  // the band's tap tile
+    const int4* thdr = reinterpret_cast<const int4*>(coefs + v.coef_off);
+    const int32_t* tbias = coefs + v.coef_off + 4 * (int64_t)ntiles;
+    const uint4* tblk = reinterpret_cast<const uint4*>(coefs + v.coef_off + 20 * (int64_t)ntiles);
+    int4 th = thdr[t];
+    th.x = __builtin_amdgcn_readfirstlane(th.x);  // first T row of the tile's window
+    th.y = __builtin_amdgcn_readfirstlane(th.y);  // K steps
+    th.z = __builtin_amdgcn_readfirstlane(th.z);  // first tap block
+    const int ctiles = (p.ov_w + 15) >> 4;
+    const int64_t gstride = v.src_pitch >> 4;  // 16-B groups per T group row
+    const int x_l = lane & 15;
+    int32_t rb[4];  // the row biases
+#pragma unroll
+    for (int r = 0; r < 4; ++r) rb[r] = tbias[16 * t + 4 * (lane >> 4) + r];
+    const int gbase = (th.x + 16 * (lane >> 4)) >> 2;
+    // byte 12 of T group (row group gbase, column 0): the alpha dword
+    const uint8_t* abase = tmp + v.src_off + gbase * gstride * 16 + 12;
+
+    int xmin = INT32_MAX, ymin = INT32_MAX, xmax = -1, ymax = -1;
+    for (int ct = wave; ct < ctiles; ct += 4) {
+        const int x = 16 * ct + x_l;
+        const int xs = min(x, p.ov_w - 1);
+        const uint8_t* aq = abase + (int64_t)xs * 16;
+        i32x4 acc[3];
+        acc[0] = i32x4{rb[0], rb[1], rb[2], rb[3]};
+        acc[1] = i32x4{0, 0, 0, 0};
+        acc[2] = i32x4{0, 0, 0, 0};
+#pragma unroll 1
+        for (int ks = 0; ks < th.y; ++ks) {
+            i32x4 bq;
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                bq[j] = *reinterpret_cast<const int32_t*>(aq + (16 * ks + j) * gstride * 16);
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                const i32x4 a = __builtin_bit_cast(i32x4, tblk[th.z + (ks * 3 + q) * 64 + lane]);
+                acc[q] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, bq, acc[q], 0, 0, 0);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            // plain code reads the accumulators (planes3)
+            const int32_t s = planes3(acc[0][r], acc[1][r], acc[2][r]);
+            const int32_t a = min(max(s >> 22, 0), 255);  // Resample.c clip8
+            const int o = y0 + 4 * (lane >> 4) + r - p.y;  // overlay row 16 t - phase + tile row
+            if (x < p.ov_w && o >= oy_lo && o < oy_hi && a >= alpha_min) {
+                xmin = min(xmin, x);
+                xmax = max(xmax, x);
+                ymin = min(ymin, o);
+                ymax = max(ymax, o);
+            }
+        }
+    }
+    bbox_commit(bbox + 4 * (int64_t)im, xmin, ymin, xmax, ymax);
+}
+
+// ipp_alpha_bbox's tiling (ipp_gather.hip k_alpha_bbox): 64×16 pixels per
+// block, 4 pixels of one row per thread.
+constexpr int BT_W = 64, BT_H = 16, BT_PX = 4;
+
+__global__ void __launch_bounds__(256)
+k_alpha_bbox_min(const uint8_t* __restrict__ img, const ipp_image_desc* __restrict__ descs, int tiles_x,
+                 int tiles_y, int alpha_min, int32_t* __restrict__ bbox) {
+    const uint32_t b = xcd_remap(blockIdx.x, gridDim.x);
+    const int per_img = tiles_x * tiles_y;
+    const int im = b / per_img;
+    const int t = b - im * per_img;
+    const int ty = t / tiles_x, tx = t - ty * tiles_x;
+    const ipp_image_desc d = descs[im];
+    const int y = ty * BT_H + (int)(threadIdx.x >> 4);
+    const int x0 = tx * BT_W + (int)(threadIdx.x & 15) * BT_PX;
+    int xmin = INT32_MAX, ymin = INT32_MAX, xmax = -1, ymax = -1;
+    // images without an alpha band (cn other than 2 or 4) have no visible pixel
+    if (y < d.h && (d.cn == 2 || d.cn == 4)) {
+        const uint8_t* row = img + d.off + (int64_t)y * d.pitch;
+        for (int k = 0; k < BT_PX; ++k) {
+            const int x = x0 + k;
+            if (x < d.w && (int)row[(int64_t)x * d.cn + d.cn - 1] >= alpha_min) {
+                xmin = min(xmin, x);
+                xmax = max(xmax, x);
+                ymin = min(ymin, y);
+                ymax = max(ymax, y);
+            }
+        }
+    }
+    bbox_commit(bbox + 4 * (int64_t)im, xmin, ymin, xmax, ymax);
+}
+
+}  // namespace
+
+extern "C" int ipp_pipe_overlay_bbox(const uint8_t* tmp, const int32_t* coefs, const ipp_pipe_desc* descs,
+                                     int32_t n_images, int32_t max_ov_w, int32_t max_ov_h, int32_t alpha_min,
+                                     int32_t tap_format, int32_t* bbox, void* stream) {
+    if (alpha_min < 1 || alpha_min > 255 || tap_format != IPP_TAPS_MFMA) return IPP_E_ARG;
+    if (!tmp || !coefs || !descs || !bbox || n_images < 0 || max_ov_w <= 0 || max_ov_h <= 0) return IPP_E_ARG;
+    if (n_images == 0) return IPP_OK;
+    // an overlay of height H at any y spans at most ceil((15 + H) / 16) bands
+    const int tyb = (max_ov_h + 15 + LBR - 1) / LBR;
+    const int64_t nb = (int64_t)tyb * n_images;
+    if (nb >= INT32_MAX) return IPP_E_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    const int ib = (n_images + 255) / 256;
+    hipLaunchKernelGGL(k_label_bbox_init, dim3(ib), dim3(256), 0, s, bbox, n_images);
+    hipLaunchKernelGGL(k_pipe_overlay_bbox, dim3((uint32_t)nb), dim3(256), 0, s, tmp, coefs, descs,
+                       fast_div((uint32_t)tyb), alpha_min, bbox);
+    hipLaunchKernelGGL(k_label_bbox_finish, dim3(ib), dim3(256), 0, s, bbox, n_images);
+    IPP_CHECK_LAUNCH();
+    return IPP_OK;
+}
+
+extern "C" int ipp_alpha_bbox_min(const uint8_t* img, const ipp_image_desc* descs, int32_t n_images,
+                                  int32_t max_w, int32_t max_h, int32_t alpha_min, int32_t* bbox, void* stream) {
+    if (alpha_min < 1 || alpha_min > 255) return IPP_E_ARG;
+    if (!img || !descs || !bbox || n_images < 0 || max_w <= 0 || max_h <= 0) return IPP_E_ARG;
+    if (n_images == 0) return IPP_OK;
+    const int tx = (max_w + BT_W - 1) / BT_W, ty = (max_h + BT_H - 1) / BT_H;
+    const int64_t blocks = (int64_t)tx * ty * n_images;
+    if (blocks >= (int64_t)INT32_MAX) return IPP_E_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    const int ib = (n_images + 255) / 256;
+    hipLaunchKernelGGL(k_label_bbox_init, dim3(ib), dim3(256), 0, s, bbox, n_images);
+    hipLaunchKernelGGL(k_alpha_bbox_min, dim3((uint32_t)blocks), dim3(256), 0, s, img, descs, tx, ty, alpha_min,
+                       bbox);
+    hipLaunchKernelGGL(k_label_bbox_finish, dim3(ib), dim3(256), 0, s, bbox, n_images);
+    IPP_CHECK_LAUNCH();
+    return IPP_OK;
+}

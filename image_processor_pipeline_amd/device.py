@@ -243,6 +243,53 @@ def alpha_bbox(imgs: Sequence[torch.Tensor]) -> List[Optional[Tuple[int, int, in
     return [None if r[0] < 0 else tuple(int(v) for v in r) for r in bb]
 
 
+def check_alpha_min(alpha_min) -> int:
+    if isinstance(alpha_min, bool) or not isinstance(alpha_min, (int, np.integer)) or not 1 <= alpha_min <= 255:
+        raise ValueError(f"alpha_min {alpha_min!r}: an integer in 1..255")
+    return int(alpha_min)
+
+
+def alpha_bbox_min_packed(buf: torch.Tensor, offs: Sequence[int], shapes: Sequence[Tuple[int, int, int]],
+                          alpha_min: int = 1) -> List[Optional[Tuple[int, int, int, int]]]:
+    """ipp_alpha_bbox_min over dense (h, w, cn) images at byte offsets `offs`
+    of one device buffer, one launch: the box (x0, y0, x1, y1) of each
+    image's pixels whose last band is >= alpha_min, None where there is none."""
+    alpha_min = check_alpha_min(alpha_min)
+    _require_cuda(buf, "alpha_bbox_min")
+    n = len(offs)
+    if n == 0:
+        return []
+    d = np.zeros(n, N.IMAGE_DESC)
+    for i, (off, (h, w, cn)) in enumerate(zip(offs, shapes)):
+        if cn not in (2, 4):
+            raise ValueError(f"alpha_bbox_min: image {i} has {cn} channels (an alpha band needs 2 or 4)")
+        d[i]["off"], d[i]["w"], d[i]["h"], d[i]["pitch"], d[i]["cn"] = off, w, h, w * cn, cn
+    bbox = torch.empty(4 * n, dtype=torch.int32, device=buf.device)
+    dd = _to_dev(d, buf.device)
+    N.check(N.load().ipp_alpha_bbox_min(buf.data_ptr(), dd.data_ptr(), n, max(int(s[1]) for s in shapes),
+                                        max(int(s[0]) for s in shapes), alpha_min, bbox.data_ptr(),
+                                        _stream(buf.device)), "ipp_alpha_bbox_min")
+    bb = bbox.cpu().numpy().reshape(n, 4)
+    return [None if r[0] < 0 else tuple(int(v) for v in r) for r in bb]
+
+
+def alpha_bbox_min(imgs: Sequence[torch.Tensor], alpha_min: int = 1) -> List[Optional[Tuple[int, int, int, int]]]:
+    """alpha_bbox with a threshold, for the tight YOLO box of a pasted
+    overlay (overlays.py:139 pastes through the overlay's alpha): (h, w, 2|4)
+    images, last band >= alpha_min."""
+    alpha_min = check_alpha_min(alpha_min)
+    if len(imgs) == 0:
+        return []
+    flat, offs, off = [], [], 0
+    for im in imgs:
+        _require_cuda(im, "alpha_bbox_min")
+        flat.append(im.contiguous().reshape(-1))
+        offs.append(off)
+        off += im.numel()
+    buf = torch.cat(flat) if len(imgs) > 1 else flat[0]
+    return alpha_bbox_min_packed(buf, offs, [tuple(int(v) for v in im.shape) for im in imgs], alpha_min)
+
+
 # ---------------------------------------------------------------------------
 # HSV range mask (filtres_liste.py:84-134)
 # ---------------------------------------------------------------------------

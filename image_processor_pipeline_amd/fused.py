@@ -14,6 +14,12 @@ Here one host planning pass draws every random parameter in the reference's
 draw order (``draw_params``) and fills one ``ipp_pipe_desc`` per item; the
 device work is two launches for the whole batch (``ipp_pipe_hpass_bgcopy``,
 ``ipp_pipe_vblend_bands``).  Intermediate cut-outs never touch HBM.
+
+The reference's last step also writes one YOLO label per composite
+(overlays.py:141-149): ``yolo_labels`` formats them from the plan, and
+``PipeRunner.run_labelled`` / ``overlay_bboxes`` give the tight box of what
+is visible of each overlay (``ipp_pipe_overlay_bbox``, a third launch between
+the two, opt-in).
 """
 from __future__ import annotations
 
@@ -30,6 +36,8 @@ import torch
 from . import _native as N
 from . import geometry as G
 from .device import SYM_FLIP, _stream, _to_dev
+from .device import check_alpha_min as _check_alpha_min
+from .labels_math import xyxy2xywhn
 
 ALL_SYMS = ("o", "h", "v", "hv")
 H_RING_COLUMNS = 512   # ipp_pipe.hip RING
@@ -91,6 +99,12 @@ class PipePlan:
         it = self.items
         return [ItemParams(float(a), self.sym_pool[s], int(b), float(r), int(x), int(y))
                 for a, s, b, r, x, y in zip(it["angle"], it["sym"], it["bg_index"], it["ratio"], it["x"], it["y"])]
+
+    @property
+    def order(self) -> np.ndarray:
+        """order[i] = item index of descriptor i: the planner groups the
+        descriptors by background with a stable sort (ipp_plan.cpp)."""
+        return np.argsort(self.items["bg_index"], kind="stable")
 
     @property
     def cut_dims(self) -> List[Tuple[int, int]]:
@@ -299,6 +313,45 @@ def plan_taps(plan: PipePlan, device, stream=None) -> Tuple[torch.Tensor, int]:
     return coefs, int(stats[0])
 
 
+def yolo_label(class_id: int, box: Tuple[int, int, int, int], bg_w: int, bg_h: int) -> str:
+    """One YOLO label line for the pixel box (x0, y0, x1, y1) on a bg_w×bg_h
+    composite, formatted as the reference does (overlays.py:143-149)."""
+    cx, cy, w, h = xyxy2xywhn(np.array(box).reshape(1, 4), bg_w, bg_h)[0]
+    return f"{class_id} {cx:.6f} {cy:.6f} {w:.6f} {h:.6f}"
+
+
+def yolo_labels(plan: PipePlan, class_id: int = 0, boxes: Optional[np.ndarray] = None) -> List[Optional[str]]:
+    """The YOLO label of every item's composite, in item order.
+
+    ``boxes=None``: the reference's label, the resized overlay's rectangle
+    (x, y, x + ov_w, y + ov_h) (overlays.py:141-149) — byte for byte what the
+    per-file plugin writes.  ``boxes`` = the (n, 4) array of
+    ``PipeRunner.overlay_bboxes`` (overlay coordinates): the tight label, the
+    box (x + x0, y + y0, x + x1, y + y1) through the same conversion.  An
+    item whose row is all -1 has no visible overlay pixel and gets ``None``:
+    the caller writes an empty label file for it, the YOLO convention for an
+    image without objects."""
+    it = plan.items
+    n = len(it)
+    if boxes is not None:
+        boxes = np.asarray(boxes)
+        if boxes.shape != (n, 4):
+            raise ValueError(f"boxes of shape {boxes.shape} for {n} items")
+    out: List[Optional[str]] = []
+    for i in range(n):
+        x, y = int(it["x"][i]), int(it["y"][i])
+        if boxes is None:
+            box = (x, y, x + int(it["ov_w"][i]), y + int(it["ov_h"][i]))
+        elif boxes[i][0] < 0:
+            out.append(None)
+            continue
+        else:
+            x0, y0, x1, y1 = (int(v) for v in boxes[i])
+            box = (x + x0, y + y0, x + x1, y + y1)
+        out.append(yolo_label(class_id, box, plan.bg_w, plan.bg_h))
+    return out
+
+
 def overlap_bounds(n: int, parts: int, ratio: float = 1.0, group: int = N.IPP_PIPE_COPY_GROUP) -> List[int]:
     """Item-range bounds of PipeRunner.run_overlapped: `parts` ranges of whole
     copy groups, range k holding a share proportional to ratio**k; bounds[0]
@@ -323,6 +376,7 @@ class PipeRunner:
         self.coefs, self.host_tiles = plan_taps(plan, self.device)
         self.tmp = torch.empty(plan.tmp_bytes, dtype=torch.uint8, device=self.device)
         self.lib = N.load()
+        self._hpass_done = False   # an H launch has filled tmp (overlay_bboxes needs it)
 
     def hpass_bgcopy(self, src: torch.Tensor, bgs: torch.Tensor, out: torch.Tensor, items=None) -> None:
         """H pass + the composite rows outside the overlay bands (split form);
@@ -333,6 +387,46 @@ class PipeRunner:
                                                self.descs.data_ptr() + i0 * p.descs.itemsize, n, p.max_out_w,
                                                p.max_rows, 3, N.np_ptr(p.hsv), p.tap_format, bgs.data_ptr(),
                                                out.data_ptr(), _stream(self.device)), "ipp_pipe_hpass_bgcopy")
+        self._hpass_done = True
+
+    def overlay_bboxes(self, alpha_min: int = 1, items=None) -> np.ndarray:
+        """Tight boxes of the resized overlays (ipp_pipe_overlay_bbox): (n, 4)
+        int32 rows (x0, y0, x1, y1), half-open, in overlay coordinates, of the
+        pixels whose alpha (the paste mask of overlays.py:139) is >=
+        alpha_min; an invisible overlay has the row (-1, -1, -1, -1).  Rows
+        are in item order.  It reads the H launch's scratch, so it runs after
+        ``hpass_bgcopy`` (before the next one refills the scratch) on the
+        current stream, and synchronises for the copy back.  `items` = (first,
+        count) of the descriptors, as for ``hpass_bgcopy``: the rows are then
+        those descriptors' items, by ascending item index."""
+        alpha_min = _check_alpha_min(alpha_min)
+        i0, n = items if items is not None else (0, len(self.plan.descs))
+        if n <= 0:
+            return np.zeros((0, 4), np.int32)
+        return self._bboxes_by_item(self._launch_bboxes(alpha_min, i0, n), i0, n)
+
+    def _launch_bboxes(self, alpha_min: int, i0: int, n: int) -> torch.Tensor:
+        """Queue ipp_pipe_overlay_bbox for descriptors [i0, i0 + n): the device
+        int32 boxes, in descriptor order."""
+        alpha_min = _check_alpha_min(alpha_min)
+        if not self._hpass_done:
+            raise N.NativeError("PipeRunner.overlay_bboxes: no H launch (hpass_bgcopy) has run on this runner")
+        p = self.plan
+        bbox = torch.empty(4 * max(n, 0), dtype=torch.int32, device=self.device)
+        N.check(self.lib.ipp_pipe_overlay_bbox(self.tmp.data_ptr(), self.coefs.data_ptr(),
+                                               self.descs.data_ptr() + i0 * p.descs.itemsize, n, p.max_ov_w,
+                                               p.max_ov_h, alpha_min, p.tap_format, bbox.data_ptr(),
+                                               _stream(self.device)), "ipp_pipe_overlay_bbox")
+        return bbox
+
+    def _bboxes_by_item(self, bbox: torch.Tensor, i0: int, n: int) -> np.ndarray:
+        """Copy the boxes back (synchronises) and order them by item index."""
+        by_desc = bbox.cpu().numpy().reshape(-1, 4)
+        # descriptor i0 + k holds item order[i0 + k]: row = its rank among the range's items
+        rank = np.argsort(np.argsort(self.plan.order[i0:i0 + n], kind="stable"), kind="stable")
+        out = np.empty_like(by_desc)
+        out[rank] = by_desc
+        return out
 
     def vblend_bands(self, bgs: torch.Tensor, out: torch.Tensor, items=None) -> None:
         """V pass + paste over the 16-row bands the overlay touches (split form)."""
@@ -392,6 +486,32 @@ class PipeRunner:
         self.hpass_bgcopy(src, bgs, out)
         self.vblend_bands(bgs, out)
         return out
+
+    def run_labelled(self, src: torch.Tensor, bgs: torch.Tensor, out: torch.Tensor, tight: bool = True,
+                     alpha_min: int = 1, class_id: int = 0) -> Tuple[torch.Tensor, List[Optional[str]]]:
+        """``run`` plus the YOLO label of every composite (``yolo_labels``),
+        in item order: H launch, box launch, V launch on the current stream.
+        ``tight=True``: the box of the overlay pixels with alpha >= alpha_min
+        (``overlay_bboxes``), None for an invisible overlay; ``tight=False``:
+        the reference's rectangle labels, nothing extra is launched."""
+        for t, name in ((src, "src"), (bgs, "bgs"), (out, "out")):
+            if not (t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()):
+                raise N.NativeUnavailable(f"PipeRunner.run_labelled: {name} must be a contiguous uint8 ROCm tensor")
+        if not self.split:
+            raise N.NativeError(f"PipeRunner.run_labelled: tap format {self.plan.tap_format} "
+                                "(the pipe takes IPP_TAPS_MFMA)")
+        if tight:
+            alpha_min = _check_alpha_min(alpha_min)
+        self.hpass_bgcopy(src, bgs, out)
+        if not tight:
+            self.vblend_bands(bgs, out)
+            return out, yolo_labels(self.plan, class_id)
+        # the V launch is queued before the boxes are copied back, so the
+        # host's wait for them covers it too
+        n = len(self.plan.descs)
+        bbox = self._launch_bboxes(alpha_min, 0, n)
+        self.vblend_bands(bgs, out)
+        return out, yolo_labels(self.plan, class_id, self._bboxes_by_item(bbox, 0, n))
 
 
 class PipeStream:

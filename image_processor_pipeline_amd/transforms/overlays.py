@@ -38,6 +38,18 @@ def _convert_to_yolo_bbox(img_width: int, img_height: int, box: Tuple[int, int, 
             (box[3] - box[1]) * dh)
 
 
+def _label_str(yolo_class_id: int, box: Optional[Tuple[int, int, int, int]], pos_x: int, pos_y: int,
+               bw: int, bh: int) -> str:
+    """overlays.py:143-149 for the box (x0, y0, x1, y1) of the overlay placed
+    at (pos_x, pos_y): the whole rectangle (0, 0, new_w, new_h) in the
+    reference; None (tight_bbox, nothing visible) gives the empty label."""
+    if box is None:
+        return ""
+    bbox = np.array([pos_x + box[0], pos_y + box[1], pos_x + box[2], pos_y + box[3]]).reshape(1, 4)
+    cx, cy, w_norm, h_norm = xyxy2xywhn(bbox, bw, bh)[0]
+    return f"{yolo_class_id} {cx:.6f} {cy:.6f} {w_norm:.6f} {h_norm:.6f}"
+
+
 @device_transform
 def paste_overlay_onto_background(
     overlay_path: Path,
@@ -46,8 +58,15 @@ def paste_overlay_onto_background(
     yolo_class_id: int = 0,
     scale_min: float = 0.15,
     scale_max: float = 0.30,
+    tight_bbox: bool = False,
+    alpha_min: int = 1,
     **options: Any,
 ) -> Optional[List[Path]]:
+    """``tight_bbox`` (not in the reference): the label's box is that of the
+    resized overlay's pixels with alpha >= ``alpha_min`` (1..255) instead of
+    its whole rectangle; an overlay without such a pixel gets an empty label
+    file (the YOLO convention for an image without objects).  The draws, the
+    composite, file names and messages do not depend on it."""
     image_target_dir, label_target_dir = utils._validate_dirs(output_dirs, nb_dirs=2)
     names = f"[{overlay_path.name} + {background_path.name}]"
     try:
@@ -80,9 +99,8 @@ def paste_overlay_onto_background(
         pos_y = random.randint(0, bh - new_h)
         comp = D.paste_blend(_rt.h2d(np.asarray(background)), resized, pos_x, pos_y)
         composite_image = Image.fromarray(_rt.d2h(comp), "RGB")
-        bbox = np.array([pos_x, pos_y, pos_x + new_w, pos_y + new_h]).reshape(1, 4)
-        cx, cy, w_norm, h_norm = xyxy2xywhn(bbox, bw, bh)[0]
-        yolo_label_str = f"{yolo_class_id} {cx:.6f} {cy:.6f} {w_norm:.6f} {h_norm:.6f}"
+        tight = D.alpha_bbox_min([resized], alpha_min)[0] if tight_bbox else (0, 0, new_w, new_h)
+        yolo_label_str = _label_str(yolo_class_id, tight, pos_x, pos_y, bw, bh)
     except ValueError as ve:
         print(f"Erreur de valeur {names}: {ve}")
         return None
@@ -112,12 +130,15 @@ def paste_overlay_onto_background(
 
 
 def _overlays_batch(arg_tuples, output_dirs: List[Path], threads: int = 1, yolo_class_id: int = 0,
-                    scale_min: float = 0.15, scale_max: float = 0.30, **options: Any) -> List:
+                    scale_min: float = 0.15, scale_max: float = 0.30, tight_bbox: bool = False,
+                    alpha_min: int = 1, **options: Any) -> List:
     """Batched paste_overlay_onto_background ('modulo' pairs): decode on host
     threads, the per-item draws (uniform ratio, then two randint) in pair
     order, ONE batched LANCZOS H + V + paste launch set for the chunk
     (batch_ops.overlays), encode + label on host threads.  Messages and
-    None results as in the per-file path."""
+    None results as in the per-file path.  ``tight_bbox``: the boxes come
+    from one more batched launch over the chunk's resized overlays
+    (ipp_alpha_bbox_min)."""
     image_target_dir, label_target_dir = utils._validate_dirs(output_dirs, nb_dirs=2)
 
     def load(args):
@@ -170,18 +191,26 @@ def _overlays_batch(arg_tuples, output_dirs: List[Path], threads: int = 1, yolo_
             bgs.append(bg)
             sizes.append((new_w, new_h))
             pos.append((pos_x, pos_y))
-        comps = BO.overlays(ovs, bgs, sizes, pos) if ovs else []
-        return [None if p is None else (comps[p[0]], p) for p in plans]
+        if tight_bbox:
+            try:
+                comps, boxes = BO.overlays(ovs, bgs, sizes, pos, bbox_alpha_min=alpha_min) if ovs else ([], [])
+            except ValueError as ve:   # (alpha_min out of range: every pair fails as in the per-file path)
+                for p, a in zip(plans, args):
+                    if p is not None:
+                        print(f"Erreur de valeur [{a[0].name} + {a[1].name}]: {ve}")
+                return [None] * len(plans)
+        else:
+            comps = BO.overlays(ovs, bgs, sizes, pos) if ovs else []
+            boxes = [(0, 0, w, h) for w, h in sizes]
+        return [None if p is None else (comps[p[0]], p, boxes[p[0]]) for p in plans]
 
     def save(args, _item, res):
         if res is None:
             return None
-        comp, (_, (new_w, new_h), (pos_x, pos_y), (bw, bh)) = res
+        comp, (_, (new_w, new_h), (pos_x, pos_y), (bw, bh)), box = res
         overlay_path, background_path = args[0], args[1]
         names = f"[{overlay_path.name} + {background_path.name}]"
-        bbox = np.array([pos_x, pos_y, pos_x + new_w, pos_y + new_h]).reshape(1, 4)
-        cx, cy, w_norm, h_norm = xyxy2xywhn(bbox, bw, bh)[0]
-        yolo_label_str = f"{yolo_class_id} {cx:.6f} {cy:.6f} {w_norm:.6f} {h_norm:.6f}"
+        yolo_label_str = _label_str(yolo_class_id, box, pos_x, pos_y, bw, bh)
         saved_paths: List[Path] = []
         img_output_path = Path(image_target_dir) / f"{overlay_path.stem}{background_path.suffix}"
         label_output_path = Path(label_target_dir) / f"{overlay_path.stem}.txt"

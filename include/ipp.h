@@ -270,6 +270,16 @@ int ipp_pipe_vblend_bands(const uint8_t* tmp, const uint8_t* bg, uint8_t* dst,
  * violated, see above).  Synchronises `stream`. */
 int ipp_pipe_status(int32_t* status, void* stream);
 
+/* After ipp_pipe_hpass_bgcopy on the same stream, before tmp is reused:
+ * bbox[4*i..] = (x0, y0, x1, y1), half-open, in OVERLAY coordinates, of the
+ * pixels of descriptor i's resized overlay whose alpha >= alpha_min (the alpha
+ * Pillow's resize(LANCZOS) gives the RGBA overlay, i.e. the paste mask of
+ * overlays.py:139); (-1,-1,-1,-1) when there is none.  1 <= alpha_min <= 255.
+ * Reads tmp and coefs only. */
+int ipp_pipe_overlay_bbox(const uint8_t* tmp, const int32_t* coefs, const ipp_pipe_desc* descs,
+                          int32_t n_images, int32_t max_ov_w, int32_t max_ov_h,
+                          int32_t alpha_min, int32_t tap_format, int32_t* bbox, void* stream);
+
 /* ------------------------------------------------------------------------ */
 /* K10-K13: pixels_isolés.keep_largest_component                             */
 /* :32 threshold(α,1,255) :35 connectedComponentsWithStats(8) :38-55 keep    */
@@ -323,6 +333,14 @@ int ipp_video_keep_largest(const uint8_t* frames, const ipp_image_desc* descs, i
  * bbox[i] = (x0, y0, x1, y1) or (-1,-1,-1,-1) when empty. */
 int ipp_alpha_bbox(const uint8_t* img, const ipp_image_desc* descs, int32_t n_images,
                    int32_t max_w, int32_t max_h, int32_t* bbox, void* stream);
+/* The thresholded form, for the tight YOLO box of a pasted overlay
+ * (overlays.py:139 pastes through the overlay's alpha): the box of the pixels
+ * whose last band is >= alpha_min, on 2- and 4-channel images (an image with
+ * another channel count has no alpha band and gets the all -1 row).
+ * 1 <= alpha_min <= 255; alpha_min = 1 equals ipp_alpha_bbox on such images. */
+int ipp_alpha_bbox_min(const uint8_t* img, const ipp_image_desc* descs, int32_t n_images,
+                       int32_t max_w, int32_t max_h, int32_t alpha_min, int32_t* bbox,
+                       void* stream);
 
 /* ------------------------------------------------------------------------ */
 /* Host-side planning (CPU).                                                 */
