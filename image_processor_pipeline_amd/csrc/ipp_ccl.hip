@@ -992,7 +992,11 @@ k_ccl_apply(uint8_t* __restrict__ img, const ipp_image_desc* __restrict__ descs,
 //     255 inside the component, 0 elsewhere) into the image's output slot,
 //     row by row in output order: 4 pixels per thread (three dword loads, one
 //     16-byte store), so output lines are written whole whatever the bbox's
-//     alignment to the 64-pixel tiles.
+//     alignment to the 64-pixel tiles.  Any frame width.  Live code: frames
+//     of more than CROP_ROWS_MAX_TILES_X tile columns (wider than 4096 px)
+//     take it instead of (b') k_ccl_crop_rows, and
+//     tests/test_gpu_parity.py test_video_chain_wide_frames_vs_oracle is its
+//     only coverage (narrower frames never launch it in the default build).
 __global__ void __launch_bounds__(64 * WAVES)
 k_ccl_inwords(const ipp_image_desc* __restrict__ descs, const ipp_ccl_work* __restrict__ works,
               uint8_t* __restrict__ scratch, const int32_t* __restrict__ bbox, int groups_per_img, int groups_x) {
@@ -1117,6 +1121,7 @@ constexpr int CROP_ROW_BLOCKS = IPP_CCL_CROP_ROW_BLOCKS;  // blocks per image (4
 #endif
 constexpr int CROP_SEG = 4 * 256;            // output pixels per wave iteration (4 × 64 lanes × 4)
 constexpr int CROP_CHUNKS = 3 * CROP_SEG / 16 + 1;  // 16-B source chunks one iteration may touch
+constexpr int CROP_ROWS_MAX_TILES_X = TW;    // widest frame, in tile columns: a lane per mask word of a row
 
 struct CropRowsLds {
     uint32_t stage[WAVES][CROP_CHUNKS * 4];  // source span of the wave's iteration
@@ -1144,11 +1149,19 @@ k_ccl_crop_rows(const uint8_t* __restrict__ img, const ipp_image_desc* __restric
     const Frame f = frame_of(d);
     const Work k = work_of(scratch, works[im]);
     const int cw = bx1 - bx0;
-    const int tc0 = bx0 >> 6, ntc = ((bx1 - 1) >> 6) - tc0 + 1;  // ≤ 61 tile columns
+    // ntc ≤ CROP_ROWS_MAX_TILES_X = 64, one mask word per lane and words[] of
+    // TW + 2: ipp_video_keep_largest launches this kernel only for frames of
+    // at most that many tile columns (≤ 4096 px) and k_ccl_crop_stream for
+    // wider ones (tests/test_gpu_parity.py
+    // test_video_chain_wide_frames_vs_oracle: 65, 69 and 120 tile columns).
+    const int tc0 = bx0 >> 6, ntc = ((bx1 - 1) >> 6) - tc0 + 1;
     // The buffer starts at the 16-B aligned address at or below the frame
     // (fmis bytes before it, in the same aligned chunk) and ends with the
     // 4-aligned dword holding the frame's last byte: the range check works per
     // dword (a straddling one reads 0), and neither extension crosses a page.
+    // The last 16-byte load of a frame whose fmis + fbytes is no multiple of
+    // 16 straddles nrec: its dwords below nrec must come back whole
+    // (tests/test_gpu_parity.py test_video_chain_tail_chunk_vs_oracle).
     const uint8_t* fbase = img + d.off;
     const uint32_t fmis = (uint32_t)(reinterpret_cast<uintptr_t>(fbase) & 15u);
     const uint32_t fbytes = (uint32_t)((int64_t)d.h * d.pitch);
@@ -1397,7 +1410,9 @@ extern "C" int ipp_video_keep_largest(const uint8_t* frames, const ipp_image_des
     if (rc != IPP_OK) return rc;
     hipLaunchKernelGGL(k_ccl_inwords, L.group_grid, dim3(64 * WAVES), 0, s, descs, works, scratch, bbox,
                        L.groups_per_img, L.groups_x);
-    if (IPP_CCL_CROP_ROWS)
+    // k_ccl_crop_rows holds a row's mask words one per lane: frames wider than
+    // 64 tile columns take the item stream, which has no width limit
+    if (IPP_CCL_CROP_ROWS && L.tiles_x <= CROP_ROWS_MAX_TILES_X)
         hipLaunchKernelGGL(k_ccl_crop_rows, dim3((uint32_t)((int64_t)CROP_ROW_BLOCKS * n_images)), dim3(256), 0, s,
                            frames, descs, works, scratch, bbox, out, out_descs);
     else

@@ -378,6 +378,14 @@ class PipeRunner:
         self.lib = N.load()
         self._hpass_done = False   # an H launch has filled tmp (overlay_bboxes needs it)
 
+    @staticmethod
+    def _check_tensors(caller: str, src: torch.Tensor, bgs: torch.Tensor, out: torch.Tensor) -> None:
+        """The entry points that take tensors hand their raw pointers to the
+        launches: each must be a contiguous uint8 tensor on the GPU."""
+        for t, name in ((src, "src"), (bgs, "bgs"), (out, "out")):
+            if not (t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()):
+                raise N.NativeUnavailable(f"PipeRunner.{caller}: {name} must be a contiguous uint8 ROCm tensor")
+
     def hpass_bgcopy(self, src: torch.Tensor, bgs: torch.Tensor, out: torch.Tensor, items=None) -> None:
         """H pass + the composite rows outside the overlay bands (split form);
         `items` = (first, count) of the descriptors in processing order."""
@@ -445,6 +453,7 @@ class PipeRunner:
         HBM streaming overlaps the texture-bound H pass.  The ranges are whole
         copy groups of the H launch; the caller's stream waits for the last V
         launch."""
+        self._check_tensors("run_overlapped", src, bgs, out)
         bounds = overlap_bounds(len(self.plan.descs), parts, ratio)
         main = torch.cuda.current_stream(self.device)
         if getattr(self, "_vstream", None) is None:
@@ -478,9 +487,7 @@ class PipeRunner:
         return self.plan.tap_format == N.IPP_TAPS_MFMA
 
     def run(self, src: torch.Tensor, bgs: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
-        for t, name in ((src, "src"), (bgs, "bgs"), (out, "out")):
-            if not (t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()):
-                raise N.NativeUnavailable(f"PipeRunner.run: {name} must be a contiguous uint8 ROCm tensor")
+        self._check_tensors("run", src, bgs, out)
         if not self.split:
             raise N.NativeError(f"PipeRunner.run: tap format {self.plan.tap_format} (the pipe takes IPP_TAPS_MFMA)")
         self.hpass_bgcopy(src, bgs, out)
@@ -494,9 +501,7 @@ class PipeRunner:
         ``tight=True``: the box of the overlay pixels with alpha >= alpha_min
         (``overlay_bboxes``), None for an invisible overlay; ``tight=False``:
         the reference's rectangle labels, nothing extra is launched."""
-        for t, name in ((src, "src"), (bgs, "bgs"), (out, "out")):
-            if not (t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()):
-                raise N.NativeUnavailable(f"PipeRunner.run_labelled: {name} must be a contiguous uint8 ROCm tensor")
+        self._check_tensors("run_labelled", src, bgs, out)
         if not self.split:
             raise N.NativeError(f"PipeRunner.run_labelled: tap format {self.plan.tap_format} "
                                 "(the pipe takes IPP_TAPS_MFMA)")

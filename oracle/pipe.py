@@ -23,10 +23,16 @@ def cut_out(src_rgb: np.ndarray, params, cfg) -> np.ndarray:
     return np.concatenate([fl[..., :3], alpha[..., None]], axis=-1)
 
 
-def pipe_item(src_rgb: np.ndarray, bgs: np.ndarray, params, cfg) -> np.ndarray:
+def overlay(src_rgb: np.ndarray, bg_hw, params, cfg) -> np.ndarray:
+    """Stage 5 before the paste: the cut-out resized (LANCZOS, RGBA) to the
+    overlay's size on a background of bg_hw = (bh, bw)."""
     m = cut_out(src_rgb, params, cfg)
-    bg = bgs[params.bg_index]
-    bh, bw = bg.shape[:2]
+    bh, bw = bg_hw
     nw, nh = ops.overlay_geometry(m.shape[1], m.shape[0], bw, bh, params.ratio)
-    ov = ops.resize_lanczos_rgba(m, nw, nh)
+    return ops.resize_lanczos_rgba(m, nw, nh)
+
+
+def pipe_item(src_rgb: np.ndarray, bgs: np.ndarray, params, cfg) -> np.ndarray:
+    bg = bgs[params.bg_index]
+    ov = overlay(src_rgb, bg.shape[:2], params, cfg)
     return ops.paste_rgba_onto_rgb(bg, ov, params.x, params.y)

@@ -250,3 +250,31 @@ def test_overlapped_item_ranges_equal_sequential(parts, ratio):
     runner.run_overlapped(src, bgs, out, parts, ratio)
     torch.cuda.synchronize()
     assert torch.equal(out, ref)
+
+
+def test_overlapped_rejects_unusable_tensors():
+    """PipeRunner.run_overlapped hands raw pointers to two streams, so it makes
+    the same check as run and run_labelled before anything is launched: a
+    non-contiguous out (a sliced view), an int8 src and a host bgs each raise
+    NativeUnavailable naming the caller, and out (pre-filled with 7s) is
+    unchanged afterwards."""
+    from image_processor_pipeline_amd import _native as N
+    from image_processor_pipeline_amd import fused
+    n, S, K = 4, 64, 2
+    g = torch.Generator().manual_seed(6)
+    src = torch.randint(0, 256, (n, S, S, 3), dtype=torch.uint8, generator=g).to(DEV)
+    bgs = torch.randint(0, 256, (K, S, S, 3), dtype=torch.uint8, generator=g).to(DEV)
+    runner = fused.PipeRunner(fused.plan_pipe((S, S), n, (S, S), K, fused.PipeConfig(margins=(4, 4, 4, 4)), seed=3),
+                              DEV)
+    wide = torch.full((n, S, 2 * S, 3), 7, dtype=torch.uint8, device=DEV)
+    out = torch.full((n, S, S, 3), 7, dtype=torch.uint8, device=DEV)
+    sliced = wide[:, :, :S]
+    assert sliced.shape == out.shape and not sliced.is_contiguous()
+    cases = [("out", (src, bgs, sliced)),
+             ("src", (src.view(torch.int8), bgs, out)),
+             ("bgs", (src, bgs.cpu(), out))]
+    for name, (s, b, o) in cases:
+        with pytest.raises(N.NativeUnavailable, match=f"run_overlapped: {name} must be"):
+            runner.run_overlapped(s, b, o, 2)
+        torch.cuda.synchronize()
+        assert bool((wide == 7).all()) and bool((out == 7).all()), name

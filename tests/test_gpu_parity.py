@@ -344,6 +344,112 @@ def test_pipe_wide_overlays_vs_oracle(D):
         assert np.array_equal(got[i], opipe.pipe_item(src[i], bgs, plan.params[i], cfg)), i
 
 
+# (src h, src w, [(angle, sym, ratio, expected ov_w), ...]) of
+# test_pipe_widest_overlays_vs_oracle, on a 1000×160 background with margins
+# (3, 5, 2, 7); the ratios sit in the middle of the interval that gives the
+# width (found by a host-side search over fused.item_geometry).
+_WIDEST_BG = (160, 1000)
+_WIDEST_MARGINS = (3, 5, 2, 7)
+_WIDEST_BATCHES = [
+    (56, 409, [(1.0, "h", 0.9779, 977), (178.0, "hv", 0.9944, 992)]),       # up-scaled ×2.4, non-table V launch
+    (180, 1415, [(359.0, "v", 0.9847, 984), (1.0, "o", 0.9919, 991)]),      # down-scaled ×0.7, non-table V launch
+    (60, 412, [(0.0, "h", 0.9761, 976), (180.0, "v", 0.6, None)]),          # the table path's last width
+]
+
+
+def _black_speckled_sources(rng, n, H, W):
+    """Random bytes with 3 % scattered pure-black pixels and a few black
+    rectangles (as conftest.config3_black_source, at any size)."""
+    src = rng.integers(0, 256, (n, H, W, 3), np.uint8)
+    for i in range(n):
+        for _ in range(6):
+            y0, x0 = int(rng.integers(0, H - 4)), int(rng.integers(0, W - 8))
+            hh, ww = int(rng.integers(3, max(4, H // 3))), int(rng.integers(6, max(7, W // 6)))
+            src[i, y0:y0 + hh, x0:x0 + ww] = 0
+        src[i][rng.random((H, W)) < 0.03] = 0
+    return src
+
+
+def _widest_batch(k):
+    """Batch k of _WIDEST_BATCHES: (src, bgs, cfg, plan, expected widths);
+    host work only.  Overlays alternate between flush with the background's
+    left / top and right / bottom borders."""
+    from image_processor_pipeline_amd import fused
+    from image_processor_pipeline_amd import geometry as G
+    from tests.conftest import BLACK_RANGE
+    H, W, items = _WIDEST_BATCHES[k]
+    bh, bw = _WIDEST_BG
+    cfg = fused.PipeConfig(margins=_WIDEST_MARGINS, hsv_ranges=[BLACK_RANGE])
+    rng = np.random.default_rng(9770 + k)
+    src = _black_speckled_sources(rng, len(items), H, W)
+    bgs = rng.integers(0, 256, (2, bh, bw, 3), np.uint8)
+    mt, mb, ml, mr = G.crop_margins(H, W, cfg.margins)
+    params = []
+    for i, (angle, sym, ratio, _) in enumerate(items):
+        p = fused.ItemParams(angle=angle, sym=sym, bg_index=(i + k) % 2, ratio=ratio)
+        _, _, (nw, nh) = fused.item_geometry(W - ml - mr, H - mt - mb, angle, ratio, bw, bh, i)
+        p.x = 0 if i % 2 == 0 else bw - nw
+        p.y = 0 if i % 2 == 0 else bh - nh
+        params.append(p)
+    plan = fused.plan_pipe((H, W), len(items), (bh, bw), 2, cfg, params=params)
+    return src, bgs, cfg, plan, [it[3] for it in items]
+
+
+def _partial_alphas(src, bgs, cfg, plan):
+    """Distinct α values strictly between 0 and 255 in the oracle's resized
+    overlays of a batch."""
+    seen = set()
+    for i, p in enumerate(plan.params):
+        a = np.unique(opipe.overlay(src[i], bgs.shape[1:3], p, cfg)[..., 3])
+        seen.update(int(v) for v in a if 0 < v < 255)
+    return seen
+
+
+@pytest.mark.parametrize("k", range(len(_WIDEST_BATCHES)))
+def test_pipe_widest_overlays_vs_oracle(D, k):
+    """Both sides of ipp_pipe_vblend_bands' switch between its two V kernels:
+    with max_ov_w in 977..992 (992 = IPP_PIPE_MAX_OV_W) the 16 overlay rows
+    leave no room in 64 KB of LDS for the magic-divisor table, and
+    k_pipe_vblend_mfma<false> unpremultiplies with a reciprocal and two
+    fix-ups instead; 976 px is the table path's last width.  Overlays of 977
+    and 992 px up-scaled from a 409-px source, of 984 and 991 px down-scaled
+    from a 1415-px one (several angles and flips), flush with the left and
+    right borders of a 1000×160 background, and a batch whose widest overlay
+    is 976 px.  The exclusion range holds exactly black and the sources have
+    scattered black pixels and rectangles, so LANCZOS leaves partial α (the
+    unpremultiply's divisors) all over the overlay: at least 128 distinct
+    0 < α < 255 per batch (reference-only counts: 254, 254 and 254).  `out`
+    is pre-filled with junk; every composite byte equals the oracle's.  A
+    993-px overlay is still refused by plan_pipe."""
+    from image_processor_pipeline_amd import fused
+    from tests.conftest import BLACK_RANGE
+    src, bgs, cfg, plan, widths = _widest_batch(k)
+    table = k == 2
+    for i, w in enumerate(widths):
+        if w is not None:
+            assert plan.ov_dims[i][1] == w, (i, plan.ov_dims[i])
+    if table:
+        assert plan.max_ov_w == 976
+    else:
+        assert 977 <= plan.max_ov_w <= 992 and plan.max_ov_w == max(widths)
+    assert all(p.x == 0 or p.x + w == plan.bg_w for p, (_, w) in zip(plan.params, plan.ov_dims))
+    alphas = _partial_alphas(src, bgs, cfg, plan)
+    print("distinct partial alphas:", len(alphas))
+    assert len(alphas) >= 128
+    if k == 0:
+        p993 = fused.ItemParams(angle=0.0, sym="o", bg_index=0, ratio=1.0)
+        assert fused.item_geometry(399 - 9, 50 - 8, 0.0, 1.0, 1000, 160)[2][0] == 993
+        with pytest.raises(ValueError, match="993 px exceeds the fused pipe's limit"):
+            fused.plan_pipe((50, 399), 1, _WIDEST_BG, 2, fused.PipeConfig(margins=_WIDEST_MARGINS,
+                                                                          hsv_ranges=[BLACK_RANGE]), params=[p993])
+    runner = fused.PipeRunner(plan, DEV)
+    out = torch.full((len(src),) + bgs.shape[1:], 7, dtype=torch.uint8, device=DEV)
+    runner.run(_t(src), _t(bgs), out)
+    got = out.cpu().numpy()
+    for i in range(len(src)):
+        assert np.array_equal(got[i], opipe.pipe_item(src[i], bgs, plan.params[i], cfg)), (k, i)
+
+
 def test_pipe_stream_equals_runner(D):
     """fused.PipeStream (the bench's streaming leg) on a high-priority and on
     the default-priority stream: every batch has its own plan; the last
@@ -593,6 +699,139 @@ def test_video_chain_uniform_colour_slots_vs_oracle(D):
             assert res[i] is None, i
         else:
             assert res[i] is not None and np.array_equal(res[i], exp), i
+
+
+_KEEP = np.array([220, 140, 40], np.uint8)        # kept colour (blue-ish)
+_DROP = np.array([24, 18, 30], np.uint8)          # excluded (dark)
+
+
+def _wide_frames(kind, h, w, rng):
+    """Two h×w frames of test_video_chain_wide_frames_vs_oracle."""
+    n = 2
+    if kind == "noise":
+        return np.where((rng.random((n, h, w)) < 0.6)[..., None], _KEEP, _DROP).astype(np.uint8)
+    fr = np.empty((n, h, w, 3), np.uint8)
+    fr[:] = _DROP
+    for i in range(n):
+        if kind == "band":
+            # a kept band over the whole width: rows 62-64 straddle the two
+            # tile rows (frame 0), rows 66-68 lie in the last one (frame 1)
+            y0 = 62 if i == 0 else 66
+            fr[i, y0:y0 + 3] = _KEEP
+            for x in (4095, 4096, w - 1):          # single pixels on the row above, 8-adjacent to the band
+                fr[i, y0 - 1, x] = _KEEP
+            # a smaller kept rectangle past tile column 64 (at x >= 4200 where
+            # the frame is wide enough, else in its last columns), to be removed
+            rx = 4200 if w >= 4300 else 4097
+            fr[i, 10:30, rx:min(rx + 70, w)] = _KEEP
+        else:
+            # the only large component lies wholly in tile columns >= 65
+            # (x >= 4160, about 300 px wide) where the frame has them, else in
+            # the 65th (x >= 4096); small kept specks elsewhere
+            x0 = 4160 if w >= 4160 + 200 else 4096
+            x1 = min(x0 + 300, w - i)
+            fr[i, 5 + i:60, x0:x1] = _KEEP
+            fr[i, 40:50, x0 + 1:x0 + 3] = _DROP     # a hole, so interior mask words differ
+            for x in (3, 1000, 4000, 4090):
+                fr[i, 20:22, x:x + 2] = _KEEP
+    return fr
+
+
+def test_video_chain_wide_frames_vs_oracle(D):
+    """Frames wider than 4096 px (more than 64 tile columns): the fused
+    chain's crop-fit is then k_ccl_crop_stream (k_ccl_crop_rows holds a row's
+    mask words one per lane, 64 at the most, and is launched only up to 4096
+    px; this test is the stream kernel's only coverage).  Widths 4100 (65 tile
+    columns), 4416 (69) and 7680 (8K, 120), two frames of 70 rows (two tile
+    rows, more crop rows than one block's four waves), bit-exact against the
+    oracle: dense noise whose kept set percolates (the crop spans more than
+    0.9 of the width; reference-only shares 1.000, 1.000 and 1.000); a kept
+    band over the full width with single pixels at x = 4095, 4096 and w - 1
+    and a smaller rectangle past x = 4096 that must go; a lone large component
+    wholly past x = 4096 (first tile column >= 64, few of them).  The staged
+    form (ipp_hsv_mask, ipp_ccl_keep_largest, ipp_crop_to_bbox) gives the same
+    crops on the 4416-px noise frames."""
+    from image_processor_pipeline_amd import geometry as G
+    from image_processor_pipeline_amd.video_chain import VideoChain
+    rng = np.random.default_rng(4100)
+    n, h = 2, 70
+    for w in (4100, 4416, 7680):
+        chain = VideoChain(n, h, w, DEV)
+        for kind in ("noise", "band", "lone"):
+            fr = _wide_frames(kind, h, w, rng)
+            frd = _t(fr)
+            chain.out.fill_(7)
+            chain.run(frd)
+            res = chain.results()
+            for i in range(n):
+                exp = ops.keep_largest_component(ops.color_mask_bgra(fr[i], G.REFERENCE_HSV_RANGES))
+                print(kind, w, i, "crop", exp.shape, "share of width %.3f" % (exp.shape[1] / w))
+                if kind == "noise":
+                    assert exp.shape[1] > 0.9 * w
+                elif kind == "band":
+                    assert exp.shape[:2] == (4, w) and exp[1:, :, 3].all() and int((exp[0, :, 3] != 0).sum()) == 3
+                else:
+                    assert exp.shape[1] < 320 and exp.shape[0] >= 54
+                assert res[i] is not None and res[i].shape == exp.shape and np.array_equal(res[i], exp), (kind, w, i)
+                if kind == "noise":
+                    assert res[i].shape[1] > 0.9 * w
+            if kind == "noise" and w == 4416:
+                chain.out.fill_(9)
+                chain.run_staged(frd)
+                staged = chain.results()
+                assert all(np.array_equal(a, b) for a, b in zip(staged, res))
+
+
+def _tail_frames(n, h, w, rng):
+    """n random BGR frames whose last row and last column are all kept pixels
+    (random kept colours), so the bottom-right pixel belongs to a component
+    reaching every border."""
+    from image_processor_pipeline_amd import geometry as G
+    fr = rng.integers(0, 256, (n, h, w, 3), np.uint8)
+    path = np.zeros((h, w), bool)
+    path[-1, :] = True
+    path[:, -1] = True
+    for i in range(n):
+        for _ in range(64):
+            bad = path & (ops.color_mask_bgra(fr[i], G.REFERENCE_HSV_RANGES)[..., 3] == 0)
+            if not bad.any():
+                break
+            fr[i][bad] = rng.integers(0, 256, (int(bad.sum()), 3), np.uint8)
+        assert not bad.any()
+    return fr
+
+
+def test_video_chain_tail_chunk_vs_oracle(D):
+    """k_ccl_crop_rows' last 16-byte buffer load of a frame straddles the
+    buffer's num_records, which is rounded up to a dword only: the dwords
+    below it must come back whole (were the straddling load zeroed, the last
+    pixels' colour bytes would be 0).  Single-frame chains, so the frame is
+    the allocation's last, of 65×67 (fbytes = 13065, 9 mod 16), 33×35 (3465,
+    9 mod 16) and 7×5 (105, 9 mod 16), the frame 16-byte aligned (fmis = 0);
+    and a 3-frame chain of 65×67, whose frames 1 and 2 start at fmis = 9 and
+    2: (fmis + fbytes) % 16 = 9, 2 and 11.  Random BGR content with a kept
+    last row and column: the oracle's crop is the whole frame and its last
+    pixel has α 255.  Bit-exact."""
+    from image_processor_pipeline_amd import geometry as G
+    from image_processor_pipeline_amd.video_chain import VideoChain
+    rng = np.random.default_rng(13065)
+    for (n, h, w) in [(1, 65, 67), (1, 33, 35), (1, 7, 5), (3, 65, 67)]:
+        fr = _tail_frames(n, h, w, rng)
+        frd = _t(fr)
+        fbytes = h * w * 3
+        ends = [((frd.data_ptr() + i * fbytes) % 16 + fbytes) % 16 for i in range(n)]
+        print((n, h, w), "(fmis + fbytes) % 16 =", ends)
+        assert frd.data_ptr() % 16 == 0 and all(e != 0 for e in ends)
+        assert ends == ([9] if n == 1 else [9, 2, 11])
+        chain = VideoChain(n, h, w, DEV)
+        chain.out.fill_(7)
+        chain.run(frd)
+        res = chain.results()
+        for i in range(n):
+            exp = ops.keep_largest_component(ops.color_mask_bgra(fr[i], G.REFERENCE_HSV_RANGES))
+            assert exp.shape == (h, w, 4) and exp[-1, -1, 3] == 255          # the bbox reaches (w, h)
+            assert np.array_equal(exp[-1, -1, :3], fr[i, -1, -1]) and fr[i, -1, -1].any()
+            assert res[i] is not None and res[i].shape == exp.shape and np.array_equal(res[i], exp), (n, h, w, i)
 
 
 # --------------------------------------------------------------------------- config 5: 4K video chain
