@@ -141,6 +141,10 @@ SIGNATURES = {
     "ipp_alpha_bbox": (_I, [_P, _P, _I, _I, _I, _P, _P]),
     "ipp_alpha_bbox_min": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "ipp_pipe_overlay_bbox": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "ipp_pipe_hpass": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P]),
+    "ipp_pipe_vblend_over": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "ipp_pipe_scene_scratch_bytes": (_L, [_I, _I, _I, _I, _I]),
+    "ipp_pipe_scene_boxes": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "ipp_plan_lanczos": (_L, [_I, _D, _D, _I, _P, _L]),
     "ipp_plan_lanczos_ksize": (_I, [_D, _D, _I]),
     "ipp_plan_lanczos_batch": (_I, [_I, _P, _P, _P, _P, _L, _I]),

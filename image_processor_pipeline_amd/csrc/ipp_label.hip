@@ -11,7 +11,12 @@
 //   ipp_alpha_bbox_min: the same box on a materialised 2/4-channel image
 //   (the plugin path), ipp_alpha_bbox with a threshold.
 //
-// Both follow ipp_alpha_bbox's convention (ipp_gather.hip): the boxes are
+//   ipp_pipe_scene_boxes: scenes of K overlays per composite — per overlay
+//   the box of the pixels no later layer covers, its present and its visible
+//   pixel counts (the same channel-3 V pass, stored as alpha planes, then a
+//   pass that compares the planes by composite coordinate).
+//
+// All follow ipp_alpha_bbox's convention (ipp_gather.hip): the boxes are
 // pre-set to (INT_MAX, INT_MAX, -1, -1), every wave that saw a visible pixel
 // issues four device-scope atomics, and a finish kernel turns an untouched row
 // into (-1, -1, -1, -1).
@@ -72,13 +77,15 @@ __device__ __forceinline__ void bbox_commit(int32_t* __restrict__ row, int xmin,
 // planner emits; T is read once), the row bias in plane 0's initial value,
 // then the Horner step over the planes (planes3) — vblend_block's generic
 // form for channel 3 alone: 3 MFMAs per K step.
-__global__ void __launch_bounds__(256)
-k_pipe_overlay_bbox(const uint8_t* __restrict__ tmp, const int32_t* __restrict__ coefs,
-                    const ipp_pipe_desc* __restrict__ descs, FastDiv tiles_y, int alpha_min,
-                    int32_t* __restrict__ bbox) {
-    const uint32_t b = xcd_remap(blockIdx.x, gridDim.x);
-    const int im = (int)fdiv(b, tiles_y);
-    const int ty = (int)(b - (uint32_t)im * tiles_y.d);
+//
+// overlay_alpha_band is that block: it hands every pixel of the band (overlay
+// column x, overlay row o, alpha a) to `sink`, each pixel from exactly one
+// lane.  k_pipe_overlay_bbox folds them into a box; k_scene_alpha
+// (ipp_pipe_scene_boxes) stores them as a plane.
+template <typename Sink>
+__device__ __forceinline__ void overlay_alpha_band(const uint8_t* __restrict__ tmp, const int32_t* __restrict__ coefs,
+                                                   const ipp_pipe_desc* __restrict__ descs, int im, int ty,
+                                                   Sink sink) {
     const ipp_paste_desc p = descs[im].p;
     // the overlay's bands [vb0, vb1) (paste_bands)
     const int vb0 = (p.y >> 4) << 4;
@@ -112,7 +119,6 @@ k_pipe_overlay_bbox(const uint8_t* __restrict__ tmp, const int32_t* __restrict__
     // byte 12 of T group (row group gbase, column 0): the alpha dword
     const uint8_t* abase = tmp + v.src_off + gbase * gstride * 16 + 12;
 
-    int xmin = INT32_MAX, ymin = INT32_MAX, xmax = -1, ymax = -1;
     for (int ct = wave; ct < ctiles; ct += 4) {
         const int x = 16 * ct + x_l;
         const int xs = min(x, p.ov_w - 1);
@@ -139,14 +145,27 @@ k_pipe_overlay_bbox(const uint8_t* __restrict__ tmp, const int32_t* __restrict__
             const int32_t s = planes3(acc[0][r], acc[1][r], acc[2][r]);
             const int32_t a = min(max(s >> 22, 0), 255);  // Resample.c clip8
             const int o = y0 + 4 * (lane >> 4) + r - p.y;  // overlay row 16 t - phase + tile row
-            if (x < p.ov_w && o >= oy_lo && o < oy_hi && a >= alpha_min) {
-                xmin = min(xmin, x);
-                xmax = max(xmax, x);
-                ymin = min(ymin, o);
-                ymax = max(ymax, o);
-            }
+            if (x < p.ov_w && o >= oy_lo && o < oy_hi) sink(x, o, a);
         }
     }
+}
+
+__global__ void __launch_bounds__(256)
+k_pipe_overlay_bbox(const uint8_t* __restrict__ tmp, const int32_t* __restrict__ coefs,
+                    const ipp_pipe_desc* __restrict__ descs, FastDiv tiles_y, int alpha_min,
+                    int32_t* __restrict__ bbox) {
+    const uint32_t b = xcd_remap(blockIdx.x, gridDim.x);
+    const int im = (int)fdiv(b, tiles_y);
+    const int ty = (int)(b - (uint32_t)im * tiles_y.d);
+    int xmin = INT32_MAX, ymin = INT32_MAX, xmax = -1, ymax = -1;
+    overlay_alpha_band(tmp, coefs, descs, im, ty, [&](int x, int o, int a) {
+        if (a >= alpha_min) {
+            xmin = min(xmin, x);
+            xmax = max(xmax, x);
+            ymin = min(ymin, o);
+            ymax = max(ymax, o);
+        }
+    });
     bbox_commit(bbox + 4 * (int64_t)im, xmin, ymin, xmax, ymax);
 }
 
@@ -180,6 +199,126 @@ k_alpha_bbox_min(const uint8_t* __restrict__ img, const ipp_image_desc* __restri
         }
     }
     bbox_commit(bbox + 4 * (int64_t)im, xmin, ymin, xmax, ymax);
+}
+
+// ---------------------------------------------------------------------------
+// ipp_pipe_scene_boxes: occlusion-aware labels of scenes (K overlays pasted in
+// layer order onto one composite).
+//
+// Scratch: the table slot → descriptor (int32[n_scenes·K], slot = scene·K +
+// layer, -1 = no descriptor), then one alpha plane per descriptor, max_ov_h
+// rows of scene_pitch(max_ov_w) bytes.  Three launches in stream order:
+//   k_scene_init   rows (INT_MAX, INT_MAX, -1, -1, 0, 0) and the slot table;
+//   k_scene_alpha  overlay_alpha_band, every alpha byte stored to its plane;
+//   k_scene_visible  one block per (descriptor, 16-row strip of its overlay):
+//     a pixel is present when its alpha >= alpha_min and visible when no later
+//     layer of its scene whose rectangle holds the pixel has alpha >= cover_min
+//     there (read from that layer's plane by composite coordinate); wave-wide
+//     box and counts, six atomics from lane 0;
+// then k_scene_finish turns an untouched box into (-1, -1, -1, -1).
+// A descriptor larger than (max_ov_w, max_ov_h) has no plane: it is skipped
+// and never read as a later layer, so every plane access stays in bounds.
+// ---------------------------------------------------------------------------
+__host__ __device__ constexpr int64_t scene_pitch(int max_ov_w) { return ((int64_t)max_ov_w + 15) & ~(int64_t)15; }
+__host__ __device__ constexpr int64_t scene_table_bytes(int64_t slots) { return (4 * slots + 255) & ~(int64_t)255; }
+
+__global__ void k_scene_init(int32_t* __restrict__ out, int32_t* __restrict__ table,
+                             const int32_t* __restrict__ scene_layer, int n, int n_scenes, int K) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    out[6 * i + 0] = INT32_MAX;
+    out[6 * i + 1] = INT32_MAX;
+    out[6 * i + 2] = -1;
+    out[6 * i + 3] = -1;
+    out[6 * i + 4] = 0;
+    out[6 * i + 5] = 0;
+    const int s = scene_layer[2 * i], k = scene_layer[2 * i + 1];
+    if ((unsigned)s < (unsigned)n_scenes && (unsigned)k < (unsigned)K) table[(int64_t)s * K + k] = i;
+}
+
+__global__ void k_scene_finish(int32_t* out, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n && out[6 * i + 2] < 0) out[6 * i + 0] = out[6 * i + 1] = -1;
+}
+
+__global__ void __launch_bounds__(256)
+k_scene_alpha(const uint8_t* __restrict__ tmp, const int32_t* __restrict__ coefs,
+              const ipp_pipe_desc* __restrict__ descs, FastDiv tiles_y, int max_ov_w, int max_ov_h,
+              uint8_t* __restrict__ planes) {
+    const uint32_t b = xcd_remap(blockIdx.x, gridDim.x);
+    const int im = (int)fdiv(b, tiles_y);
+    const int ty = (int)(b - (uint32_t)im * tiles_y.d);
+    if (descs[im].p.ov_w > max_ov_w || descs[im].p.ov_h > max_ov_h) return;  // no plane (block-uniform)
+    const int64_t pitch = scene_pitch(max_ov_w);
+    uint8_t* plane = planes + (int64_t)im * max_ov_h * pitch;
+    overlay_alpha_band(tmp, coefs, descs, im, ty,
+                       [&](int x, int o, int a) { plane[(int64_t)o * pitch + x] = (uint8_t)a; });
+}
+
+constexpr int SVR = 16;  // overlay rows per k_scene_visible block
+
+__global__ void __launch_bounds__(256)
+k_scene_visible(const ipp_pipe_desc* __restrict__ descs, const int32_t* __restrict__ scene_layer,
+                const int32_t* __restrict__ table, const uint8_t* __restrict__ planes, FastDiv strips, int n,
+                int n_scenes, int K, int max_ov_w, int max_ov_h, int alpha_min, int cover_min,
+                int32_t* __restrict__ out) {
+    const uint32_t b = xcd_remap(blockIdx.x, gridDim.x);
+    const int im = (int)fdiv(b, strips);
+    const int v0 = (int)(b - (uint32_t)im * strips.d) * SVR;
+    const ipp_paste_desc p = descs[im].p;
+    if (v0 >= p.ov_h || p.ov_w > max_ov_w || p.ov_h > max_ov_h) return;  // block-uniform
+    const int64_t pitch = scene_pitch(max_ov_w), psize = (int64_t)max_ov_h * pitch;
+    const uint8_t* plane = planes + (int64_t)im * psize;
+    const int scene = scene_layer[2 * im], layer = scene_layer[2 * im + 1];
+    const bool mapped = (unsigned)scene < (unsigned)n_scenes && (unsigned)layer < (unsigned)K;
+    const int v = v0 + (int)(threadIdx.x >> 4);
+    int xmin = INT32_MAX, ymin = INT32_MAX, xmax = -1, ymax = -1, area = 0, vis = 0;
+    // 4 pixels of one row per thread and step (one aligned dword of the plane:
+    // its pitch is a multiple of 16, bytes past ov_w are masked below)
+    for (int u0 = 4 * (int)(threadIdx.x & 15); u0 < p.ov_w; u0 += 64) {
+        uint32_t a4 = 0u;
+        if (v < p.ov_h) a4 = *reinterpret_cast<const uint32_t*>(plane + (int64_t)v * pitch + u0);
+        uint32_t present = 0u;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            present |= (uint32_t)(v < p.ov_h && u0 + k < p.ov_w && (int)((a4 >> (8 * k)) & 255u) >= alpha_min) << k;
+        uint32_t hidden = 0u;
+        // later layers of the scene (the loop is block-uniform)
+        for (int j = mapped ? layer + 1 : K; j < K; ++j) {
+            const int dj = table[(int64_t)scene * K + j];
+            if ((unsigned)dj >= (unsigned)n) continue;
+            const ipp_paste_desc q = descs[dj].p;
+            if (q.ov_w > max_ov_w || q.ov_h > max_ov_h) continue;  // no plane
+            const int cy = p.y + v - q.y;                          // the row in layer j's overlay
+            if ((unsigned)cy >= (unsigned)q.ov_h) continue;
+            const uint8_t* qrow = planes + (int64_t)dj * psize + (int64_t)cy * pitch;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int cx = p.x + u0 + k - q.x;
+                if (((present >> k) & 1u) && (unsigned)cx < (unsigned)q.ov_w && (int)qrow[cx] >= cover_min)
+                    hidden |= 1u << k;
+            }
+        }
+        const uint32_t visible = present & ~hidden;
+        area += __builtin_popcount(present);
+        vis += __builtin_popcount(visible);
+        if (visible) {
+            xmin = min(xmin, p.x + u0 + (int)__builtin_ctz(visible));
+            xmax = max(xmax, p.x + u0 + 31 - (int)__builtin_clz(visible));
+            ymin = min(ymin, p.y + v);
+            ymax = max(ymax, p.y + v);
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        area += __shfl_xor(area, off);
+        vis += __shfl_xor(vis, off);
+    }
+    int32_t* row = out + 6 * (int64_t)im;
+    bbox_commit(row, xmin, ymin, xmax, ymax);
+    if ((threadIdx.x & 63) == 0) {
+        if (area) atomicAdd(&row[4], area);
+        if (vis) atomicAdd(&row[5], vis);
+    }
 }
 
 }  // namespace
@@ -218,6 +357,45 @@ extern "C" int ipp_alpha_bbox_min(const uint8_t* img, const ipp_image_desc* desc
     hipLaunchKernelGGL(k_alpha_bbox_min, dim3((uint32_t)blocks), dim3(256), 0, s, img, descs, tx, ty, alpha_min,
                        bbox);
     hipLaunchKernelGGL(k_label_bbox_finish, dim3(ib), dim3(256), 0, s, bbox, n_images);
+    IPP_CHECK_LAUNCH();
+    return IPP_OK;
+}
+
+extern "C" int64_t ipp_pipe_scene_scratch_bytes(int32_t n_images, int32_t n_scenes, int32_t per_scene,
+                                                int32_t max_ov_w, int32_t max_ov_h) {
+    if (n_images < 0 || n_scenes < 0 || per_scene < 1 || max_ov_w <= 0 || max_ov_h <= 0) return IPP_E_ARG;
+    return scene_table_bytes((int64_t)n_scenes * per_scene) + (int64_t)n_images * max_ov_h * scene_pitch(max_ov_w);
+}
+
+extern "C" int ipp_pipe_scene_boxes(const uint8_t* tmp, const int32_t* coefs, const ipp_pipe_desc* descs,
+                                    const int32_t* scene_layer, int32_t n_images, int32_t n_scenes,
+                                    int32_t per_scene, int32_t max_ov_w, int32_t max_ov_h, int32_t alpha_min,
+                                    int32_t cover_min, int32_t tap_format, uint8_t* scratch, int32_t* out,
+                                    void* stream) {
+    if (alpha_min < 1 || alpha_min > 255 || cover_min < 1 || cover_min > 255 || tap_format != IPP_TAPS_MFMA)
+        return IPP_E_ARG;
+    if (!tmp || !coefs || !descs || !scene_layer || !scratch || !out || n_images < 0 || n_scenes < 0 ||
+        per_scene < 1 || max_ov_w <= 0 || max_ov_h <= 0)
+        return IPP_E_ARG;
+    if ((reinterpret_cast<uintptr_t>(scratch) & 15u) != 0) return IPP_E_ARG;  // the planes are read by dwords
+    if (n_images == 0) return IPP_OK;
+    // an overlay of height H at any y spans at most ceil((15 + H) / 16) bands
+    const int tyb = (max_ov_h + 15 + LBR - 1) / LBR, strips = (max_ov_h + SVR - 1) / SVR;
+    const int64_t slots = (int64_t)n_scenes * per_scene;
+    if ((int64_t)tyb * n_images >= INT32_MAX || slots >= INT32_MAX) return IPP_E_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    int32_t* table = reinterpret_cast<int32_t*>(scratch);
+    uint8_t* planes = scratch + scene_table_bytes(slots);
+    if (slots > 0 && hipMemsetAsync(table, 0xFF, 4 * (size_t)slots, s) != hipSuccess) return IPP_E_LAUNCH;
+    const int ib = (n_images + 255) / 256;
+    hipLaunchKernelGGL(k_scene_init, dim3(ib), dim3(256), 0, s, out, table, scene_layer, n_images, n_scenes,
+                       per_scene);
+    hipLaunchKernelGGL(k_scene_alpha, dim3((uint32_t)(tyb * n_images)), dim3(256), 0, s, tmp, coefs, descs,
+                       fast_div((uint32_t)tyb), max_ov_w, max_ov_h, planes);
+    hipLaunchKernelGGL(k_scene_visible, dim3((uint32_t)(strips * n_images)), dim3(256), 0, s, descs, scene_layer,
+                       table, planes, fast_div((uint32_t)strips), n_images, n_scenes, per_scene, max_ov_w, max_ov_h,
+                       alpha_min, cover_min, out);
+    hipLaunchKernelGGL(k_scene_finish, dim3(ib), dim3(256), 0, s, out, n_images);
     IPP_CHECK_LAUNCH();
     return IPP_OK;
 }

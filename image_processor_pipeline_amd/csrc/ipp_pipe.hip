@@ -1017,12 +1017,54 @@ __device__ __forceinline__ void vb_mfma_tile(const i32x4 (&ta)[NK][3], const i32
 // unpremultiply_magic) instead of a reciprocal and two fix-ups per channel:
 // 1.340 -> 1.319 ms (round 5, profiles/r05/vpass/ab_unpremul_magic_r05al.txt);
 // overlays too wide for the table beside their rows take the reciprocal.
-template <bool MAGIC>
+//
+// INPLACE (ipp_pipe_vblend_over, a later layer of a scene): bg and dst are the
+// same pointer — the composite the earlier layers left — and are therefore
+// not __restrict__; the descriptor's bg_off / bg_pitch are replaced by its
+// dst_off / dst_pitch.  Why the block may blend in place:
+//   * phase 1 reads tmp and coefs and writes LDS only;
+//   * phase 2 walks a set of disjoint byte ranges of the band's rows — the
+//     48-byte groups (grouped path), the 16-byte chunks (general path) — and
+//     each range belongs to exactly one thread of the block, which loads it
+//     (gload / load16) before it stores it and never touches it again: the
+//     prefetch of the thread's next range (gnxt, the four chunks in flight)
+//     is another range, owned by the same thread.  No thread reads a byte
+//     another thread of the launch writes, so neither a barrier nor any order
+//     among blocks is needed;
+//   * the blocks of one descriptor own disjoint 16-row bands, and two
+//     descriptors of one launch never share a composite (the caller's
+//     contract, ipp.h);
+//   * a range's bytes outside the overlay's rectangle are stored as loaded:
+//     not blended (rows outside [oy_lo, oy_hi), groups or chunks beside the
+//     overlay) or blended with the zero alpha of orow's margin columns, and
+//     BLEND(b, ·, 0) = DIV255(255 b + 128) = b.
+// Under the column split it visits the overlay's groups [sx0, sx1) alone;
+// otherwise the band rows.
+template <bool INPLACE>
+struct VbPtr {
+    typedef const uint8_t* __restrict__ bg_t;
+    typedef uint8_t* __restrict__ dst_t;
+};
+template <>
+struct VbPtr<true> {
+    typedef const uint8_t* bg_t;
+    typedef uint8_t* dst_t;
+};
+__device__ __forceinline__ ipp_paste_desc vb_paste_desc(const ipp_paste_desc& q, bool inplace) {
+    ipp_paste_desc p = q;
+    if (inplace) {
+        p.bg_off = p.dst_off;
+        p.bg_pitch = p.dst_pitch;
+    }
+    return p;
+}
+
+template <bool MAGIC, bool INPLACE = false>
 __device__ __forceinline__ void vblend_block(uint32_t* __restrict__ orow, const uint8_t* __restrict__ tmp,
-                                             const uint8_t* __restrict__ bg, uint8_t* __restrict__ dst,
+                                             typename VbPtr<INPLACE>::bg_t bg, typename VbPtr<INPLACE>::dst_t dst,
                                              const int32_t* __restrict__ coefs,
                                              const ipp_pipe_desc* __restrict__ descs, int im, int ty, int ov_w_max) {
-    const ipp_paste_desc p = descs[im].p;
+    const ipp_paste_desc p = vb_paste_desc(descs[im].p, INPLACE);
     int y0 = ty * VBR;
     {
         int vb0, vb1;
@@ -1308,12 +1350,28 @@ k_pipe_vblend_mfma(const uint8_t* __restrict__ tmp, const uint8_t* __restrict__ 
     vblend_block<MAGIC>(orow, tmp, bg, dst, coefs, descs, im, ty, ov_w_max);
 }
 
+// The same block over one image pointer (a scene's layers >= 1): reads the
+// composite, blends the overlay, writes it back (vblend_block, INPLACE).
+template <bool MAGIC>
+__global__ void __launch_bounds__(256) IPP_VB_ATTR
+k_pipe_vblend_over(const uint8_t* __restrict__ tmp, uint8_t* img, const int32_t* __restrict__ coefs,
+                   const ipp_pipe_desc* __restrict__ descs, FastDiv tiles_y, int ov_w_max) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t orow[];  // as k_pipe_vblend_mfma
+    const uint32_t b = xcd_remap(blockIdx.x, gridDim.x);
+    const int im = (int)fdiv(b, tiles_y);
+    const int ty = (int)(b - (uint32_t)im * tiles_y.d);
+    vblend_block<MAGIC, true>(orow, tmp, img, img, coefs, descs, im, ty, ov_w_max);
+}
+
 template <int NR, bool ZONES, int CN>
 void launch_hpass(int n, int ty, hipStream_t s, const uint8_t* src, uint8_t* tmp, const int32_t* coefs,
                   const ipp_pipe_desc* descs, const ipp_hsv_params& hp, const uint8_t* bg, uint8_t* dst) {
-    // H pass + the background outside the overlays, per group of kCopyGroup items
+    // H pass + the background outside the overlays, per group of kCopyGroup
+    // items.  bg == nullptr (ipp_pipe_hpass): no copy slabs — every block
+    // index within a group is < kCopyGroup·ty, so the kernel's copy branch is
+    // never taken and bg / dst are never dereferenced.
     const int64_t groups = (n + kCopyGroup - 1) / kCopyGroup;
-    const uint32_t per_grp = (uint32_t)(kCopyGroup * ty + kCopySlabs);
+    const uint32_t per_grp = (uint32_t)(kCopyGroup * ty + (bg ? kCopySlabs : 0));
     hipLaunchKernelGGL((k_pipe_hpass2<NR, ZONES, CN>), dim3((uint32_t)(groups * per_grp)), dim3(64 * HP_NW), 0, s,
                        src, tmp, coefs, descs, n, fast_div((uint32_t)ty), fast_div(per_grp), hp, bg, dst);
 }
@@ -1331,14 +1389,13 @@ void launch_hpass_nr(bool zones, int cn, int n, int ty, hipStream_t s, const uin
     }
 }
 
-}  // namespace
-
-extern "C" int ipp_pipe_hpass_bgcopy(const uint8_t* src, uint8_t* tmp, const int32_t* coefs,
-                                     const ipp_pipe_desc* descs, int32_t n_images, int32_t max_out_w,
-                                     int32_t max_rows, int32_t src_cn, const ipp_hsv_params* hsv,
-                                     int32_t tap_format, const uint8_t* bg, uint8_t* dst, void* stream) {
+// The H launch of ipp_pipe_hpass_bgcopy (bg and dst given) and of
+// ipp_pipe_hpass (both null: no copy blocks).
+int hpass_entry(const uint8_t* src, uint8_t* tmp, const int32_t* coefs, const ipp_pipe_desc* descs, int32_t n_images,
+                int32_t max_out_w, int32_t max_rows, int32_t src_cn, const ipp_hsv_params* hsv, int32_t tap_format,
+                const uint8_t* bg, uint8_t* dst, void* stream) {
     if (n_images == 0) return IPP_OK;
-    if (!src || !tmp || !coefs || !descs || !hsv || !bg || !dst || n_images < 0 || max_out_w <= 0 || max_rows <= 0)
+    if (!src || !tmp || !coefs || !descs || !hsv || n_images < 0 || max_out_w <= 0 || max_rows <= 0)
         return IPP_E_ARG;
     if (src_cn != 3 && src_cn != 4) return IPP_E_ARG;
     if (tap_format != IPP_TAPS_MFMA) return IPP_E_ARG;
@@ -1377,6 +1434,24 @@ extern "C" int ipp_pipe_hpass_bgcopy(const uint8_t* src, uint8_t* tmp, const int
     return IPP_OK;
 }
 
+}  // namespace
+
+extern "C" int ipp_pipe_hpass_bgcopy(const uint8_t* src, uint8_t* tmp, const int32_t* coefs,
+                                     const ipp_pipe_desc* descs, int32_t n_images, int32_t max_out_w,
+                                     int32_t max_rows, int32_t src_cn, const ipp_hsv_params* hsv,
+                                     int32_t tap_format, const uint8_t* bg, uint8_t* dst, void* stream) {
+    if (n_images == 0) return IPP_OK;
+    if (!bg || !dst) return IPP_E_ARG;
+    return hpass_entry(src, tmp, coefs, descs, n_images, max_out_w, max_rows, src_cn, hsv, tap_format, bg, dst, stream);
+}
+
+extern "C" int ipp_pipe_hpass(const uint8_t* src, uint8_t* tmp, const int32_t* coefs, const ipp_pipe_desc* descs,
+                              int32_t n_images, int32_t max_out_w, int32_t max_rows, int32_t src_cn,
+                              const ipp_hsv_params* hsv, int32_t tap_format, void* stream) {
+    return hpass_entry(src, tmp, coefs, descs, n_images, max_out_w, max_rows, src_cn, hsv, tap_format, nullptr,
+                       nullptr, stream);
+}
+
 extern "C" int ipp_pipe_status(int32_t* status, void* stream) {
     if (!status) return IPP_E_ARG;
     hipStream_t s = (hipStream_t)stream;
@@ -1390,11 +1465,12 @@ extern "C" int ipp_pipe_status(int32_t* status, void* stream) {
     return IPP_OK;
 }
 
-extern "C" int ipp_pipe_vblend_bands(const uint8_t* tmp, const uint8_t* bg, uint8_t* dst, const int32_t* coefs,
-                                     const ipp_pipe_desc* descs, int32_t n_images, int32_t bg_w, int32_t bg_h,
-                                     int32_t max_ov_w, int32_t max_ov_h, int32_t tap_format, void* stream) {
+// bg == nullptr: the in-place form (ipp_pipe_vblend_over) on dst.
+static int vblend_entry(const uint8_t* tmp, const uint8_t* bg, uint8_t* dst, const int32_t* coefs,
+                        const ipp_pipe_desc* descs, int32_t n_images, int32_t bg_w, int32_t bg_h, int32_t max_ov_w,
+                        int32_t max_ov_h, int32_t tap_format, void* stream) {
     if (n_images == 0) return IPP_OK;
-    if (!tmp || !bg || !dst || !coefs || !descs || n_images < 0 || bg_w <= 0 || bg_h <= 0) return IPP_E_ARG;
+    if (!tmp || !dst || !coefs || !descs || n_images < 0 || bg_w <= 0 || bg_h <= 0) return IPP_E_ARG;
     if (tap_format != IPP_TAPS_MFMA || max_ov_w <= 0 || max_ov_w > bg_w || max_ov_h <= 0 || max_ov_h > bg_h ||
         max_ov_w > IPP_PIPE_MAX_OV_W)
         return IPP_E_ARG;
@@ -1407,6 +1483,16 @@ extern "C" int ipp_pipe_vblend_bands(const uint8_t* tmp, const uint8_t* bg, uint
     if (nb >= INT32_MAX) return IPP_E_ARG;
     hipStream_t st = (hipStream_t)stream;
     const FastDiv ftyb = fast_div((uint32_t)tyb);
+    if (!bg) {
+        if (use_magic)
+            hipLaunchKernelGGL(k_pipe_vblend_over<true>, dim3((uint32_t)nb), dim3(256), rows + magic, st, tmp, dst,
+                               coefs, descs, ftyb, max_ov_w);
+        else
+            hipLaunchKernelGGL(k_pipe_vblend_over<false>, dim3((uint32_t)nb), dim3(256), rows, st, tmp, dst, coefs,
+                               descs, ftyb, max_ov_w);
+        IPP_CHECK_LAUNCH();
+        return IPP_OK;
+    }
     if (use_magic)
         hipLaunchKernelGGL(k_pipe_vblend_mfma<true>, dim3((uint32_t)nb), dim3(256), rows + magic, st, tmp, bg, dst,
                            coefs, descs, ftyb, max_ov_w);
@@ -1415,4 +1501,18 @@ extern "C" int ipp_pipe_vblend_bands(const uint8_t* tmp, const uint8_t* bg, uint
                            descs, ftyb, max_ov_w);
     IPP_CHECK_LAUNCH();
     return IPP_OK;
+}
+
+extern "C" int ipp_pipe_vblend_bands(const uint8_t* tmp, const uint8_t* bg, uint8_t* dst, const int32_t* coefs,
+                                     const ipp_pipe_desc* descs, int32_t n_images, int32_t bg_w, int32_t bg_h,
+                                     int32_t max_ov_w, int32_t max_ov_h, int32_t tap_format, void* stream) {
+    if (n_images == 0) return IPP_OK;
+    if (!bg) return IPP_E_ARG;
+    return vblend_entry(tmp, bg, dst, coefs, descs, n_images, bg_w, bg_h, max_ov_w, max_ov_h, tap_format, stream);
+}
+
+extern "C" int ipp_pipe_vblend_over(const uint8_t* tmp, uint8_t* dst, const int32_t* coefs,
+                                    const ipp_pipe_desc* descs, int32_t n_images, int32_t bg_w, int32_t bg_h,
+                                    int32_t max_ov_w, int32_t max_ov_h, int32_t tap_format, void* stream) {
+    return vblend_entry(tmp, nullptr, dst, coefs, descs, n_images, bg_w, bg_h, max_ov_w, max_ov_h, tap_format, stream);
 }

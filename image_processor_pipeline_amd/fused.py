@@ -20,6 +20,12 @@ The reference's last step also writes one YOLO label per composite
 ``PipeRunner.run_labelled`` / ``overlay_bboxes`` give the tight box of what
 is visible of each overlay (``ipp_pipe_overlay_bbox``, a third launch between
 the two, opt-in).
+
+Scenes (an addition; the reference pastes one overlay per composite):
+``plan_scenes`` / ``SceneRunner`` paste K overlays per composite in layer
+order — layer 0 as above, every later layer by an H launch without the copy
+(``ipp_pipe_hpass``) and an in-place V launch (``ipp_pipe_vblend_over``) — and
+label each overlay by what no later layer covers (``ipp_pipe_scene_boxes``).
 """
 from __future__ import annotations
 
@@ -620,3 +626,262 @@ class PipeStream:
                 self.timing.append(tm)
         if self.main is not None:
             torch.cuda.current_stream(self.device).wait_stream(self.main)  # outputs visible to the caller's stream
+
+
+# ---------------------------------------------------------------------------
+# Scenes: K overlays per composite, occlusion-aware labels (an addition: the
+# reference pastes one overlay per composite).
+# ---------------------------------------------------------------------------
+def draw_scene_params(n_scenes_global: int, stop_scene: int, per_scene: int, src_hw: Tuple[int, int],
+                      bg_hw: Tuple[int, int], n_bg: int, cfg: PipeConfig, seed) -> List[ItemParams]:
+    """The seeded parameters of overlay items 0 .. stop_scene·per_scene - 1 of
+    a batch of scenes: exactly ``draw_params``'s stream over n_scenes_global ·
+    per_scene items (all angles, all symmetries, the background shuffle, then
+    per item ratio, x, y); overlay item i = scene·per_scene + layer, and the
+    background of item i is order[(i // per_scene) % n_bg], one per scene."""
+    K = per_scene
+    angles, syms, order, drawn = draw_params(n_scenes_global * K, stop_scene * K, src_hw, bg_hw, n_bg, cfg, seed)
+    return [ItemParams(angles[i], syms[i], order[(i // K) % n_bg], drawn[i][0], drawn[i][1], drawn[i][2])
+            for i in range(stop_scene * K)]
+
+
+@dataclass
+class ScenePlan:
+    """A batch of S scenes of K overlays each.  Overlay item i = s·K + k
+    (scene s, layer k; layer K-1 on top) is built from source image i.
+
+    ``descs`` is layer-major: descriptors [k·S, (k+1)·S) are layer k's, each
+    layer in the same scene order — scenes grouped by background (stable), so
+    layer 0's grouped copy keeps its shared loads.  ``desc_item[d]`` is the
+    overlay item of descriptor d (``pipe.order`` does not describe this
+    order).  Every descriptor's ``p.dst_off`` is its scene's composite slot;
+    layers >= 1 have ``p.bg_off = p.dst_off`` and ``p.bg_pitch = p.dst_pitch``
+    (they blend in place).  With K = 1 the descriptors are ``plan_pipe``'s."""
+    pipe: PipePlan               # the S·K overlay items (items, axes, hsv, totals)
+    descs: np.ndarray            # PIPE_DESC[S·K], layer-major
+    desc_item: np.ndarray        # int32[S·K]
+    n_scenes: int
+    per_scene: int
+    copy_read_bytes: int = 0     # background bytes layer 0's grouped copy loads
+
+    @property
+    def items(self) -> np.ndarray:
+        return self.pipe.items
+
+    @property
+    def axes(self) -> np.ndarray:
+        return self.pipe.axes
+
+    @property
+    def params(self) -> List[ItemParams]:
+        return self.pipe.params
+
+    @property
+    def bg_w(self) -> int:
+        return self.pipe.bg_w
+
+    @property
+    def bg_h(self) -> int:
+        return self.pipe.bg_h
+
+    @property
+    def scene_layer(self) -> np.ndarray:
+        """int32 (S·K, 2): (scene, layer) of each descriptor."""
+        return np.stack([self.desc_item // self.per_scene, self.desc_item % self.per_scene], axis=1).astype(np.int32)
+
+
+def plan_scenes(src_hw: Tuple[int, int], n_scenes: int, per_scene: int, bg_hw: Tuple[int, int], n_bg: int,
+                cfg: PipeConfig, seed: int = 0, src_pitch: Optional[int] = None,
+                item_range: Optional[Tuple[int, int]] = None, n_scenes_global: Optional[int] = None,
+                params: Optional[Sequence[ItemParams]] = None, n_threads: int = 0) -> ScenePlan:
+    """Plan `n_scenes` scenes of `per_scene` overlays.  ``item_range`` and
+    ``n_scenes_global`` count SCENES: a rank plans scenes [start, stop) of the
+    global batch and sees the parameters a single process would
+    (``draw_scene_params``).  ``params``: one ItemParams per overlay item
+    (n_scenes·per_scene, scene-major), nothing is drawn; the items of a scene
+    must name the same background.  With ``per_scene=1`` this is ``plan_pipe``
+    with the same arguments."""
+    K, S = per_scene, n_scenes
+    if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or K < 1:
+        raise ValueError(f"per_scene {per_scene!r}: an integer >= 1")
+    start, stop = item_range if item_range is not None else (0, S)
+    if stop - start != S or start < 0 or S <= 0:
+        raise ValueError(f"item_range {item_range} does not hold {S} scenes")
+    sg = stop if n_scenes_global is None else n_scenes_global
+    if sg < stop:
+        raise ValueError(f"n_scenes_global {sg} < item_range stop {stop}")
+    if params is not None:
+        if len(params) != S * K:
+            raise ValueError(f"{len(params)} ItemParams for {S} scenes of {K} overlays")
+        for s in range(S):
+            if len({int(q.bg_index) for q in params[s * K:(s + 1) * K]}) != 1:
+                raise ValueError(f"scene {start + s}: its overlays name different backgrounds")
+    if K == 1:
+        pipe = plan_pipe(src_hw, S, bg_hw, n_bg, cfg, seed, src_pitch, (start, stop), sg, params, n_threads)
+    else:
+        given = params
+        if given is None:
+            given = draw_scene_params(sg, stop, K, src_hw, bg_hw, n_bg, cfg, seed)[start * K:]
+        pipe = plan_pipe(src_hw, S * K, bg_hw, n_bg, cfg, seed, src_pitch, (start * K, stop * K), sg * K, given,
+                         n_threads)
+    # plan_pipe's descriptor d holds item pipe.order[d], with p.dst_off = the
+    # item's own slot: re-point it at the scene's slot and reorder layer-major
+    by_item = np.empty_like(pipe.descs)
+    by_item[pipe.order] = pipe.descs
+    slot = int(pipe.descs[0]["p"]["bg_h"]) * int(pipe.descs[0]["p"]["dst_pitch"])    # bytes of one composite
+    scene_order = np.argsort(pipe.items["bg_index"][::K], kind="stable")             # scenes grouped by background
+    desc_item = (scene_order[None, :] * K + np.arange(K)[:, None]).reshape(-1).astype(np.int32)
+    descs = by_item[desc_item]
+    descs["p"]["dst_off"] = (desc_item // K).astype(np.int64) * slot
+    descs["p"]["bg_off"][S:] = descs["p"]["dst_off"][S:]
+    descs["p"]["bg_pitch"][S:] = descs["p"]["dst_pitch"][S:]
+    # one background load per run of same-background layer-0 descriptors in a copy group (IPP_PT_COPY_READS)
+    bgi = pipe.items["bg_index"][desc_item[:S]]
+    runs = sum(1 for d in range(S) if d % N.IPP_PIPE_COPY_GROUP == 0 or bgi[d] != bgi[d - 1])
+    return ScenePlan(pipe, descs, desc_item, S, K, runs * 3 * pipe.bg_w * pipe.bg_h)
+
+
+def _check_level(name: str, v) -> int:
+    """alpha_min / cover_min: an integer in 1..255 (check_alpha_min's rule)."""
+    try:
+        return _check_alpha_min(v)
+    except ValueError:
+        raise ValueError(f"{name} {v!r}: an integer in 1..255") from None
+
+
+def scene_labels(boxes: np.ndarray, bg_w: int, bg_h: int, class_ids=0, min_visible: float = 0.0) -> List[List[str]]:
+    """YOLO lines of every scene from the (S, K, 6) rows (x0, y0, x1, y1, area,
+    visible) of ``SceneRunner.scene_boxes``: labels[s] lists, in layer order,
+    one line (``yolo_label``) per overlay with visible > 0 and visible / area
+    >= min_visible; an empty list = an empty label file.  ``class_ids``: an
+    int, or one int per overlay item (S·K, scene-major)."""
+    boxes = np.asarray(boxes)
+    if boxes.ndim != 3 or boxes.shape[2] != 6:
+        raise ValueError(f"boxes of shape {boxes.shape}: (scenes, layers, 6) expected")
+    S, K = boxes.shape[:2]
+    if isinstance(class_ids, (int, np.integer)):
+        ids = [int(class_ids)] * (S * K)
+    else:
+        ids = [int(c) for c in class_ids]
+        if len(ids) != S * K:
+            raise ValueError(f"{len(ids)} class ids for {S * K} overlays")
+    out: List[List[str]] = []
+    for s in range(S):
+        lines = []
+        for k in range(K):
+            x0, y0, x1, y1, area, vis = (int(v) for v in boxes[s, k])
+            if vis > 0 and vis >= min_visible * area:
+                lines.append(yolo_label(ids[s * K + k], (x0, y0, x1, y1), bg_w, bg_h))
+        out.append(lines)
+    return out
+
+
+class SceneRunner:
+    """Device-resident scene plan + scratch for repeated runs of one batch:
+    2 + K launches on the current stream (2 when K = 1, the pipe's own)."""
+
+    def __init__(self, plan: ScenePlan, device):
+        self.plan = plan
+        self.device = torch.device(device)
+        self.descs = _to_dev(plan.descs, self.device)
+        self.coefs, self.host_tiles = plan_taps(plan.pipe, self.device)
+        self.tmp = torch.empty(plan.pipe.tmp_bytes, dtype=torch.uint8, device=self.device)
+        self.lib = N.load()
+        self._hpass_done = False   # the H launches have filled tmp (scene_boxes needs it)
+        self._scene_layer = None
+        self._scratch = None
+
+    def _check(self, caller: str, src: torch.Tensor, bgs: torch.Tensor, out: torch.Tensor) -> None:
+        for t, name in ((src, "src"), (bgs, "bgs"), (out, "out")):
+            if not (t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()):
+                raise N.NativeUnavailable(f"SceneRunner.{caller}: {name} must be a contiguous uint8 ROCm tensor")
+        p, S, K = self.plan.pipe, self.plan.n_scenes, self.plan.per_scene
+        if src.dim() < 1 or src.shape[0] != S * K:
+            raise ValueError(f"SceneRunner.{caller}: src holds {src.shape[0] if src.dim() else 0} images, "
+                             f"{S} scenes of {K} overlays take {S * K}")
+        if tuple(out.shape) != (S, p.bg_h, p.bg_w, 3):
+            raise ValueError(f"SceneRunner.{caller}: out of shape {tuple(out.shape)}, {S} composites "
+                             f"({S}, {p.bg_h}, {p.bg_w}, 3) expected")
+        if bgs.dim() != 4 or tuple(bgs.shape[1:]) != (p.bg_h, p.bg_w, 3) or \
+                bgs.shape[0] <= int(p.items["bg_index"].max()):
+            raise ValueError(f"SceneRunner.{caller}: bgs of shape {tuple(bgs.shape)} does not hold the plan's "
+                             f"backgrounds (n, {p.bg_h}, {p.bg_w}, 3)")
+
+    def _dptr(self, d0: int) -> int:
+        return self.descs.data_ptr() + d0 * self.plan.descs.itemsize
+
+    def run(self, src: torch.Tensor, bgs: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+        self._check("run", src, bgs, out)
+        p, S, K = self.plan.pipe, self.plan.n_scenes, self.plan.per_scene
+        st, lib = _stream(self.device), self.lib
+        hsv = N.np_ptr(p.hsv)
+        N.check(lib.ipp_pipe_hpass_bgcopy(src.data_ptr(), self.tmp.data_ptr(), self.coefs.data_ptr(), self._dptr(0),
+                                          S, p.max_out_w, p.max_rows, 3, hsv, p.tap_format, bgs.data_ptr(),
+                                          out.data_ptr(), st), "ipp_pipe_hpass_bgcopy")
+        if K > 1:
+            N.check(lib.ipp_pipe_hpass(src.data_ptr(), self.tmp.data_ptr(), self.coefs.data_ptr(), self._dptr(S),
+                                       S * (K - 1), p.max_out_w, p.max_rows, 3, hsv, p.tap_format, st),
+                    "ipp_pipe_hpass")
+        self._hpass_done = True
+        N.check(lib.ipp_pipe_vblend_bands(self.tmp.data_ptr(), bgs.data_ptr(), out.data_ptr(), self.coefs.data_ptr(),
+                                          self._dptr(0), S, p.bg_w, p.bg_h, p.max_ov_w, p.max_ov_h, p.tap_format,
+                                          st), "ipp_pipe_vblend_bands")
+        # one launch per later layer: two overlays of a scene never share a launch (ipp.h)
+        for k in range(1, K):
+            N.check(lib.ipp_pipe_vblend_over(self.tmp.data_ptr(), out.data_ptr(), self.coefs.data_ptr(),
+                                             self._dptr(k * S), S, p.bg_w, p.bg_h, p.max_ov_w, p.max_ov_h,
+                                             p.tap_format, st), "ipp_pipe_vblend_over")
+        return out
+
+    def status(self) -> int:
+        """Sticky status of the pipe kernels since the last call (``PipeRunner.status``).  Synchronises."""
+        st = np.zeros(1, np.int32)
+        N.check(self.lib.ipp_pipe_status(N.np_ptr(st), _stream(self.device)), "ipp_pipe_status")
+        return int(st[0])
+
+    def _launch_boxes(self, alpha_min: int, cover_min: int) -> torch.Tensor:
+        if not self._hpass_done:
+            raise N.NativeError("SceneRunner.scene_boxes: no H launch (run) has run on this runner")
+        p, S, K = self.plan.pipe, self.plan.n_scenes, self.plan.per_scene
+        n = S * K
+        if self._scratch is None:
+            nb = self.lib.ipp_pipe_scene_scratch_bytes(n, S, K, p.max_ov_w, p.max_ov_h)
+            if nb < 0:
+                raise N.NativeError(f"ipp_pipe_scene_scratch_bytes failed with code {nb}")
+            self._scratch = torch.empty(int(nb), dtype=torch.uint8, device=self.device)
+            self._scene_layer = _to_dev(self.plan.scene_layer, self.device)
+        rows = torch.empty(6 * n, dtype=torch.int32, device=self.device)
+        N.check(self.lib.ipp_pipe_scene_boxes(self.tmp.data_ptr(), self.coefs.data_ptr(), self._dptr(0),
+                                              self._scene_layer.data_ptr(), n, S, K, p.max_ov_w, p.max_ov_h,
+                                              alpha_min, cover_min, p.tap_format, self._scratch.data_ptr(),
+                                              rows.data_ptr(), _stream(self.device)), "ipp_pipe_scene_boxes")
+        return rows
+
+    def _rows_by_scene(self, rows: torch.Tensor) -> np.ndarray:
+        """Copy the rows back (synchronises): (S, K, 6) in scene, layer order."""
+        by_desc = rows.cpu().numpy().reshape(-1, 6)
+        out = np.empty_like(by_desc)
+        out[self.plan.desc_item] = by_desc
+        return out.reshape(self.plan.n_scenes, self.plan.per_scene, 6)
+
+    def scene_boxes(self, alpha_min: int = 1, cover_min: int = 128) -> np.ndarray:
+        """(S, K, 6) int32 rows (x0, y0, x1, y1, area, visible) in scene, layer
+        order (ipp_pipe_scene_boxes): the half-open tight box, in composite
+        coordinates, of the overlay's visible pixels — alpha >= alpha_min and
+        not covered by a later layer's alpha >= cover_min — or (-1,-1,-1,-1);
+        area = pixels with alpha >= alpha_min, visible = the visible ones.  It
+        reads the H launches' scratch, so it runs after ``run`` on the current
+        stream, and synchronises for the copy back."""
+        alpha_min, cover_min = _check_level("alpha_min", alpha_min), _check_level("cover_min", cover_min)
+        return self._rows_by_scene(self._launch_boxes(alpha_min, cover_min))
+
+    def run_labelled(self, src: torch.Tensor, bgs: torch.Tensor, out: torch.Tensor, class_ids=0,
+                     alpha_min: int = 1, cover_min: int = 128,
+                     min_visible: float = 0.0) -> Tuple[torch.Tensor, List[List[str]]]:
+        """``run`` plus the YOLO lines of every scene (``scene_labels``):
+        labels[s] lists scene s's lines in layer order, one per overlay with
+        visible > 0 and visible / area >= min_visible."""
+        alpha_min, cover_min = _check_level("alpha_min", alpha_min), _check_level("cover_min", cover_min)
+        self.run(src, bgs, out)
+        boxes = self._rows_by_scene(self._launch_boxes(alpha_min, cover_min))
+        return out, scene_labels(boxes, self.plan.bg_w, self.plan.bg_h, class_ids, min_visible)

@@ -281,6 +281,65 @@ int ipp_pipe_overlay_bbox(const uint8_t* tmp, const int32_t* coefs, const ipp_pi
                           int32_t alpha_min, int32_t tap_format, int32_t* bbox, void* stream);
 
 /* ------------------------------------------------------------------------ */
+/* Scenes: K overlays (layers 0 .. K-1, layer K-1 on top) pasted in layer     */
+/* order onto one composite, each by paste(ov, (x, y), ov) onto the result of */
+/* the layer before (fused.plan_scenes / SceneRunner).  An addition: the      */
+/* reference pastes one overlay per composite.  Launch sequence for the       */
+/* layer-major descriptors of a batch, all on one stream:                     */
+/*   ipp_pipe_hpass_bgcopy  layer-0 descriptors (p.bg_off = the background,   */
+/*                          p.dst_off = the scene's composite);               */
+/*   ipp_pipe_hpass         every later layer's descriptors (one launch);     */
+/*   ipp_pipe_vblend_bands  layer 0;                                          */
+/*   ipp_pipe_vblend_over   once per layer 1 .. K-1, in layer order.          */
+/* ------------------------------------------------------------------------ */
+/* The H pass of ipp_pipe_hpass_bgcopy with no background copy: the same kernel
+ * launched without copy blocks; it writes `tmp` only.  Same arguments (minus
+ * bg and dst), checks and ring limit. */
+int ipp_pipe_hpass(const uint8_t* src, uint8_t* tmp, const int32_t* coefs,
+                   const ipp_pipe_desc* descs, int32_t n_images, int32_t max_out_w,
+                   int32_t max_rows, int32_t src_cn, const ipp_hsv_params* hsv,
+                   int32_t tap_format, void* stream);
+/* The V pass, unpremultiply and alpha blend of ipp_pipe_vblend_bands IN PLACE
+ * on `dst`: it reads the composite at p.dst_off / p.dst_pitch (p.bg_off and
+ * p.bg_pitch are ignored), blends the overlay and writes the result back.  It
+ * touches only the overlay's 16-pixel groups of its 16-row bands under the
+ * column split (see above), the band rows otherwise; what it stores outside
+ * the overlay's rectangle are the bytes it loaded there.  Every byte range is
+ * loaded and stored by one thread, load first, so the result does not depend
+ * on how the blocks are scheduled — PROVIDED no two descriptors of one launch
+ * share a composite: two overlays of one scene must never be in the same
+ * launch.  Launch it once per layer; stream order is the layer order.  Same
+ * checks and IPP_PIPE_MAX_OV_W limit as ipp_pipe_vblend_bands; tmp, coefs and
+ * descs must not overlap dst. */
+int ipp_pipe_vblend_over(const uint8_t* tmp, uint8_t* dst, const int32_t* coefs,
+                         const ipp_pipe_desc* descs, int32_t n_images, int32_t bg_w, int32_t bg_h,
+                         int32_t max_ov_w, int32_t max_ov_h, int32_t tap_format, void* stream);
+/* Occlusion-aware labels of scenes.  After the H launches of the batch on the
+ * same stream, before tmp is reused (reads tmp and coefs, like
+ * ipp_pipe_overlay_bbox).  scene_layer: device int32[n_images][2] = (scene,
+ * layer) of each descriptor, 0 <= scene < n_scenes, 0 <= layer < per_scene (a
+ * descriptor outside those ranges is labelled as if alone in its scene).
+ * With A_k the alpha of layer k's resized overlay (its paste mask) at (x_k,
+ * y_k): an overlay pixel is PRESENT iff its alpha >= alpha_min, and VISIBLE iff
+ * it is present and every later layer j > k of the same scene whose rectangle
+ * holds that composite pixel has A_j < cover_min there.
+ * out[6*i..] = (x0, y0, x1, y1, area, visible) of descriptor i: the half-open
+ * tight box of its visible pixels in COMPOSITE coordinates, (-1,-1,-1,-1) when
+ * it has none; area = its present pixels, visible = its visible pixels.
+ * 1 <= alpha_min, cover_min <= 255.  scratch: device, 16-B aligned,
+ * ipp_pipe_scene_scratch_bytes(...) bytes = a slot table of n_scenes·per_scene
+ * int32 (rounded up to 256 B) + n_images alpha planes of max_ov_h rows of
+ * ⌈max_ov_w / 16⌉·16 bytes.  Descriptors larger than (max_ov_w, max_ov_h) are
+ * left at (-1,-1,-1,-1, 0, 0) and hide nothing. */
+int64_t ipp_pipe_scene_scratch_bytes(int32_t n_images, int32_t n_scenes, int32_t per_scene,
+                                     int32_t max_ov_w, int32_t max_ov_h);
+int ipp_pipe_scene_boxes(const uint8_t* tmp, const int32_t* coefs, const ipp_pipe_desc* descs,
+                         const int32_t* scene_layer, int32_t n_images, int32_t n_scenes,
+                         int32_t per_scene, int32_t max_ov_w, int32_t max_ov_h, int32_t alpha_min,
+                         int32_t cover_min, int32_t tap_format, uint8_t* scratch, int32_t* out,
+                         void* stream);
+
+/* ------------------------------------------------------------------------ */
 /* K10-K13: pixels_isolés.keep_largest_component                             */
 /* :32 threshold(α,1,255) :35 connectedComponentsWithStats(8) :38-55 keep    */
 /* largest :74-81 crop-fit (findNonZero + boundingRect).                     */

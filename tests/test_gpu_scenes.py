@@ -1,0 +1,295 @@
+"""GPU: scenes of K overlays per composite (fused.plan_scenes / SceneRunner:
+ipp_pipe_hpass, ipp_pipe_vblend_over, ipp_pipe_scene_boxes).  Composites are
+compared byte for byte with the iterated oracle paste, label rows with the
+definition of visibility restated in numpy (tests/scene_refs.py)."""
+import numpy as np
+import pytest
+
+torch = pytest.importorskip("torch")
+
+from tests import label_refs as R
+from tests import scene_refs as SR
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+LEVELS = [(1, 128), (128, 255), (255, 1)]     # (alpha_min, cover_min)
+
+
+@pytest.fixture(scope="module")
+def fused():
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from image_processor_pipeline_amd import fused as F
+    return F
+
+
+def _t(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+
+
+class Scenes:
+    """One planned scene batch after its run, with the oracle's overlays and composites."""
+
+    def __init__(self, fused, src, bgs, plan, cfg):
+        self.fused, self.src, self.bgs, self.plan, self.cfg = fused, src, bgs, plan, cfg
+        self.runner = fused.SceneRunner(plan, DEV)
+        self.dsrc, self.dbgs = _t(src), _t(bgs)
+        self.out = torch.full((plan.n_scenes,) + bgs.shape[1:], 77, dtype=torch.uint8, device=DEV)
+        self.runner.run(self.dsrc, self.dbgs, self.out)
+        self.overlays = SR.scene_overlays(src, plan, cfg)
+        self.composites = SR.scene_composites(bgs, plan, self.overlays)
+
+    def check_composites(self):
+        got = self.out.cpu().numpy()
+        for s in range(self.plan.n_scenes):
+            assert np.array_equal(got[s], self.composites[s]), (s, int((got[s] != self.composites[s]).sum()))
+
+    def rows(self, alpha_min, cover_min, **kw):
+        return SR.scene_rows(self.plan, self.overlays, alpha_min, cover_min, **kw)
+
+    def check_rows(self, alpha_min, cover_min):
+        got = self.runner.scene_boxes(alpha_min, cover_min)
+        exp = self.rows(alpha_min, cover_min)
+        assert got.dtype == np.int32 and got.shape == exp.shape
+        assert np.array_equal(got, exp), (alpha_min, cover_min, got.tolist(), exp.tolist())
+        return exp
+
+
+# --- 7: K = 1 is the existing pipe ---------------------------------------------------
+def test_one_overlay_per_scene_is_the_pipe(fused):
+    """The `small` batch of tests/test_gpu_labels.py."""
+    cfg = fused.PipeConfig(margins=(0.05, 9, 0.1, 3))
+    src, bgs, pplan = R.noise_batch(fused, 10, 150, 170, 3, 128, 160, cfg, 7)
+    plan = fused.plan_scenes((150, 170), 10, 1, (128, 160), 3, cfg, seed=7)
+    assert plan.descs.tobytes() == pplan.descs.tobytes()
+    dsrc, dbgs = _t(src), _t(bgs)
+    ref = torch.full((10, 128, 160, 3), 7, dtype=torch.uint8, device=DEV)
+    prun = fused.PipeRunner(pplan, DEV)
+    prun.run(dsrc, dbgs, ref)
+    out = torch.full_like(ref, 9)
+    srun = fused.SceneRunner(plan, DEV)
+    assert srun.run(dsrc, dbgs, out) is out
+    assert torch.equal(out, ref)
+    rows = srun.scene_boxes(1, 128)
+    assert rows.shape == (10, 1, 6)
+    tight = prun.overlay_bboxes(1)
+    xy = np.stack([pplan.items["x"], pplan.items["y"]] * 2, axis=1)
+    assert (tight[:, 0] >= 0).all()
+    assert np.array_equal(rows[:, 0, :4], tight + xy)
+    assert np.array_equal(rows[:, 0, 4], rows[:, 0, 5]) and (rows[:, 0, 4] > 0).all()
+
+
+# --- 8: noise scenes, grouped path -----------------------------------------------------
+NOISE_SEED = 23        # chosen on the CPU: the reference alone meets the conditions asserted below
+
+
+@pytest.fixture(scope="module")
+def noise(fused):
+    # (0.2-0.7: wide enough for the overlays to overlap AND for V tiles of 3 K
+    # steps, which need a downscale of the 150×170 sources below ~0.35)
+    cfg = fused.PipeConfig(margins=(0.05, 9, 0.1, 3), scale_min=0.2, scale_max=0.7)
+    src, bgs, plan = SR.scene_noise_batch(fused, 4, 3, 150, 170, 3, 128, 160, cfg, NOISE_SEED)
+    return Scenes(fused, src, bgs, plan, cfg)
+
+
+def test_noise_scenes_composite(noise):
+    plan = noise.plan
+    assert len(set((plan.items["y"] & 15).tolist())) >= 4            # tile phases
+    coefs = noise.runner.coefs.cpu().numpy()                         # as Batch.v_ksteps reads them
+    ks = set()
+    for d in plan.descs:
+        off, nt = int(d["v"]["coef_off"]), (int(d["v"]["out_len"]) + (int(d["p"]["y"]) & 15) + 15) >> 4
+        ks |= set(coefs[off:off + 4 * nt].reshape(nt, 4)[:, 1].tolist())
+    print("V tile K steps:", sorted(ks))
+    assert {2, 3} <= ks
+    noise.check_composites()
+    assert noise.runner.status() == 0
+
+
+@pytest.mark.parametrize("alpha_min,cover_min", LEVELS)
+def test_noise_scenes_labels(noise, alpha_min, cover_min):
+    exp = noise.rows(alpha_min, cover_min)
+    free = noise.rows(alpha_min, cover_min, occlusion=False)
+    hidden_scenes = int((exp[..., 5] < exp[..., 4]).any(axis=1).sum())
+    shrunk = int(((exp[..., :4] != free[..., :4]).any(axis=2) & (exp[..., 0] >= 0)).sum())
+    print("scenes with hidden pixels:", hidden_scenes, "boxes shrunk by occlusion:", shrunk)
+    assert hidden_scenes >= 2 and shrunk >= 1
+    noise.check_rows(alpha_min, cover_min)
+
+
+def test_run_labelled_matches_the_reference_rows(noise):
+    out = torch.full_like(noise.out, 5)
+    ids = list(range(12))
+    got_out, labels = noise.runner.run_labelled(noise.dsrc, noise.dbgs, out, class_ids=ids, min_visible=0.5)
+    assert got_out is out and torch.equal(out, noise.out)
+    exp = noise.fused.scene_labels(noise.rows(1, 128), 160, 128, ids, 0.5)
+    assert labels == exp and len(labels) == 4
+
+
+# --- 9: odd width, the ungrouped path --------------------------------------------------
+def test_odd_background_width(fused):
+    """Backgrounds, margins, scales and sources of test_gpu_labels.test_odd_background_width."""
+    cfg = fused.PipeConfig(margins=(3, 5, 2, 7), scale_min=0.2, scale_max=0.6)
+    src, bgs, plan = SR.scene_noise_batch(fused, 3, 2, 90, 110, 3, 97, 125, cfg, 125)
+    b = Scenes(fused, src, bgs, plan, cfg)
+    b.check_composites()
+    for a, c in LEVELS[:2]:
+        b.check_rows(a, c)
+
+
+# --- given parameters -------------------------------------------------------------------
+def _given(fused, src_hw, bg_hw, n_bg, cfg, K, specs, place):
+    """Plan scenes from specs = [(angle, sym, bg_index, ratio)] per overlay item;
+    `place(ov)` returns the (x, y) of every item from the overlays' (w, h)."""
+    S = len(specs) // K
+    sizes = fused.plan_scenes(src_hw, S, K, bg_hw, n_bg, cfg,
+                              params=[fused.ItemParams(a, s, b, r, 0, 0) for a, s, b, r in specs])
+    ov = list(zip(sizes.items["ov_w"].tolist(), sizes.items["ov_h"].tolist()))
+    xy = place(ov)
+    return fused.plan_scenes(src_hw, S, K, bg_hw, n_bg, cfg,
+                             params=[fused.ItemParams(a, s, b, r, x, y) for (a, s, b, r), (x, y) in zip(specs, xy)])
+
+
+# --- 10: neighbours in one 16-pixel group and one 16-row band ----------------------------
+def test_neighbours_share_a_group_and_a_band(fused):
+    cfg = fused.PipeConfig(margins=(0.05, 9, 0.1, 3))
+    rng = np.random.default_rng(41)
+    src = rng.integers(0, 256, (4, 150, 170, 3), np.uint8)
+    bgs = rng.integers(0, 256, (2, 128, 160, 3), np.uint8)
+    specs = [(33.0, "o", 0, 0.22), (127.0, "h", 0, 0.25), (250.0, "v", 1, 0.2), (75.0, "hv", 1, 0.23)]
+
+    def place(ov):
+        (w0, h0), (w1, h1), (w2, h2), (w3, h3) = ov
+        x0 = 21 if (21 + w0) % 16 else 22        # layer 1 starts inside layer 0's last 16-pixel group
+        y2 = 9 if (9 + h2) % 16 else 10          # layer 1 starts inside layer 0's last 16-row band
+        return [(x0, 37), (x0 + w0, 42), (50, y2), (53, y2 + h2)]
+
+    plan = _given(fused, (150, 170), (128, 160), 2, cfg, 2, specs, place)
+    it = plan.items
+    x, y, w, h = (it[k].astype(int) for k in ("x", "y", "ov_w", "ov_h"))
+    # scene 0: side by side, disjoint, one shared 16-pixel group, intersecting band ranges
+    assert x[1] == x[0] + w[0] and x[1] // 16 == (x[0] + w[0] - 1) // 16
+    assert max(y[0] // 16, y[1] // 16) <= min((y[0] + h[0] - 1) // 16, (y[1] + h[1] - 1) // 16)
+    # scene 1: one above the other, disjoint, one shared 16-row band, intersecting group ranges
+    assert y[3] == y[2] + h[2] and y[3] // 16 == (y[2] + h[2] - 1) // 16
+    assert max(x[2] // 16, x[3] // 16) <= min((x[2] + w[2] - 1) // 16, (x[3] + w[3] - 1) // 16)
+    b = Scenes(fused, src, bgs, plan, cfg)
+    b.check_composites()
+    rows = b.check_rows(1, 128)
+    assert np.array_equal(rows[..., 4], rows[..., 5])          # disjoint rectangles hide nothing
+
+
+# --- 11: full and partial cover ----------------------------------------------------------
+def test_full_partial_and_faint_cover(fused):
+    """Structured sources as tests/label_refs.structured_batch plants them:
+    the (90, 120, 60) fill is transparent (V <= 150), planted bright bytes are
+    opaque.  Unrotated, every overlay of a scene at the same place and size."""
+    cfg = fused.PipeConfig(margins=R.STRUCT_MARGINS, hsv_ranges=list(R.STRUCT_RANGES))
+    H, W, K = 140, 120, 2
+    rng = np.random.default_rng(5)
+    src = np.empty((6, H, W, 3), np.uint8)
+    src[:] = (90, 120, 60)
+
+    def plant(i, r0, r1, c0, c1):
+        src[i, r0:r1, c0:c1] = rng.integers(160, 256, (r1 - r0, c1 - c0, 3))
+
+    plant(0, 50, 80, 40, 70), plant(1, 10, 130, 10, 110)       # scene 0: layer 1 covers all of layer 0
+    plant(2, 50, 80, 40, 70), plant(3, 10, 130, 10, 55)        # scene 1: layer 1 covers layer 0's left part
+    plant(4, 50, 80, 40, 70), plant(5, 10, 130, 55, 56)        # scene 2: a 1-pixel line, faint once downscaled
+    bgs = rng.integers(0, 256, (2, 96, 128, 3), np.uint8)
+    specs = [(0.0, "o", s % 2, 0.5) for s in range(3) for _ in range(K)]
+    plan = _given(fused, (H, W), (96, 128), 2, cfg, K, specs, lambda ov: [(30, 20)] * 6)
+    b = Scenes(fused, src, bgs, plan, cfg)
+    b.check_composites()
+    exp = b.check_rows(1, 128)
+    free = b.rows(1, 128, occlusion=False)
+    # scene 0: layer 0 is present but wholly hidden
+    assert exp[0, 0].tolist()[:4] == [-1, -1, -1, -1] and exp[0, 0, 4] > 0 and exp[0, 0, 5] == 0
+    # scene 1: layer 0's left edge moves right by the reference's amount, the other edges stay
+    assert exp[1, 0, 0] > free[1, 0, 0] and exp[1, 0, 1:4].tolist() == free[1, 0, 1:4].tolist()
+    assert 0 < exp[1, 0, 5] < exp[1, 0, 4]
+    # scene 2: the line's alpha stays below cover_min = 128 and hides nothing; at 32 it does
+    faint = b.overlays[5][..., 3]
+    assert 32 <= faint.max() < 128
+    assert exp[2, 0].tolist() == free[2, 0].tolist() and exp[2, 0, 4] == exp[2, 0, 5] > 0
+    low = b.check_rows(1, 32)
+    assert low[2, 0, 5] < low[2, 0, 4]
+    labels = fused.scene_labels(exp, 128, 96)
+    assert len(labels[0]) == 1 and labels[0][0] == fused.yolo_label(0, tuple(exp[0, 1, :4].tolist()), 128, 96)
+    assert len(labels[1]) == 2 and len(labels[2]) == 2
+
+
+# --- 12: overlays at the background's last row and column ------------------------------
+def test_overlays_in_the_last_row_and_column(fused):
+    cfg = fused.PipeConfig(margins=(0.05, 9, 0.1, 3))
+    rng = np.random.default_rng(43)
+    src = rng.integers(0, 256, (4, 150, 170, 3), np.uint8)
+    bgs = rng.integers(0, 256, (2, 128, 160, 3), np.uint8)
+    specs = [(61.0, "o", 1, 0.3), (200.0, "h", 1, 0.25), (310.0, "v", 0, 0.28), (15.0, "hv", 0, 0.35)]
+
+    def place(ov):
+        (w0, h0), _, _, (w3, h3) = ov
+        return [(160 - w0, 128 - h0), (70, 60), (64, 48), (160 - w3, 128 - h3)]
+
+    plan = _given(fused, (150, 170), (128, 160), 2, cfg, 2, specs, place)
+    it = plan.items
+    for i in (0, 3):
+        assert it["x"][i] + it["ov_w"][i] == 160 and it["y"][i] + it["ov_h"][i] == 128
+    b = Scenes(fused, src, bgs, plan, cfg)
+    b.check_composites()
+    b.check_rows(1, 128)
+
+
+# --- 13: guards and checks ----------------------------------------------------------------
+def test_guards(fused, noise):
+    from image_processor_pipeline_amd import _native as N
+    runner = fused.SceneRunner(noise.plan, DEV)
+    with pytest.raises(N.NativeError):
+        runner.scene_boxes()
+    out = torch.full_like(noise.out, 3)
+    with pytest.raises(ValueError):
+        runner.run(noise.dsrc[:11], noise.dbgs, out)
+    with pytest.raises(ValueError):
+        runner.run(noise.dsrc, noise.dbgs, torch.full((12, 128, 160, 3), 3, dtype=torch.uint8, device=DEV))
+    with pytest.raises(N.NativeUnavailable):
+        runner.run(noise.dsrc.cpu(), noise.dbgs, out)
+    assert bool((out == 3).all()) and not runner._hpass_done     # refused before any launch
+    for kw in (dict(alpha_min=0), dict(cover_min=256), dict(cover_min=1.5)):
+        with pytest.raises(ValueError):
+            noise.runner.scene_boxes(**kw)
+
+
+def test_c_entry_points_refuse_bad_arguments(fused, noise):
+    from image_processor_pipeline_amd import _native as N
+    lib, r, p, sp = N.load(), noise.runner, noise.plan.pipe, noise.plan
+    n = len(sp.descs)
+    st = torch.cuda.current_stream().cuda_stream
+    hsv = N.np_ptr(p.hsv)
+    assert lib.ipp_pipe_hpass(noise.dsrc.data_ptr(), r.tmp.data_ptr(), r.coefs.data_ptr(), r.descs.data_ptr(), 0,
+                              p.max_out_w, p.max_rows, 3, hsv, p.tap_format, st) == N.IPP_OK
+    for kw in (dict(src=None), dict(tmp=None), dict(cn=2), dict(fmt=0), dict(rows=0)):
+        a = dict(src=noise.dsrc.data_ptr(), tmp=r.tmp.data_ptr(), cn=3, fmt=p.tap_format, rows=p.max_rows)
+        a.update(kw)
+        assert lib.ipp_pipe_hpass(a["src"], a["tmp"], r.coefs.data_ptr(), r.descs.data_ptr(), n, p.max_out_w,
+                                  a["rows"], a["cn"], hsv, a["fmt"], st) == N.IPP_E_ARG, kw
+    for kw in (dict(dst=None), dict(fmt=2), dict(w=N.IPP_PIPE_MAX_OV_W + 1), dict(w=p.bg_w + 1)):
+        a = dict(dst=noise.out.data_ptr(), fmt=p.tap_format, w=p.max_ov_w)
+        a.update(kw)
+        assert lib.ipp_pipe_vblend_over(r.tmp.data_ptr(), a["dst"], r.coefs.data_ptr(), r.descs.data_ptr(), 4,
+                                        p.bg_w, p.bg_h, a["w"], p.max_ov_h, a["fmt"], st) == N.IPP_E_ARG, kw
+    rows = torch.zeros(6 * n, dtype=torch.int32, device=DEV)
+    nb = lib.ipp_pipe_scene_scratch_bytes(n, 4, 3, p.max_ov_w, p.max_ov_h)
+    pitch = (p.max_ov_w + 15) // 16 * 16
+    assert nb == 256 + n * p.max_ov_h * pitch
+    assert lib.ipp_pipe_scene_scratch_bytes(n, 4, 0, p.max_ov_w, p.max_ov_h) == N.IPP_E_ARG
+    scratch = torch.empty(nb, dtype=torch.uint8, device=DEV)
+    sl = _t(sp.scene_layer)
+    for kw in (dict(a=0), dict(c=0), dict(c=256), dict(fmt=0), dict(sl=None), dict(scratch=None), dict(rows=None),
+               dict(K=0)):
+        a = dict(a=1, c=128, fmt=p.tap_format, sl=sl.data_ptr(), scratch=scratch.data_ptr(), rows=rows.data_ptr(), K=3)
+        a.update(kw)
+        assert lib.ipp_pipe_scene_boxes(r.tmp.data_ptr(), r.coefs.data_ptr(), r.descs.data_ptr(), a["sl"], n, 4,
+                                        a["K"], p.max_ov_w, p.max_ov_h, a["a"], a["c"], a["fmt"], a["scratch"],
+                                        a["rows"], st) == N.IPP_E_ARG, kw
+    torch.cuda.synchronize()

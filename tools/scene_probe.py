@@ -1,0 +1,115 @@
+"""Scene batch against the flat batch of the same overlays ("Scenes").
+
+    python tools/scene_probe.py [--scenes 1024] [--per-scene 4] [--size 1024] [--backgrounds 16]
+                                [--steps 20] [--warmup 3] [--seed 0]
+
+Workload: S scenes × K overlays of size² sources on size² backgrounds with the
+config-3 parameters (fused.PipeConfig()), against PipeRunner.run on the flat
+S·K-item batch of the same sources.  The two runs alternate step by step on
+one device; every time is taken with HIP events on the current stream.  A
+second series times each launch of the scene run and the label launch
+(ipp_pipe_scene_boxes) on their own.  Prints one JSON line."""
+import argparse
+import json
+import statistics
+import sys
+import time
+from pathlib import Path
+
+sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--scenes", type=int, default=1024)
+    ap.add_argument("--per-scene", type=int, default=4)
+    ap.add_argument("--size", type=int, default=1024)
+    ap.add_argument("--backgrounds", type=int, default=16)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--seed", type=int, default=0)
+    args = ap.parse_args()
+
+    import torch
+    from bench import make_sources
+    from image_processor_pipeline_amd import _native as N
+    from image_processor_pipeline_amd import fused
+    from image_processor_pipeline_amd.device import _stream
+
+    dev = torch.device("cuda:0")
+    S, K, Z, nbg = args.scenes, args.per_scene, args.size, args.backgrounds
+    n = S * K
+    cfg = fused.PipeConfig()
+    src = make_sources(0, n, Z, args.seed, dev)
+    g0 = torch.Generator(device=dev)
+    g0.manual_seed(1)
+    bgs = torch.randint(0, 256, (nbg, Z, Z, 3), dtype=torch.uint8, device=dev, generator=g0)
+    t0 = time.perf_counter()
+    flat_plan = fused.plan_pipe((Z, Z), n, (Z, Z), nbg, cfg, seed=args.seed * 7919)
+    t1 = time.perf_counter()
+    scene_plan = fused.plan_scenes((Z, Z), S, K, (Z, Z), nbg, cfg, seed=args.seed * 7919)
+    t2 = time.perf_counter()
+    flat, scene = fused.PipeRunner(flat_plan, dev), fused.SceneRunner(scene_plan, dev)
+    out_flat = torch.empty((n, Z, Z, 3), dtype=torch.uint8, device=dev)
+    out_scene = torch.empty((S, Z, Z, 3), dtype=torch.uint8, device=dev)
+
+    def timed(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        return a, b
+
+    ms_flat, ms_scene, ms_label = [], [], []
+    for step in range(args.warmup + args.steps):
+        ef = timed(lambda: flat.run(src, bgs, out_flat))
+        es = timed(lambda: scene.run(src, bgs, out_scene))
+        el = timed(lambda: scene._launch_boxes(1, 128))
+        torch.cuda.synchronize(dev)
+        if step >= args.warmup:
+            ms_flat.append(ef[0].elapsed_time(ef[1]))
+            ms_scene.append(es[0].elapsed_time(es[1]))
+            ms_label.append(el[0].elapsed_time(el[1]))
+
+    # per launch: the scene run's own sequence, an event pair around each launch
+    p, lib, st = scene_plan.pipe, scene.lib, _stream(dev)
+    hsv = N.np_ptr(p.hsv)
+    tmp, coefs, dp = scene.tmp.data_ptr(), scene.coefs.data_ptr(), scene._dptr
+    launches = [("hpass_bgcopy(layer 0)", lambda: lib.ipp_pipe_hpass_bgcopy(
+        src.data_ptr(), tmp, coefs, dp(0), S, p.max_out_w, p.max_rows, 3, hsv, p.tap_format, bgs.data_ptr(),
+        out_scene.data_ptr(), st))]
+    if K > 1:
+        launches.append((f"hpass(layers 1..{K - 1})", lambda: lib.ipp_pipe_hpass(
+            src.data_ptr(), tmp, coefs, dp(S), S * (K - 1), p.max_out_w, p.max_rows, 3, hsv, p.tap_format, st)))
+    launches.append(("vblend_bands(layer 0)", lambda: lib.ipp_pipe_vblend_bands(
+        tmp, bgs.data_ptr(), out_scene.data_ptr(), coefs, dp(0), S, p.bg_w, p.bg_h, p.max_ov_w, p.max_ov_h,
+        p.tap_format, st)))
+    for k in range(1, K):
+        launches.append((f"vblend_over(layer {k})", lambda k=k: lib.ipp_pipe_vblend_over(
+            tmp, out_scene.data_ptr(), coefs, dp(k * S), S, p.bg_w, p.bg_h, p.max_ov_w, p.max_ov_h, p.tap_format,
+            st)))
+    per = {name: [] for name, _ in launches}
+    for step in range(args.warmup + args.steps):
+        evs = [(name, timed(lambda fn=fn: N.check(fn(), name))) for name, fn in launches]
+        torch.cuda.synchronize(dev)
+        if step >= args.warmup:
+            for name, (a, b) in evs:
+                per[name].append(a.elapsed_time(b))
+
+    def summary(v):
+        return {"median_ms": round(statistics.median(v), 3), "min_ms": round(min(v), 3), "max_ms": round(max(v), 3)}
+
+    print(json.dumps({
+        "device": torch.cuda.get_device_name(dev), "scenes": S, "per_scene": K, "size": Z, "backgrounds": nbg,
+        "steps": args.steps, "warmup": args.warmup,
+        "plan_host_ms": {"flat": round((t1 - t0) * 1e3, 1), "scenes": round((t2 - t1) * 1e3, 1)},
+        "flat_step": summary(ms_flat), "scene_step": summary(ms_scene), "label_launch": summary(ms_label),
+        "scene_launches": {name: summary(v) for name, v in per.items()},
+        "copy_read_bytes": {"flat": flat_plan.copy_read_bytes, "scenes": scene_plan.copy_read_bytes},
+        "composite_bytes": {"flat": out_flat.numel(), "scenes": out_scene.numel()},
+        "scratch_label_bytes": int(scene._scratch.numel()),
+    }))
+
+
+if __name__ == "__main__":
+    main()
