@@ -130,13 +130,14 @@ def rotate_expand_bilinear(img: np.ndarray, angle: float) -> np.ndarray:
 
 
 def getbbox_alpha(img: np.ndarray) -> Optional[Tuple[int, int, int, int]]:
-    """Pillow ``getbbox()`` (alpha_only=True) on an RGBA array.
+    """Pillow ``getbbox()`` (alpha_only=True) on an (h, w, cn) array: the
+    alpha band alone for LA / RGBA (cn 2 / 4), any band for L / RGB.
 
     PIL/Image.py:1480-1497; reference call site rotations.py:99.
     Returns (x0, y0, x1, y1) or None.
     """
-    if img.shape[2] == 4:
-        nz = img[:, :, 3] != 0
+    if img.shape[2] in (2, 4):
+        nz = img[:, :, -1] != 0
     else:
         nz = np.any(img != 0, axis=2)
     rows = np.flatnonzero(nz.any(axis=1))

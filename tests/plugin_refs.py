@@ -1,0 +1,402 @@
+"""Case tables and small references of the plugin-path kernel tests
+(test_plugin_refs_cpu.py, test_gpu_plugin_kernels.py).
+
+The kernels behind the drop-in plugins (ipp_lanczos_h/v, ipp_paste_blend,
+ipp_copy_window, ipp_hsv_mask, ipp_alpha_bbox(_min), ipp_enhance_*,
+ipp_box_pass, ipp_rotate_bilinear) are compared with ``oracle/ops.py``; the CPU
+module compares ``oracle/ops.py`` with live Pillow on the same cases.  This
+module holds
+
+* the seeded case tables — shapes, sizes, positions, factors, radii and α
+  palettes, chosen from the kernels' tilings (64 outputs × 4 lines, 16-byte
+  chunks of 1024-byte blocks, 1024- and 256-pixel tiles, 64×16 bbox tiles);
+* the image builders, each a pure function of its arguments;
+* the numpy references that ``oracle/ops.py`` has no routine for (window
+  slices with flips, the box of α ≥ alpha_min).
+
+No GPU work here.  Sizes are (w, h) in the tables and (h, w, cn) in arrays.
+"""
+import numpy as np
+
+from oracle import ops
+
+# ---------------------------------------------------------------------------
+# RGBA images with the α values and colours where premultiply / unpremultiply
+# take their special branches: α 0 and 255 pass a pixel through, α 1 and 2
+# make 255·c / α overflow 255 (the clamp), 254 is the last α that divides.
+# ---------------------------------------------------------------------------
+
+ALPHA_PALETTE = (0, 1, 2, 127, 128, 254, 255)
+COLOUR_PALETTE = (0, 1, 127, 128, 254, 255, 255, 255)   # 255 three times as likely
+
+
+def rgba_image(seed: int, w: int, h: int, mode: str = "palette") -> np.ndarray:
+    """(h, w, 4) uint8.  mode: 'palette' (α from ALPHA_PALETTE, colours half
+    from COLOUR_PALETTE and half random), 'white' (colour 255 everywhere, α from
+    ALPHA_PALETTE), 'transparent' (α 0, random colours), 'opaque' (α 255)."""
+    rng = np.random.default_rng(seed)
+    img = np.empty((h, w, 4), np.uint8)
+    pal = np.asarray(COLOUR_PALETTE, np.uint8)[rng.integers(0, len(COLOUR_PALETTE), (h, w, 3))]
+    rnd = rng.integers(0, 256, (h, w, 3), np.uint8)
+    img[..., :3] = np.where(rng.random((h, w, 1)) < 0.5, pal, rnd)
+    img[..., 3] = np.asarray(ALPHA_PALETTE, np.uint8)[rng.integers(0, len(ALPHA_PALETTE), (h, w))]
+    if mode == "white":
+        img[..., :3] = 255
+    elif mode == "transparent":
+        img[..., 3] = 0
+    elif mode == "opaque":
+        img[..., 3] = 255
+    elif mode != "palette":
+        raise ValueError(mode)
+    return img
+
+
+def rgb_image(seed: int, w: int, h: int) -> np.ndarray:
+    return np.random.default_rng(seed).integers(0, 256, (h, w, 3), np.uint8)
+
+
+# ---------------------------------------------------------------------------
+# 1. LANCZOS, single image: (in_w, in_h, out_w, out_h, image mode).
+#    k_lanczos_h / k_lanczos_v: a block is 64 outputs × 4 lines.
+# ---------------------------------------------------------------------------
+
+LANCZOS_CASES = [
+    (1, 1, 7, 5, "palette"),          # 1-pixel input: one tap of 2^22 per output
+    (9, 1, 3, 1, "palette"),          # one-axis: H pass premultiplies and unpremultiplies
+    (1, 9, 1, 20, "palette"),         # one-axis: V pass does both
+    (5, 5, 9, 5, "palette"),
+    (5, 5, 5, 9, "palette"),
+    (3, 2, 1, 1, "palette"),          # 1-pixel output
+    (3, 50, 64, 7, "palette"),
+    (65, 33, 17, 16, "palette"),
+    (20, 9, 63, 5, "palette"),        # outputs of 63 / 64 / 65 px along x ...
+    (20, 9, 64, 5, "palette"),
+    (20, 9, 65, 5, "palette"),
+    (9, 20, 5, 63, "palette"),        # ... and along y
+    (9, 20, 5, 64, "palette"),
+    (9, 20, 5, 65, "palette"),
+    (7, 3, 11, 2, "palette"),         # intermediate (H-pass) line counts of 3 / 4 / 5
+    (7, 4, 11, 3, "palette"),
+    (7, 5, 11, 7, "palette"),
+    (8, 6, 64, 48, "palette"),        # 8× upscale
+    (330, 7, 11, 5, "palette"),       # 30× downscale: 181 taps per output
+    (7, 330, 5, 11, "palette"),
+    (330, 1, 11, 1, "white"),         # the long filter in the one-axis form
+    (13, 11, 7, 17, "transparent"),
+    (13, 11, 7, 17, "opaque"),
+    (13, 11, 7, 17, "white"),         # colour 255 under every α of the palette
+    (8, 6, 64, 48, "white"),
+    (65, 33, 17, 16, "white"),
+]
+LANCZOS_SEED = 8100
+
+
+def lanczos_image(k: int) -> np.ndarray:
+    in_w, in_h, _, _, mode = LANCZOS_CASES[k]
+    return rgba_image(LANCZOS_SEED + k, in_w, in_h, mode)
+
+
+def lanczos_lines(in_h: int, out_h: int) -> int:
+    """Rows the H pass of a two-axis resize produces: the span of input rows
+    the V taps read (Resample.c ybox_first .. ybox_last)."""
+    _, bv, _ = ops.precompute_coeffs(in_h, 0.0, float(in_h), out_h)
+    return int(bv[-1, 0] + bv[-1, 1] - bv[0, 0])
+
+
+# ---------------------------------------------------------------------------
+# 2. Overlays, ragged: (ov_w, ov_h, out_w, out_h, bg_w, bg_h, x, y, mode).
+#    k_paste_blend: 16 bytes of a row per thread, 1024 bytes per block row;
+#    3·bg_w mod 16 ≠ 0 leaves every row but the first of a packed background
+#    misaligned (byte path).  Widths 341 / 342 give rows of 1023 / 1026 bytes.
+#    The small items make most blocks of the launch (sized by the largest)
+#    exit early.  Item 5 changes one axis only: per-image branch mid-list.
+# ---------------------------------------------------------------------------
+
+OVERLAY_ITEMS = [
+    (3, 2, 1, 1, 5, 4, 4, 3, "palette"),          # 1×1 on the last pixel
+    (1, 1, 7, 5, 21, 9, 0, 0, "palette"),          # top left
+    (8, 6, 64, 48, 341, 50, 277, 0, "palette"),    # top right
+    (330, 7, 11, 5, 342, 37, 0, 32, "palette"),    # bottom left
+    (65, 33, 17, 16, 21, 16, 4, 0, "white"),       # full height, flush right
+    (9, 1, 3, 1, 6, 3, 3, 2, "palette"),           # one-axis; bottom right
+    (3, 50, 64, 7, 341, 50, 1, 43, "palette"),     # bottom edge
+    (20, 9, 63, 5, 342, 6, 279, 1, "palette"),     # bottom right
+    (7, 3, 11, 2, 16, 7, 5, 5, "palette"),         # bottom right
+    (13, 11, 7, 17, 16, 17, 2, 0, "transparent"),
+    (7, 5, 11, 7, 21, 9, 10, 2, "palette"),        # flush right and bottom
+    (13, 11, 7, 17, 341, 50, 334, 33, "opaque"),   # bottom right
+    (9, 20, 5, 63, 342, 64, 11, 1, "palette"),     # bottom edge
+    (4, 3, 5, 4, 5, 4, 0, 0, "palette"),           # covers its whole background
+    (5, 7, 3, 4, 6, 9, 1, 2, "white"),             # interior
+]
+OVERLAY_SEED = 8200
+OVERLAY_ALPHA_MINS = (None, 1, 128, 255)
+
+
+def overlay_inputs():
+    """(overlays, backgrounds, sizes, positions) of OVERLAY_ITEMS, as
+    batch_ops.overlays takes them."""
+    ovs, bgs, sizes, pos = [], [], [], []
+    for k, (ow, oh, nw, nh, bw, bh, x, y, mode) in enumerate(OVERLAY_ITEMS):
+        ovs.append(rgba_image(OVERLAY_SEED + k, ow, oh, mode))
+        bgs.append(rgb_image(OVERLAY_SEED + 500 + k, bw, bh))
+        sizes.append((nw, nh))
+        pos.append((x, y))
+    return ovs, bgs, sizes, pos
+
+
+# ---------------------------------------------------------------------------
+# 3. Paste through the C ABI with padded rows:
+#    (bg_w, bg_h, ov_w, ov_h, x, y, bg_pitch, dst_pitch).  Pitches that are
+#    multiples of 16 keep the vector path (its last chunk of a 1023-byte row
+#    is partial), the others force the byte path.
+# ---------------------------------------------------------------------------
+
+PASTE_PITCH_CASES = [
+    (21, 9, 7, 5, 14, 4, 70, 80),
+    (341, 6, 64, 5, 277, 1, 1040, 1040),
+    (342, 5, 1, 1, 341, 4, 1031, 1029),      # 1×1 overlay on the last pixel
+    (6, 5, 6, 5, 0, 0, 32, 19),              # overlay covers the whole background
+    (16, 7, 16, 7, 0, 0, 64, 64),            # the same, rows of whole 16-byte chunks
+    (5, 4, 2, 2, 0, 2, 16, 31),              # bottom left
+]
+PASTE_SEED = 8300
+PASTE_SENTINEL = 0xA5
+
+
+def paste_inputs(k: int):
+    """(bg (h, w, 3), ov (h, w, 4)) of PASTE_PITCH_CASES[k]."""
+    bw, bh, ow, oh = PASTE_PITCH_CASES[k][:4]
+    return rgb_image(PASTE_SEED + k, bw, bh), rgba_image(PASTE_SEED + 100 + k, ow, oh)
+
+
+# ---------------------------------------------------------------------------
+# 4. Window copies: images (w, h, cn; cn 0 = a 2-D array) and jobs
+#    (image, (x0, y0, w, h), flip bits).  k_copy_rows: 16 bytes per thread, 1024
+#    per block row; flip bit 0 (mirror x) takes the per-byte path.
+# ---------------------------------------------------------------------------
+
+COPY_IMAGES = [
+    (1025, 5, 0),    # 0: 2-D, rows of 1025 bytes
+    (17, 4, 0),      # 1: 2-D, rows of 17 bytes
+    (341, 6, 3),     # 2: rows of 1023 bytes
+    (256, 5, 4),     # 3: rows of 1024 bytes
+    (9, 7, 3),       # 4
+    (6, 3, 4),       # 5
+    (1, 1, 0),       # 6: 2-D, one pixel
+    (1, 1, 4),       # 7
+]
+COPY_SEED = 8400
+COPY_JOBS = [
+    (0, (0, 0, 1025, 5), 0), (0, (0, 0, 1025, 5), 3), (0, (1, 0, 1024, 5), 1), (0, (0, 1, 1024, 4), 2),
+    (0, (2, 2, 1023, 3), 0), (0, (1, 0, 1023, 1), 1), (0, (1024, 0, 1, 5), 2),      # last column
+    (0, (0, 4, 1025, 1), 1),                                                        # last row
+    (1, (0, 0, 17, 4), 0), (1, (0, 0, 17, 4), 1), (1, (1, 0, 16, 4), 2), (1, (0, 1, 16, 3), 3),
+    (1, (2, 0, 15, 4), 0), (1, (1, 3, 15, 1), 3), (1, (16, 0, 1, 4), 0), (1, (0, 3, 17, 1), 2),
+    (2, (0, 0, 341, 6), 0), (2, (0, 0, 341, 6), 1), (2, (0, 0, 341, 6), 2), (2, (336, 1, 5, 4), 3),
+    (2, (340, 0, 1, 6), 0), (2, (0, 5, 341, 1), 3),
+    (3, (0, 0, 256, 5), 0), (3, (0, 0, 256, 5), 3), (3, (252, 0, 4, 5), 1), (3, (0, 4, 256, 1), 2),
+    (3, (255, 4, 1, 1), 0),
+    (4, (0, 0, 9, 7), 1), (4, (4, 3, 5, 4), 2), (4, (8, 6, 1, 1), 3), (4, (3, 0, 5, 7), 0),
+    (5, (0, 0, 6, 3), 3), (5, (2, 0, 4, 3), 0), (5, (0, 2, 6, 1), 1), (5, (5, 0, 1, 3), 2),
+    (6, (0, 0, 1, 1), 0), (6, (0, 0, 1, 1), 3), (7, (0, 0, 1, 1), 1), (7, (0, 0, 1, 1), 2),
+]
+
+
+def copy_images():
+    out = []
+    for k, (w, h, cn) in enumerate(COPY_IMAGES):
+        shape = (h, w) if cn == 0 else (h, w, cn)
+        out.append(np.random.default_rng(COPY_SEED + k).integers(0, 256, shape, np.uint8))
+    return out
+
+
+def window_ref(img: np.ndarray, window, flip: int) -> np.ndarray:
+    """The window (x0, y0, w, h) of img, mirrored in x (flip bit 0) and / or in
+    y (bit 1): recadrages.py:46 crops and symmetry.py:114-119 flips."""
+    x0, y0, w, h = window
+    out = img[y0:y0 + h, x0:x0 + w]
+    if flip & 1:
+        out = out[:, ::-1]
+    if flip & 2:
+        out = out[::-1]
+    return np.ascontiguousarray(out)
+
+
+# ---------------------------------------------------------------------------
+# 5. HSV masks, ragged: images (w, h, cn) and (ranges, zones, gimp scale) sets.
+#    A zone is (top, bottom, left, right) margins of mask[t:H-b, l:W-r] with
+#    numpy slice semantics on the image's own H and W.  The all-colour range
+#    with the negative zone keeps the last 3 rows × 4 columns of every image,
+#    wherever that is; the 40-row margins are empty for every image here; the
+#    (2, 1, 1, 3) zone is empty for the images smaller than it.
+# ---------------------------------------------------------------------------
+
+HSV_IMAGES = [(1, 1, 3), (1, 1, 4), (3, 2, 4), (4, 5, 3), (65, 17, 3), (64, 16, 4), (70, 33, 3), (1, 7, 4),
+              (130, 19, 3)]
+HSV_SEED = 8500
+HSV_SETS = [
+    ([(0, 0, 0, 180, 255, 150), (15, 60, 200, 35, 255, 255), (0, 0, 0, 180, 255, 255), (100, 3, 9, 170, 254, 254),
+      (0, 0, 0, 180, 255, 255)],
+     [(2, 1, 1, 3), None, (-3, -2, -4, -1), (5, 10, 3, 7), (40, 40, 0, 0)], False),
+    ([(30, 20, 30, 90, 80, 90), (300, 10, 10, 360, 100, 60), (0, 0, 0, 360, 100, 100)],
+     [(0, 0, 0, 0), (-5, 200, 10, -3), (1, 1, 2, 60)], True),
+]
+
+
+def hsv_images():
+    out = []
+    for k, (w, h, cn) in enumerate(HSV_IMAGES):
+        img = np.random.default_rng(HSV_SEED + k).integers(0, 256, (h, w, cn), np.uint8)
+        img[::3, ::2, :3] //= 3                       # dark pixels for the V ranges
+        img[1::4, :, :3] = img[1::4, :, :1]           # greys (S = 0)
+        out.append(img)
+    return out
+
+
+# ---------------------------------------------------------------------------
+# 6. Alpha boxes.  k_alpha_bbox / k_alpha_bbox_min: 64×16 pixels per block.
+#    Images of 2 and 4 channels are judged by their last band, the others by
+#    any band (Pillow getbbox(alpha_only=True)).
+# ---------------------------------------------------------------------------
+
+BBOX_SEED = 8600
+BBOX_ALPHA_MINS = (1, 2, 128, 255)
+
+
+def _blob(seed: int, w: int, h: int, cn: int, x0: int, y0: int, x1: int, y1: int) -> np.ndarray:
+    """Non-zero colour everywhere (so only the last band can bound an alpha
+    image), last band 0 outside [x0, x1) × [y0, y1) and drawn from
+    ALPHA_PALETTE inside, so the box shrinks as alpha_min grows."""
+    rng = np.random.default_rng(seed)
+    img = rng.integers(1, 256, (h, w, cn), np.uint8)
+    a = np.zeros((h, w), np.uint8)
+    a[y0:y1, x0:x1] = np.asarray(ALPHA_PALETTE, np.uint8)[rng.integers(0, len(ALPHA_PALETTE), (y1 - y0, x1 - x0))]
+    if cn in (2, 4):
+        img[..., -1] = a
+    else:
+        img[a == 0] = 0
+    return img
+
+
+def _dot(w: int, h: int, cn: int, x: int, y: int, value: int) -> np.ndarray:
+    """One non-zero pixel: its last band is `value`; an alpha image's colour
+    bands are non-zero everywhere."""
+    img = np.zeros((h, w, cn), np.uint8)
+    if cn in (2, 4):
+        img[..., :-1] = 200
+    img[y, x, -1] = value
+    return img
+
+
+def bbox_images(channels=(1, 2, 3, 4)):
+    """Images for one ragged box call, channel counts cycling through
+    `channels`: an empty one, a single pixel at each corner, and blobs on
+    sizes around the 64×16 tile."""
+    cn = lambda k: channels[k % len(channels)]   # noqa: E731
+    out = [_dot(65, 17, cn(3), 0, 0, 0)]                       # empty (colour without alpha)
+    out[0][..., -1] = 0
+    corners = [(65, 17, 0, 0, 255), (65, 17, 64, 0, 1), (63, 15, 0, 14, 128), (64, 16, 63, 15, 254),
+               (130, 33, 129, 32, 2), (1, 1, 0, 0, 127)]
+    for k, (w, h, x, y, v) in enumerate(corners):
+        out.append(_dot(w, h, cn(k), x, y, v))
+    blobs = [(65, 17, 3, 2, 65, 16), (64, 16, 0, 0, 64, 16), (63, 15, 10, 3, 11, 4), (130, 33, 60, 14, 70, 19),
+             (129, 49, 63, 15, 66, 18), (7, 40, 2, 30, 7, 40), (200, 3, 64, 1, 129, 2), (5, 1, 0, 0, 5, 1)]
+    for k, (w, h, x0, y0, x1, y1) in enumerate(blobs):
+        out.append(_blob(BBOX_SEED + k, w, h, cn(k + 2), x0, y0, x1, y1))
+    return out
+
+
+def bbox_alpha_min(img: np.ndarray, alpha_min: int):
+    """(x0, y0, x1, y1) of the pixels whose last band is >= alpha_min, None
+    where there is none."""
+    keep = img[..., -1] >= alpha_min
+    rows = np.flatnonzero(keep.any(axis=1))
+    if rows.size == 0:
+        return None
+    cols = np.flatnonzero(keep.any(axis=0))
+    return int(cols[0]), int(rows[0]), int(cols[-1]) + 1, int(rows[-1]) + 1
+
+
+# ---------------------------------------------------------------------------
+# 7. Enhance.  k_enh_lsum / k_enh_color: 1024 pixels per block; k_box_pass:
+#    256 per block.  A box radius r on a row shorter than 2r + 2 is BoxBlur.c's
+#    edgeA > edgeB branch (every output reads a clamped index).
+# ---------------------------------------------------------------------------
+
+ENHANCE_SHAPES = [(1, 1), (1, 40), (40, 1), (3, 4), (4, 5), (5, 6), (17, 16),
+                  (16, 16), (1, 257), (32, 32), (25, 41)]       # (w, h)
+ENHANCE_RADII = (0.9, 1.5, 2.2, 3.0)
+ENHANCE_NARROW = 6          # 2r + 2 for the largest box radius here (r = 2)
+ENHANCE_FACTORS = (0.0, 1.0, float(np.nextafter(np.float32(1), np.float32(0))), 0.7, 1.3, 2.5, -0.3)
+ENHANCE_BASE = (1.1, 0.9, 1.2)     # the two factors that are not being varied
+ENHANCE_SEED = 8700
+
+
+def enhance_luts() -> np.ndarray:
+    return np.random.default_rng(ENHANCE_SEED - 1).integers(0, 256, (3, 256), np.uint8)
+
+
+def enhance_ragged():
+    """Items (image, (brightness, contrast, color), blur radius | None, LUT
+    flag) of the one ragged call: every shape narrower or shorter than
+    ENHANCE_NARROW under all four radii, every other shape under one radius and
+    once without blur, the LUT flag alternating."""
+    mild = [(1.3, 0.7, 1.2999), (0.7, 1.3, 0.7), (1.0, 1.0, 0.0), (0.9, 1.1, 1.0), (1.25, 0.75, 1.1)]
+    items = []
+    for s, (w, h) in enumerate(ENHANCE_SHAPES):
+        radii = list(ENHANCE_RADII) if min(w, h) < ENHANCE_NARROW else [ENHANCE_RADII[s % 4], None]
+        if (w, h) == (1, 1):
+            radii.append(None)
+        for j, r in enumerate(radii):
+            k = len(items)
+            items.append((rgb_image(ENHANCE_SEED + k, w, h), mild[k % len(mild)], r, (k + j + s) % 2 == 0))
+    return items
+
+
+def enhance_factor_sweep():
+    """Every factor of ENHANCE_FACTORS in each of the three positions (the
+    other two at ENHANCE_BASE), on one 1025-pixel image; the last seven blurred."""
+    img = rgb_image(ENHANCE_SEED + 900, 25, 41)
+    items = []
+    for pos in range(3):
+        for f in ENHANCE_FACTORS:
+            fs = list(ENHANCE_BASE)
+            fs[pos] = f
+            items.append((img, tuple(fs), 1.5 if pos == 2 else None, pos == 1))
+    return items
+
+
+def enhance_constant_images():
+    """All black (Σ L = 0: no wave adds to the sum), all white, and the pair of
+    greys 10 and 11 whose mean L is 10.5 (Contrast rounds it to 11)."""
+    black = np.zeros((33, 32, 3), np.uint8)            # 1056 px: two blocks
+    white = np.full((5, 7, 3), 255, np.uint8)
+    greys = np.array([[[10, 10, 10], [11, 11, 11]]], np.uint8)
+    return [(black, (1.3, 0.7, 1.2), None, False), (black, (1.0, 2.5, 1.0), 1.5, True),
+            (white, (1.3, 0.7, 1.2), None, True), (white, (0.7, 1.3, 0.7), 2.2, False),
+            (greys, (1.0, 0.5, 1.0), None, False), (greys[:, ::-1].copy(), (1.0, 0.5, 0.7), None, False)]
+
+
+def enhance_ref(img: np.ndarray, factors, radius, luts) -> np.ndarray:
+    """The ops chain of tranfo.enhance_image for explicit parameters."""
+    out = ops.enhance_color(ops.enhance_contrast(ops.enhance_brightness(img, factors[0]), factors[1]), factors[2])
+    if radius is not None:
+        out = ops.gaussian_blur(out, radius)
+    if luts is not None:
+        out = np.stack([luts[c][out[..., c]] for c in range(3)], axis=-1)
+    return out
+
+
+# ---------------------------------------------------------------------------
+# 8. Bilinear rotate: (w, h) × angles; 0 / 90 / 180 / 270 are transposes.
+# ---------------------------------------------------------------------------
+
+ROTATE_SHAPES = [(1, 1), (1, 7), (13, 2), (64, 64)]
+ROTATE_ANGLES = (0.0, 90.0, 180.0, 270.0, 33.3, 117.0, 301.7)
+ROTATE_SEED = 8800
+
+
+def rotate_image(k: int) -> np.ndarray:
+    w, h = ROTATE_SHAPES[k]
+    return rgba_image(ROTATE_SEED + k, w, h)
