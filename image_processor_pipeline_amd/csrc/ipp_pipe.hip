@@ -24,7 +24,7 @@
 // [line0, line0 + lines).
 //
 // Experiment switches left in this file are the live ones that DESIGN.md §3
-// names (IPP_HP_BANDS, IPP_COPY_GROUP/SLABS, IPP_VB_WPE/DB/HOIST_MAX); the
+// names (IPP_COPY_GROUP/SLABS, IPP_VB_WPE/DB/HOIST_MAX); the
 // diagnostic builds of rounds 1-5 and the closed A/B switches were removed in
 // round 6 (their numbers stay in DESIGN.md).
 #include <algorithm>
@@ -258,11 +258,15 @@ __device__ __forceinline__ Hp2Chunk hp2_chunk(const int4* hdr, int s0, int ntile
 // slower than this one-band block: the taps, meta and bias held across the
 // next band's phase 1 cost more than the tap loads they save; DESIGN.md §3
 // "Round 6, multi-band H blocks".)
+//
+// The body sweeps the output tiles [s_lo, s_hi) (wave-uniform, s_lo < s_hi):
+// hpass_block trims the band's leading and trailing tiles whose whole input
+// window is fill and writes their constant T groups itself (fill_trim).
 template <int NR, bool ZONES, int CN, bool CLAMP>
 __device__ __forceinline__ void hpass2_body(const HsvTables<NR>& T, WinRing& win, int wave, const Hp2Block& B,
                                             uint8_t* __restrict__ tmp, const int32_t* __restrict__ coefs,
                                             const ipp_resample_desc& h, int row0, int nrows, const int32_t* zc0,
-                                            const int32_t* zcw, uint32_t zrow) {
+                                            const int32_t* zcw, uint32_t zrow, int s_lo, int s_hi) {
     const int lane = threadIdx.x & 63;
     const int r = 2 * (lane >> 3) + ((lane >> 1) & 1);  // the lane's window row
     const int ntiles = (h.out_len + 15) >> 4;
@@ -271,8 +275,8 @@ __device__ __forceinline__ void hpass2_body(const HsvTables<NR>& T, WinRing& win
     const uint4* tblk = reinterpret_cast<const uint4*>(coefs + h.coef_off + 20 * (int64_t)ntiles);
     const uint32_t sx = (uint32_t)HP_STEPC * (uint32_t)B.b0, sy = (uint32_t)HP_STEPC * (uint32_t)B.b3;  // per-step advance
 
-    int filled = hdr[0].x;  // ring holds M columns [.., filled)
-    Hp2Chunk ck = hp2_chunk(hdr, 0, ntiles, filled, wave);
+    int filled = hdr[s_lo].x;  // ring holds M columns [.., filled)
+    Hp2Chunk ck = hp2_chunk(hdr, s_lo, s_hi, filled, wave);
     // Lane's first column of step 0 and its source position.
     auto lane_x = [&](const Hp2Chunk& c) { return c.c0 + 16 * wave + 8 * ((lane >> 2) & 1) + 4 * (lane & 1); };
     // (24-bit products: columns < 2^15 and |b| ≤ 2^16; a 32-bit product made
@@ -315,7 +319,7 @@ __device__ __forceinline__ void hpass2_body(const HsvTables<NR>& T, WinRing& win
         {
             // Loaded unconditionally (a valid tile stands in when the wave
             // has none), so the loads in flight do not depend on the path.
-            const int te = min(t, ntiles - 1);
+            const int te = min(t, s_hi - 1);
             th = hdr[te];
             // wave-uniform: kept in SGPRs
             th.x = __builtin_amdgcn_readfirstlane(th.x);
@@ -329,7 +333,7 @@ __device__ __forceinline__ void hpass2_body(const HsvTables<NR>& T, WinRing& win
             for (int p = 0; p < 3; ++p) bn[p] = tblk[th.z + (th.w ? 4 : 0) + lane + p * 64];
             if (!has_tile) th.y = 0;
         }
-        const int te = min(t, ntiles - 1);
+        const int te = min(t, s_hi - 1);
 
         // Phase 1: new M columns → planar LDS ring.  Three register sets
         // rotate so that each step's gathers have two steps of HSV work to land.
@@ -415,9 +419,9 @@ __device__ __forceinline__ void hpass2_body(const HsvTables<NR>& T, WinRing& win
             bias = tbias[min(16 * te + (lane & 15), h.out_len - 1)];
         }
         const int s1 = ck.s1;
-        const bool more = s1 < ntiles;
+        const bool more = s1 < s_hi;
         if (more) {
-            ck = hp2_chunk(hdr, s1, ntiles, filled, wave);
+            ck = hp2_chunk(hdr, s1, s_hi, filled, wave);
             xl = lane_x(ck);
             xxl = B.rowx + (uint32_t)__mul24(xl, B.b0);
             yyl = B.rowy + (uint32_t)__mul24(xl, B.b3);
@@ -858,12 +862,56 @@ __device__ __forceinline__ void hpass_block(Hpass2Lds<NR>& L, const uint8_t* __r
         B.xhi = bhi;
     }
 
+    // Fill trim (forms without zones).  A tile whose whole input window
+    // [hdr.x, hdr.x + 64·hdr.y) misses the band's valid columns sees only fill;
+    // where the fill quad is 0x80808080 (black excluded) every T byte of it is
+    // clip8(2^21 >> 22) ^ 0x80 = 0x80 (the identity in the file header).  The
+    // band's valid columns are an interval and the window starts do not
+    // decrease, so such tiles lead and trail the tile list: the body sweeps
+    // only [s_lo, s_hi), the first to the last tile whose window meets
+    // [xlo, xhi], and the others' constant T groups are stored here, before
+    // any gather is in flight.  One header per lane and a ballot give both
+    // bounds, wave-uniform; items of more than 64 tiles are not trimmed.
+    const int ntiles = (h.out_len + 15) >> 4;
+    int s_lo = 0, s_hi = ntiles;
+    if constexpr (!ZONES) {
+        // raw 0 has h = s = v = 0 (hsv_tab_excl): excluded ⟺ some range holds 0 on all three channels
+        bool black_out = false;
+#pragma unroll
+        for (int k = 0; k < NR; ++k) {
+            const ipp_hsv_range& q = hp.r[k];
+            black_out |= q.lo[0] <= 0 && q.hi[0] >= 0 && q.lo[1] <= 0 && q.hi[1] >= 0 && q.lo[2] <= 0 && q.hi[2] >= 0;
+        }
+        if (black_out && ntiles <= 64) {  // block-uniform
+            const int4* hdr = reinterpret_cast<const int4*>(coefs + h.coef_off);
+            const int4 hv = hdr[min(lane, ntiles - 1)];
+            const bool keep = lane < ntiles && hv.x + 64 * hv.y > B.xlo && hv.x <= B.xhi;
+            const uint64_t km = __builtin_amdgcn_ballot_w64(keep);
+            s_lo = km ? __builtin_ctzll(km) : 0;
+            s_hi = km ? 64 - __builtin_clzll(km) : 0;
+            // The trimmed tiles' T groups (the address arithmetic of the body's
+            // epilogue), one tile per wave and turn.
+            const int ntrim = s_lo + ntiles - s_hi;
+            for (int i = wave; i < ntrim; i += HP_NW) {
+                const int t = i < s_lo ? i : i - s_lo + s_hi;
+                const int xo = 16 * t + (lane & 15);
+                if (xo < h.out_len) {
+                    const int grp = (row0 >> 2) + (lane >> 4);
+                    uint4* dst = reinterpret_cast<uint4*>(tmp + h.dst_off + (int64_t)grp * h.dst_pitch) + xo;
+                    const uint32_t w[4] = {0x80808080u, 0x80808080u, 0x80808080u, 0x80808080u};
+                    store16<2>(reinterpret_cast<uint8_t*>(dst), 16, true, w);
+                }
+            }
+            if (s_lo >= s_hi) return;  // nothing to sweep (block-uniform: no barrier was met)
+        }
+    }
+
     // (the table barrier is in the body, after the first gathers)
     const int nrows = min(HR, h.lines - row0);
     if (fast)
-        hpass2_body<NR, ZONES, CN, false>(L.T, L.win, wave, B, tmp, coefs, h, row0, nrows, zc0, zcw, zrow);
+        hpass2_body<NR, ZONES, CN, false>(L.T, L.win, wave, B, tmp, coefs, h, row0, nrows, zc0, zcw, zrow, s_lo, s_hi);
     else
-        hpass2_body<NR, ZONES, CN, true>(L.T, L.win, wave, B, tmp, coefs, h, row0, nrows, zc0, zcw, zrow);
+        hpass2_body<NR, ZONES, CN, true>(L.T, L.win, wave, B, tmp, coefs, h, row0, nrows, zc0, zcw, zrow, s_lo, s_hi);
 }
 
 // 4 waves per SIMD (≤ 128 VGPRs); the zone forms get 3 (their per-lane zone
