@@ -29,12 +29,17 @@ def _i32(v):
     return ((np.asarray(v, np.int64) + (1 << 31)) % (1 << 32)) - (1 << 31)
 
 
-def band_valid_columns(g, h, band: int) -> Tuple[int, int]:
+TRIM_SLACK = 2        # columns the kernel widens each row's interval by, on both sides
+
+
+def band_valid_columns(g, h, band: int, slack: int = TRIM_SLACK) -> Tuple[int, int]:
     """(xlo, xhi) of `band` of the item with gather desc `g` and H resample
     desc `h`, in the kernel's float32 arithmetic: per row the x interval where
     0 <= xx(x) < in_w·2^16 and 0 <= yy(x) < in_h·2^16 (both linear in x),
-    widened by 2 columns; then the union over the band's 16 rows.  A band
-    with no valid column gives xlo > xhi."""
+    widened by `slack` columns (the kernel's 2); then the union over the
+    band's 16 rows, as the kernel takes it: rows past the item's last line
+    included.  A band with no valid column gives xlo > xhi.  A smaller `slack`
+    is what tests/test_hpass_trim_conservative.py holds the interval to."""
     f32 = np.float32
     b = [int(v) for v in g["b"]]
     y = int(h["line0"]) + HP_ROWS * band + np.arange(HP_ROWS, dtype=np.int64)
@@ -52,8 +57,8 @@ def band_valid_columns(g, h, band: int) -> Tuple[int, int]:
             lo = np.maximum(lo, np.minimum(t1, t2))
             hi = np.minimum(hi, np.maximum(t1, t2))
     empty = lo > hi
-    ilo = np.where(empty, 0x3FFFFFFF, np.trunc(np.maximum(lo - f32(2), f32(-1e8))).astype(np.int64))
-    ihi = np.where(empty, -0x3FFFFFFF, np.trunc(np.minimum(hi + f32(2), f32(1e8))).astype(np.int64))
+    ilo = np.where(empty, 0x3FFFFFFF, np.trunc(np.maximum(lo - f32(slack), f32(-1e8))).astype(np.int64))
+    ihi = np.where(empty, -0x3FFFFFFF, np.trunc(np.minimum(hi + f32(slack), f32(1e8))).astype(np.int64))
     return int(ilo.min()), int(ihi.max())
 
 
@@ -96,16 +101,23 @@ def trim_enabled(hsv) -> bool:
     return bool(np.any(np.all((r["lo"] <= 0) & (r["hi"] >= 0), axis=-1)))
 
 
+def desc_item(plan, i: int) -> int:
+    """The item of descriptor `i` of a PipePlan (processing order, plan.order)
+    or of a ScenePlan (layer-major, plan.desc_item)."""
+    return int(plan.desc_item[i] if hasattr(plan, "desc_item") else plan.order[i])
+
+
 def h_axis(plan, i: int):
-    """The H tap axis of descriptor `i`: the axes are in item order, the
-    descriptors in processing order (plan.order)."""
-    ax = plan.axes[2 * int(plan.order[i])]
+    """The H tap axis of descriptor `i` of a PipePlan or a ScenePlan: the axes
+    are in item order, the descriptors are not (desc_item)."""
+    ax = plan.axes[2 * desc_item(plan, i)]
     assert int(ax["coef_off"]) == int(plan.descs[i]["h"]["coef_off"])
     return ax
 
 
 def item_bounds(plan, i: int) -> List[Tuple[int, int, int]]:
-    """(s_lo, s_hi, n_tiles) of every band of descriptor `i` of a PipePlan."""
+    """(s_lo, s_hi, n_tiles) of every band of descriptor `i` of a PipePlan or a
+    ScenePlan."""
     d = plan.descs[i]
     win = tile_windows(h_axis(plan, i))
     nt = len(win)

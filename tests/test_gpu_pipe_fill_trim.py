@@ -15,9 +15,20 @@ body taken) is asserted on the plan with the host restatement of the trim
 
 A band in which no tile is kept (s_lo >= s_hi) cannot come out of a plan: the
 cut-out is the rotated canvas's exact alpha box, so every band holds a row
-with a valid column and some tile's window covers it.  The thin-source case
-reaches a band with a single kept tile.  (A tile's window is 64 columns or
-more, so even a 24-px strip keeps two or three tiles in most bands.)
+with a valid column and some tile's window covers it.
+tests/test_hpass_trim_conservative.py asserts this for every band of its
+geometries (no GPU).  The thin-source case reaches a band with a single kept
+tile.  (A tile's window is 64 columns or more, so even a 24-px strip keeps two
+or three tiles in most bands.)
+
+For the same reason an item of one band (lines <= 16) never trims: the union
+over all its rows holds every column of the box.  The one_band case therefore
+pins the other thing such an item can get wrong, the interval itself: the
+rows past the item's end join the union (nrows < 16), and the body gathers
+only the columns inside [xlo, xhi].
+
+The paths that share the H launch (4-channel sources, scenes, the label
+kernels, the 64-tile limit) are in tests/test_gpu_pipe_fill_trim_paths.py.
 """
 import numpy as np
 import pytest
@@ -56,6 +67,13 @@ CASES = {
     # zones: the untouched instantiation
     "zones": ((150, 190), (256, 320), (0, 0, 0, 0), [(30.0, "o", 0.5)],
               {"zones": [None, (10, 0, 0, 5), None, (0, 0, 20, 0)]}),
+    # lines = 16: one band, whose union over the rows is the whole box (nothing can trim)
+    "one_band": ((10, 200), (128, 320), (0, 0, 0, 0), [(2.0, "o", 0.5), (178.0, "hv", 0.5)], {}),
+    # lines % 16 == 1: the last band is one real row and 15 rows past the item's end
+    "one_row_tail": ((35, 60), (128, 160), (0, 0, 0, 0), [(40.0, "o", 0.6), (140.0, "h", 0.6)], {}),
+    # a 4200-px source 0.01° off the axis, flipped: b3 = ±11, 65536·in_w = 2^28 (a float32 ulp of 16 or 32);
+    # the planner takes the 8× downscale of ratio 0.9 on this background
+    "near_axis_wide": ((33, 4200), (48, 640), (0, 0, 0, 0), [(0.01, "hv", 0.9), (179.995, "h", 0.9)], {}),
 }
 
 
@@ -92,6 +110,21 @@ def check_case(name, plan):
     if name in ("upscale", "downscale"):
         nk = HT.tile_windows(HT.h_axis(plan, 0))[:, 1]
         assert (nk.max() == 1) if name == "upscale" else (nk.max() >= 3), (name, nk)
+    if name == "one_band":
+        for i in range(n):
+            assert int(plan.descs[i]["h"]["lines"]) <= 16 and len(bounds[i]) == 1, (name, i)
+            assert bounds[i][0][2] <= HT.TRIM_MAX_TILES and bounds[i] == [(0, bounds[i][0][2], bounds[i][0][2])]
+    if name == "one_row_tail":
+        for i in range(n):
+            assert int(plan.descs[i]["h"]["lines"]) % 16 == 1 and len(bounds[i]) >= 2, (name, i)
+            lo, hi, nt = bounds[i][-1]
+            assert hi - lo < nt, (name, i, bounds[i])                           # the one-row band trims
+    if name == "near_axis_wide":
+        for i in range(n):
+            g, h = plan.descs[i]["g"], plan.descs[i]["h"]
+            assert int(g["in_w"]) >= 4100 and 16 < int(h["lines"]) <= 48, (name, i)
+            assert 0 < abs(int(g["b"][3])) <= 16 and abs(int(g["b"][0])) >= 65000, (name, i, g["b"])
+            assert int(g["flip"]) != 0 and bounds[i][0][2] <= HT.TRIM_MAX_TILES
     if name == "clamp_body":
         for i in range(n):
             g = plan.descs[i]["g"]
