@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "ipp.h"
+#include "ipp_pipe_layout.h"
 
 namespace {
 
@@ -210,7 +211,7 @@ extern "C" int ipp_gather_prepare(ipp_gather_desc* descs, int32_t n) {
 }
 
 // Balanced signed bytes of a 22-bit tap: k = b0 + 256 b1 + 65536 b2, each
-// b in [-128, 127] (the MFMA tile format below).
+// b in [-128, 127] (the MFMA tile format, ipp_pipe_layout.h).
 namespace {
 
 inline void balanced_bytes(int32_t k, int8_t b[3]) {
@@ -224,24 +225,10 @@ inline void balanced_bytes(int32_t k, int8_t b[3]) {
 
 }  // namespace
 
-// ---------------------------------------------------------------------------
-// MFMA tile format (fused pipe, v_mfma_i32_16x16x64_i8).  Outputs are grouped
-// in tiles of 16, tile t covering outputs [16t - phase, 16t - phase + 16) ∩
-// [0, out) (phase lets the V pass align tiles with 16-row background bands);
-// input indices are shifted by `shift` (the V pass's ybox_first).  For tile t:
-//   hdr[t]  = (K0, nK, boff, 0)   K0 = first input column of the tile rounded
-//                                 down to 16, nK = 64-column K steps, boff =
-//                                 uint4 index of the tile's B blocks
-//   bias[16t + c] = 2^21 + 128·Σk of the tile's output c (0 for padding)
-//   block (s, p), s < nK, p < 3: 64 lanes × 16 B; lane l holds bytes
-//           j = 0..15 = balanced byte p of the tap of the tile's output l&15
-//           at input K0 + 64s + 16(l>>4) + j (0 outside its support).  This is
-//           the B operand B[k][col] of the H pass and, unchanged, the A
-//           operand A[row][k] of the V pass (same lane map).
-// so that with pixels stored XOR 0x80 the i8 MFMA accumulators give
-//   2^21 + Σ p·k = bias + Σ_p 2^(8p) acc_p   exactly.
-// Layout per axis (int32 units): hdr[4T], bias[16T], blocks (4 int32 each).
-// ---------------------------------------------------------------------------
+// The MFMA tile format of the fused pipe (hdr, bias, blocks; dense and compact
+// tiles) is stated in ipp_pipe_layout.h; the functions below write it.
+using namespace pipe_layout;
+
 namespace {
 inline int mfma_nk_bound(int32_t in_size, int32_t out_size, int32_t ksize) {
     const double scale = (double)in_size / (double)out_size;
@@ -251,8 +238,8 @@ inline int mfma_nk_bound(int32_t in_size, int32_t out_size, int32_t ksize) {
 
 extern "C" int64_t ipp_plan_mfma_size(int32_t in_size, int32_t out_size, int32_t ksize) {
     if (in_size <= 0 || out_size <= 0 || ksize <= 0) return IPP_E_ARG;
-    const int64_t T = (out_size + 15) / 16 + 1;  // + 1: a phase may add a tile
-    return 20 * T + T * mfma_nk_bound(in_size, out_size, ksize) * 3 * 64 * 4;
+    const int64_t T = tap_ntiles(out_size, 0) + 1;  // + 1: a phase may add a tile
+    return tap_axis_words(T, mfma_nk_bound(in_size, out_size, ksize));
 }
 
 extern "C" int32_t ipp_plan_mfma_nk_bound(int32_t in_size, int32_t out_size, int32_t ksize) {
@@ -264,13 +251,13 @@ extern "C" int ipp_plan_mfma_from_taps(int32_t in_size, int32_t out_size, int32_
                                        int32_t shift, int32_t phase, int32_t* out) {
     if (in_size <= 0 || out_size <= 0 || ksize <= 0 || !std_taps || !out || phase < 0 || phase > 15)
         return IPP_E_ARG;
-    const int T = (out_size + phase + 15) / 16;
+    const int T = tap_ntiles(out_size, phase);
     const int nkb = mfma_nk_bound(in_size, out_size, ksize);
     const int32_t* bounds = std_taps;
     const int32_t* kk = std_taps + 2 * (int64_t)out_size;
     int32_t* hdr = out;
-    int32_t* bias = out + 4 * (int64_t)T;
-    uint8_t* blocks = reinterpret_cast<uint8_t*>(out + 20 * (int64_t)T);
+    int32_t* bias = out + tap_bias_word(T);
+    uint8_t* blocks = reinterpret_cast<uint8_t*>(out + tap_block_word(T));
     int64_t boff = 0;  // in uint4 units
     for (int t = 0; t < T; ++t) {
         const int o0 = 16 * t - phase, o1 = std::min(o0 + 16, (int)out_size), oa = std::max(o0, 0);
@@ -285,7 +272,7 @@ extern "C" int ipp_plan_mfma_from_taps(int32_t in_size, int32_t out_size, int32_
         hdr[4 * t + 2] = (int32_t)boff;
         hdr[4 * t + 3] = 0;
         uint8_t* tb = blocks + 16 * boff;
-        memset(tb, 0, (size_t)nK * 3 * 64 * 16);
+        memset(tb, 0, (size_t)nK * kKStepBytes);
         for (int col = 0; col < 16; ++col) {
             const int o = o0 + col;
             if (o < oa || o >= o1) {
@@ -301,21 +288,21 @@ extern "C" int ipp_plan_mfma_from_taps(int32_t in_size, int32_t out_size, int32_
                 balanced_bytes(k, b);
                 const int rel = xmin + q - K0, s = rel / 64, kin = rel % 64;
                 const int lane = 16 * (kin / 16) + col, j = kin % 16;
-                for (int p = 0; p < 3; ++p) tb[((int64_t)(s * 3 + p) * 64 + lane) * 16 + j] = (uint8_t)b[p];
+                for (int p = 0; p < 3; ++p) tb[(int64_t)tap_dense_block(s, p, lane) * 16 + j] = (uint8_t)b[p];
             }
             bias[16 * t + col] = (int32_t)((1 << 21) + 128 * sum);
         }
-        boff += (int64_t)nK * 3 * 64;
+        boff += (int64_t)nK * kKStepBlocks;
     }
     return IPP_OK;
 }
 
-// One tile of an axis in the layout of the device tap planner (tile t's
-// blocks at uint4 offset t·nkb·192), from Pillow's taps computed here.
+// One tile of an axis in the layout of the device tap planner (every tile
+// with nkb K-step slots: tap_tile_block), from Pillow's taps computed here.
 extern "C" int ipp_plan_mfma_tile(const ipp_tap_axis* a, int32_t t, int32_t hdr[4], int32_t bias[16],
                                   uint8_t* blocks, int64_t blocks_cap) {
     if (!a || !hdr || !bias || !blocks || a->in_size <= 0 || a->out_size <= 0 || a->phase < 0 || a->phase > 15 ||
-        t < 0 || t >= (a->out_size + a->phase + 15) / 16)
+        t < 0 || t >= tap_ntiles(a->out_size, a->phase))
         return IPP_E_ARG;
     const int in = a->in_size, out = a->out_size, shift = a->shift;
     const int o0 = 16 * t - a->phase, o1 = std::min(o0 + 16, out), oa = std::max(o0, 0);
@@ -344,8 +331,8 @@ extern "C" int ipp_plan_mfma_tile(const ipp_tap_axis* a, int32_t t, int32_t hdr[
     int end = K0;
     for (int o = oa; o < o1; ++o) end = std::max(end, xs[o - o0] + cn[o - o0]);
     const int nK = (end - K0 + 63) / 64;
-    if (nK > a->nkb || (int64_t)nK * 3072 > blocks_cap) return IPP_E_RANGE;
-    // compact layout (ipp.h): each output's nonzero 16-column groups
+    if (nK > a->nkb || (int64_t)nK * kKStepBytes > blocks_cap) return IPP_E_RANGE;
+    // compact layout: each output's nonzero 16-column groups
     int g0[16], len[16], base[16], nb = 0;
     for (int col = 0; col < 16; ++col) {
         const int o = o0 + col;
@@ -358,9 +345,9 @@ extern "C" int ipp_plan_mfma_tile(const ipp_tap_axis* a, int32_t t, int32_t hdr[
     const bool compact = a->compact && !a->identity && nK >= 2 && nb <= 64;
     hdr[0] = K0;
     hdr[1] = nK;
-    hdr[2] = t * a->nkb * 192;
+    hdr[2] = (int32_t)tap_tile_block(t, a->nkb);
     hdr[3] = compact ? 1 : 0;
-    memset(blocks, 0, (size_t)nK * 3072);
+    memset(blocks, 0, (size_t)nK * kKStepBytes);
     if (compact)
         for (int col = 0; col < 16; ++col) {
             const int32_t m = g0[col] | len[col] << 8 | base[col] << 16;
@@ -381,11 +368,11 @@ extern "C" int ipp_plan_mfma_tile(const ipp_tap_axis* a, int32_t t, int32_t hdr[
             const int rel = xs[col] + q - K0;
             if (compact) {
                 const int i = base[col] + (rel >> 4) - g0[col], j = rel & 15;
-                for (int p = 0; p < 3; ++p) blocks[64 + ((int64_t)p * 64 + i) * 16 + j] = (uint8_t)b[p];
+                for (int p = 0; p < 3; ++p) blocks[(int64_t)tap_compact_block(p, i) * 16 + j] = (uint8_t)b[p];
             } else {
                 const int s = rel / 64, kin = rel % 64;
                 const int lane = 16 * (kin / 16) + col, j = kin % 16;
-                for (int p = 0; p < 3; ++p) blocks[((int64_t)(s * 3 + p) * 64 + lane) * 16 + j] = (uint8_t)b[p];
+                for (int p = 0; p < 3; ++p) blocks[(int64_t)tap_dense_block(s, p, lane) * 16 + j] = (uint8_t)b[p];
             }
         }
         bias[col] = (int32_t)((1 << 21) + 128 * sum);

@@ -23,12 +23,11 @@
 #include <climits>
 
 #include "ipp_device.h"
+#include "ipp_pipe_layout.h"
 
 namespace {
 
-typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int LBR = 16;  // rows of a V tap tile = composite rows of a band (ipp_pipe.hip VBR)
+using namespace pipe_layout;
 
 __global__ void k_label_bbox_init(int32_t* bbox, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -64,10 +63,9 @@ __device__ __forceinline__ void bbox_commit(int32_t* __restrict__ row, int xmin,
 // Block = one V tap tile (one 16-row composite band the overlay touches) of
 // one item; its four waves stride over the 16-column tiles.
 //
-// The band, tile, header, bias, tap block and T group addressing below
-// repeats ipp_pipe.hip's vblend_block, which is the source of truth: a change
-// of the tap tile or T layout there must be repeated here (tests/
-// test_gpu_labels.py compares the boxes with the resized overlay's alpha).
+// The band, tap tile and T group addressing is ipp_pipe_layout.h's, as in
+// ipp_pipe.hip's vblend_block (tests/test_gpu_labels.py compares the boxes
+// with the resized overlay's alpha).
 //   A = the tile's taps, one byte plane per MFMA (lane l: row l&15, T rows
 //       16(l>>4)..+15 of the K step);
 //   B = 64 T rows × 16 overlay columns of alpha: dword 3 (byte offset 12) of
@@ -87,42 +85,39 @@ __device__ __forceinline__ void overlay_alpha_band(const uint8_t* __restrict__ t
                                                    const ipp_pipe_desc* __restrict__ descs, int im, int ty,
                                                    Sink sink) {
     const ipp_paste_desc p = descs[im].p;
-    // the overlay's bands [vb0, vb1) (paste_bands)
-    const int vb0 = (p.y >> 4) << 4;
-    const int vb1 = max(min(p.bg_h, ((p.y + p.ov_h + 15) >> 4) << 4), vb0);
-    const int y0 = vb0 + ty * LBR;
+    int vb0, vb1;
+    paste_bands(p, vb0, vb1);
+    const int y0 = vb0 + ty * kBandRows;
     if (y0 >= vb1 || y0 >= p.bg_h) return;  // block-uniform
-    const int nrows = min(LBR, p.bg_h - y0);
+    const int nrows = min(kBandRows, p.bg_h - y0);
     const int oy_lo = max(0, y0 - p.y), oy_hi = min(p.ov_h, y0 + nrows - p.y);
     if (oy_lo >= oy_hi) return;  // block-uniform
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 
     const ipp_resample_desc v = descs[im].v;
-    const int phase = p.y & 15;
-    const int ntiles = (v.out_len + phase + 15) >> 4;
-    const int t = (y0 - p.y + phase) >> 4;  // the band's tap tile
-    const int4* thdr = reinterpret_cast<const int4*>(coefs + v.coef_off);
-    const int32_t* tbias = coefs + v.coef_off + 4 * (int64_t)ntiles;
-    const uint4* tblk = reinterpret_cast<const uint4*>(coefs + v.coef_off + 20 * (int64_t)ntiles);
-    int4 th = thdr[t];
+    const int phase = tap_phase(p.y);
+    const int t = band_tap_tile(y0, p.y, phase);
+    const TapTiles tt = tap_tiles(coefs, v.coef_off, tap_ntiles(v.out_len, phase));
+    int4 th = tt.hdr[t];
     th.x = __builtin_amdgcn_readfirstlane(th.x);  // first T row of the tile's window
     th.y = __builtin_amdgcn_readfirstlane(th.y);  // K steps
     th.z = __builtin_amdgcn_readfirstlane(th.z);  // first tap block
     const int ctiles = (p.ov_w + 15) >> 4;
-    const int64_t gstride = v.src_pitch >> 4;  // 16-B groups per T group row
+    const int64_t gstride = t_pitch_vecs(v.src_pitch);
     const int x_l = lane & 15;
     int32_t rb[4];  // the row biases
 #pragma unroll
-    for (int r = 0; r < 4; ++r) rb[r] = tbias[16 * t + 4 * (lane >> 4) + r];
-    const int gbase = (th.x + 16 * (lane >> 4)) >> 2;
-    // byte 12 of T group (row group gbase, column 0): the alpha dword
-    const uint8_t* abase = tmp + v.src_off + gbase * gstride * 16 + 12;
+    for (int r = 0; r < 4; ++r) rb[r] = tt.bias[kBiasWords * t + 4 * (lane >> 4) + r];
+    const int gbase = t_row_group(th.x + 16 * (lane >> 4));
+    // The alpha dword of T group (row group gbase, column 0); the loop below
+    // walks t_group's address from it by whole groups and group rows.
+    const uint8_t* abase = tmp + v.src_off + gbase * gstride * kTGroupBytes + kTAlphaByte;
 
     for (int ct = wave; ct < ctiles; ct += 4) {
         const int x = 16 * ct + x_l;
         const int xs = min(x, p.ov_w - 1);
-        const uint8_t* aq = abase + (int64_t)xs * 16;
+        const uint8_t* aq = abase + (int64_t)xs * kTGroupBytes;
         i32x4 acc[3];
         acc[0] = i32x4{rb[0], rb[1], rb[2], rb[3]};
         acc[1] = i32x4{0, 0, 0, 0};
@@ -132,10 +127,10 @@ __device__ __forceinline__ void overlay_alpha_band(const uint8_t* __restrict__ t
             i32x4 bq;
 #pragma unroll
             for (int j = 0; j < 4; ++j)
-                bq[j] = *reinterpret_cast<const int32_t*>(aq + (16 * ks + j) * gstride * 16);
+                bq[j] = *reinterpret_cast<const int32_t*>(aq + (kKStepGroups * ks + j) * gstride * kTGroupBytes);
 #pragma unroll
             for (int q = 0; q < 3; ++q) {
-                const i32x4 a = __builtin_bit_cast(i32x4, tblk[th.z + (ks * 3 + q) * 64 + lane]);
+                const i32x4 a = __builtin_bit_cast(i32x4, tt.blk[th.z + tap_dense_block(ks, q, lane)]);
                 acc[q] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, bq, acc[q], 0, 0, 0);
             }
         }
@@ -329,8 +324,7 @@ extern "C" int ipp_pipe_overlay_bbox(const uint8_t* tmp, const int32_t* coefs, c
     if (alpha_min < 1 || alpha_min > 255 || tap_format != IPP_TAPS_MFMA) return IPP_E_ARG;
     if (!tmp || !coefs || !descs || !bbox || n_images < 0 || max_ov_w <= 0 || max_ov_h <= 0) return IPP_E_ARG;
     if (n_images == 0) return IPP_OK;
-    // an overlay of height H at any y spans at most ceil((15 + H) / 16) bands
-    const int tyb = (max_ov_h + 15 + LBR - 1) / LBR;
+    const int tyb = paste_max_bands(max_ov_h);
     const int64_t nb = (int64_t)tyb * n_images;
     if (nb >= INT32_MAX) return IPP_E_ARG;
     hipStream_t s = (hipStream_t)stream;
@@ -379,8 +373,7 @@ extern "C" int ipp_pipe_scene_boxes(const uint8_t* tmp, const int32_t* coefs, co
         return IPP_E_ARG;
     if ((reinterpret_cast<uintptr_t>(scratch) & 15u) != 0) return IPP_E_ARG;  // the planes are read by dwords
     if (n_images == 0) return IPP_OK;
-    // an overlay of height H at any y spans at most ceil((15 + H) / 16) bands
-    const int tyb = (max_ov_h + 15 + LBR - 1) / LBR, strips = (max_ov_h + SVR - 1) / SVR;
+    const int tyb = paste_max_bands(max_ov_h), strips = (max_ov_h + SVR - 1) / SVR;
     const int64_t slots = (int64_t)n_scenes * per_scene;
     if ((int64_t)tyb * n_images >= INT32_MAX || slots >= INT32_MAX) return IPP_E_ARG;
     hipStream_t s = (hipStream_t)stream;

@@ -31,9 +31,12 @@
 #include <type_traits>
 
 #include "ipp_hsv.h"
+#include "ipp_pipe_layout.h"
 #include "ipp_sampler.h"
 
 namespace {
+
+using namespace pipe_layout;
 
 constexpr int HR = 16;            // H-pass rows per band (4 per thread)
 constexpr int RING = 512;         // window ring: M columns x live at x & (RING - 1)
@@ -56,9 +59,6 @@ __device__ __forceinline__ void transpose4(uint32_t p0, uint32_t p1, uint32_t p2
     ch[2] = perm(hi23, hi01, 0x05040100u);
     ch[3] = perm(hi23, hi01, 0x07060302u);
 }
-
-typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_of(const void* p) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, 0x7FFFFFFF, 0x00020000);
@@ -262,6 +262,11 @@ __device__ __forceinline__ Hp2Chunk hp2_chunk(const int4* hdr, int s0, int ntile
 // The body sweeps the output tiles [s_lo, s_hi) (wave-uniform, s_lo < s_hi):
 // hpass_block trims the band's leading and trailing tiles whose whole input
 // window is fill and writes their constant T groups itself (fill_trim).
+//
+// (hpass2_body and the fill trim take the layout's numbers from
+// ipp_pipe_layout.h as named constants inside expressions of the shape they
+// always had: in the register-tight forms without zones, the header's helper
+// functions at these sites changed the instruction stream.)
 template <int NR, bool ZONES, int CN, bool CLAMP>
 __device__ __forceinline__ void hpass2_body(const HsvTables<NR>& T, WinRing& win, int wave, const Hp2Block& B,
                                             uint8_t* __restrict__ tmp, const int32_t* __restrict__ coefs,
@@ -269,10 +274,10 @@ __device__ __forceinline__ void hpass2_body(const HsvTables<NR>& T, WinRing& win
                                             const int32_t* zcw, uint32_t zrow, int s_lo, int s_hi) {
     const int lane = threadIdx.x & 63;
     const int r = 2 * (lane >> 3) + ((lane >> 1) & 1);  // the lane's window row
-    const int ntiles = (h.out_len + 15) >> 4;
+    const int ntiles = (h.out_len + kTileOut - 1) >> kTileOutLog2;  // tap_ntiles, phase 0
     const int4* hdr = reinterpret_cast<const int4*>(coefs + h.coef_off);
-    const int32_t* tbias = coefs + h.coef_off + 4 * (int64_t)ntiles;
-    const uint4* tblk = reinterpret_cast<const uint4*>(coefs + h.coef_off + 20 * (int64_t)ntiles);
+    const int32_t* tbias = coefs + h.coef_off + kHdrWords * (int64_t)ntiles;
+    const uint4* tblk = reinterpret_cast<const uint4*>(coefs + h.coef_off + (kHdrWords + kBiasWords) * (int64_t)ntiles);
     const uint32_t sx = (uint32_t)HP_STEPC * (uint32_t)B.b0, sy = (uint32_t)HP_STEPC * (uint32_t)B.b3;  // per-step advance
 
     int filled = hdr[s_lo].x;  // ring holds M columns [.., filled)
@@ -330,7 +335,8 @@ __device__ __forceinline__ void hpass2_body(const HsvTables<NR>& T, WinRing& win
             // per plane — one load per plane for every K step.  Dense tiles:
             // the first K step's blocks (meta then reads tap bytes, unused).
 #pragma unroll
-            for (int p = 0; p < 3; ++p) bn[p] = tblk[th.z + (th.w ? 4 : 0) + lane + p * 64];
+            for (int p = 0; p < kTapPlanes; ++p)
+                bn[p] = tblk[th.z + (th.w ? kCompactMeta : 0) + lane + p * kKStepCols];
             if (!has_tile) th.y = 0;
         }
         const int te = min(t, s_hi - 1);
@@ -400,7 +406,7 @@ __device__ __forceinline__ void hpass2_body(const HsvTables<NR>& T, WinRing& win
             iss(st + 2, RC);
             if (st + 3 >= nsteps) {
                 meta = reinterpret_cast<const int32_t*>(tblk + th.z)[lane & 15];
-                bias = tbias[min(16 * te + (lane & 15), h.out_len - 1)];
+                bias = tbias[min(kBiasWords * te + (lane & 15), h.out_len - 1)];
                 mb = true;
             }
             process(RA, st, 4 * (RB.live + RC.live));
@@ -416,7 +422,7 @@ __device__ __forceinline__ void hpass2_body(const HsvTables<NR>& T, WinRing& win
         // would drain the gathers as well.
         if (!mb) {  // (a wave with no phase-1 steps)
             meta = reinterpret_cast<const int32_t*>(tblk + th.z)[lane & 15];
-            bias = tbias[min(16 * te + (lane & 15), h.out_len - 1)];
+            bias = tbias[min(kBiasWords * te + (lane & 15), h.out_len - 1)];
         }
         const int s1 = ck.s1;
         const bool more = s1 < s_hi;
@@ -489,7 +495,7 @@ __device__ __forceinline__ void hpass2_body(const HsvTables<NR>& T, WinRing& win
                 for (int ks = 0; ks < th.y; ++ks) {
                     if (ks > 0) {
 #pragma unroll
-                        for (int p = 0; p < 3; ++p) bn[p] = tblk[th.z + lane + (ks * 3 + p) * 64];
+                        for (int p = 0; p < kTapPlanes; ++p) bn[p] = tblk[th.z + lane + (ks * kTapPlanes + p) * kKStepCols];
                     }
                     const int pos = (th.x + 64 * ks + akoff) & (RING - 1);
 #pragma unroll
@@ -518,13 +524,13 @@ __device__ __forceinline__ void hpass2_body(const HsvTables<NR>& T, WinRing& win
                 // 64-bit row address was live through phase 1 and spilled)
                 int ln = lane;
                 asm volatile("" : "+v"(ln));
-                const int grp = (row0 >> 2) + (ln >> 4);
-                uint4* dst = reinterpret_cast<uint4*>(tmp + h.dst_off + (int64_t)grp * h.dst_pitch) + xo;
+                const int grp = (row0 >> kTGroupRowsLog2) + (ln >> 4);
+                TGroup* dst = reinterpret_cast<TGroup*>(tmp + h.dst_off + (int64_t)grp * h.dst_pitch) + xo;
                 const uint32_t w[4] = {outc[0], outc[1], outc[2], outc[3]};
                 // Nontemporal: T is read back only after the whole launch
                 // (-0.8 % against plain stores; nontemporal T loads in the V
                 // pass measured +15 %).
-                store16<2>(reinterpret_cast<uint8_t*>(dst), 16, true, w);
+                store16<2>(reinterpret_cast<uint8_t*>(dst), kTGroupBytes, true, w);
             }
         }
         // The next chunk's first sets are waited for here, at the end of
@@ -537,30 +543,17 @@ __device__ __forceinline__ void hpass2_body(const HsvTables<NR>& T, WinRing& win
     }
 }
 
-// Composite rows outside the overlay's 16-row bands [vb0, vb1) are plain
-// copies of the background (Paste.c leaves them untouched).  The H-pass
-// launch's copy blocks write them (and, column split, the band rows' groups
-// outside the overlay), so ipp_pipe_vblend_bands only visits the overlay.
-__device__ __forceinline__ void paste_bands(const ipp_paste_desc& p, int& vb0, int& vb1) {
-    vb0 = (p.y >> 4) << 4;
-    vb1 = min(p.bg_h, ((p.y + p.ov_h + 15) >> 4) << 4);
-    vb1 = max(vb1, vb0);
-}
-
 // Column split of the band rows [vb0, vb1): on dense, 16-B aligned images
 // whose width is a multiple of 16, the H pass's copy blocks also write the
 // band rows' 16-pixel groups outside [gx0, gx1) (the groups the overlay
 // touches) and the V pass visits only [gx0, gx1).  Both kernels decide it
-// with this one predicate (ipp_plan.cpp counts the bytes the same way).
+// with this one predicate: ipp_pipe_layout.h's (ipp_plan.cpp counts the bytes
+// by it) with the two images' alignment.
 __device__ __forceinline__ bool band_cols_split(const ipp_paste_desc& p, const uint8_t* bg, const uint8_t* dst,
                                                 int& gx0, int& gx1) {
-    const int rb = 3 * p.bg_w;
-    gx0 = max(p.x, 0) >> 4;
-    gx1 = min((p.x + p.ov_w + 15) >> 4, p.bg_w >> 4);
-    const int64_t lr = 3 * (p.bg_w >> 4);  // ≥ the split's vectors per band row
-    return (p.bg_w & 15) == 0 && p.bg_pitch == rb && p.dst_pitch == rb && gx0 < gx1 &&
-           (int64_t)p.bg_h * lr * lr < (1ll << 32) &&  // (the H copy's umulhi division stays exact)
-           ((reinterpret_cast<uintptr_t>(bg + p.bg_off) | reinterpret_cast<uintptr_t>(dst + p.dst_off)) & 15u) == 0;
+    return pipe_layout::band_cols_split(p, gx0, gx1, [&] {
+        return ((reinterpret_cast<uintptr_t>(bg + p.bg_off) | reinterpret_cast<uintptr_t>(dst + p.dst_off)) & 15u) == 0;
+    });
 }
 
 // 16-B vectors per thread in flight in the per-item background copy.  A copy
@@ -872,7 +865,7 @@ __device__ __forceinline__ void hpass_block(Hpass2Lds<NR>& L, const uint8_t* __r
     // [xlo, xhi], and the others' constant T groups are stored here, before
     // any gather is in flight.  One header per lane and a ballot give both
     // bounds, wave-uniform; items of more than 64 tiles are not trimmed.
-    const int ntiles = (h.out_len + 15) >> 4;
+    const int ntiles = (h.out_len + kTileOut - 1) >> kTileOutLog2;  // tap_ntiles, phase 0
     int s_lo = 0, s_hi = ntiles;
     if constexpr (!ZONES) {
         // raw 0 has h = s = v = 0 (hsv_tab_excl): excluded ⟺ some range holds 0 on all three channels
@@ -889,17 +882,17 @@ __device__ __forceinline__ void hpass_block(Hpass2Lds<NR>& L, const uint8_t* __r
             const uint64_t km = __builtin_amdgcn_ballot_w64(keep);
             s_lo = km ? __builtin_ctzll(km) : 0;
             s_hi = km ? 64 - __builtin_clzll(km) : 0;
-            // The trimmed tiles' T groups (the address arithmetic of the body's
-            // epilogue), one tile per wave and turn.
+            // The trimmed tiles' T groups (addressed as in the body's epilogue:
+            // group grp of the item's T, column xo), one tile per wave and turn.
             const int ntrim = s_lo + ntiles - s_hi;
             for (int i = wave; i < ntrim; i += HP_NW) {
                 const int t = i < s_lo ? i : i - s_lo + s_hi;
                 const int xo = 16 * t + (lane & 15);
                 if (xo < h.out_len) {
-                    const int grp = (row0 >> 2) + (lane >> 4);
-                    uint4* dst = reinterpret_cast<uint4*>(tmp + h.dst_off + (int64_t)grp * h.dst_pitch) + xo;
+                    const int grp = (row0 >> kTGroupRowsLog2) + (lane >> 4);
+                    TGroup* dst = reinterpret_cast<TGroup*>(tmp + h.dst_off + (int64_t)grp * h.dst_pitch) + xo;
                     const uint32_t w[4] = {0x80808080u, 0x80808080u, 0x80808080u, 0x80808080u};
-                    store16<2>(reinterpret_cast<uint8_t*>(dst), 16, true, w);
+                    store16<2>(reinterpret_cast<uint8_t*>(dst), kTGroupBytes, true, w);
                 }
             }
             if (s_lo >= s_hi) return;  // nothing to sweep (block-uniform: no barrier was met)
@@ -954,7 +947,6 @@ k_pipe_hpass2(const uint8_t* __restrict__ src, uint8_t* __restrict__ tmp, const 
 // bias added (v_lshl_add), then plane 0's: ((S2 << 8) + S1) << 8 + bias + S0
 // equals planes3(bias + S0, S1, S2) in int32 wrap-around arithmetic.  It
 // frees 32 VGPRs of the 48 the accumulators took.
-constexpr int VBR = 16;
 // V pass: column tiles with nK ≤ IPP_VB_DB double-buffer their T groups (the
 // wave's next tile's loads fly during this tile's MFMAs).
 #ifndef IPP_VB_DB
@@ -981,8 +973,8 @@ __host__ __device__ constexpr int orow_stride(int ov_w_max) { return (ov_w_max +
 // The widest overlay the V launch takes: its rows must fit 64 KB of LDS
 // (IPP_PIPE_MAX_OV_W in ipp.h; the magic-divisor table is dropped for
 // overlays too wide to hold it beside the rows).
-static_assert((size_t)VBR * orow_stride(IPP_PIPE_MAX_OV_W) * 4 <= 64 * 1024, "V-pass rows in LDS");
-static_assert((size_t)VBR * orow_stride(IPP_PIPE_MAX_OV_W + 1) * 4 > 64 * 1024, "IPP_PIPE_MAX_OV_W is the limit");
+static_assert((size_t)kBandRows * orow_stride(IPP_PIPE_MAX_OV_W) * 4 <= 64 * 1024, "V-pass rows in LDS");
+static_assert((size_t)kBandRows * orow_stride(IPP_PIPE_MAX_OV_W + 1) * 4 > 64 * 1024, "IPP_PIPE_MAX_OV_W is the limit");
 
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 
@@ -1113,7 +1105,7 @@ __device__ __forceinline__ void vblend_block(uint32_t* __restrict__ orow, const 
                                              const int32_t* __restrict__ coefs,
                                              const ipp_pipe_desc* __restrict__ descs, int im, int ty, int ov_w_max) {
     const ipp_paste_desc p = vb_paste_desc(descs[im].p, INPLACE);
-    int y0 = ty * VBR;
+    int y0 = ty * kBandRows;
     {
         int vb0, vb1;
         paste_bands(p, vb0, vb1);
@@ -1121,7 +1113,7 @@ __device__ __forceinline__ void vblend_block(uint32_t* __restrict__ orow, const 
         if (y0 >= vb1) return;
     }
     if (y0 >= p.bg_h) return;
-    const int nrows = min(VBR, p.bg_h - y0);
+    const int nrows = min(kBandRows, p.bg_h - y0);
     const int oy_lo = max(0, y0 - p.y), oy_hi = min(p.ov_h, y0 + nrows - p.y);
     const bool any = oy_lo < oy_hi;  // block-uniform
     const int lane = threadIdx.x & 63;
@@ -1149,38 +1141,35 @@ __device__ __forceinline__ void vblend_block(uint32_t* __restrict__ orow, const 
     };
     uint4 gcur[3];
     if (any) {
-        uint32_t* umag = orow + VBR * os;  // MAGIC: the unpremultiply divisors
+        uint32_t* umag = orow + kBandRows * os;  // MAGIC: the unpremultiply divisors
         if (MAGIC) {
             umag[threadIdx.x] = unpremul_magic(threadIdx.x);
             __syncthreads();
         }
         // zero the ≤ 15 columns before the overlay and the 16 after it
-        for (int e = threadIdx.x; e < VBR * 32; e += 256) {
+        for (int e = threadIdx.x; e < kBandRows * 32; e += 256) {
             const int row = e >> 5, c = e & 31;
             if (c < xo) orow[row * os + c] = 0u;
             else if (c >= 16) orow[row * os + xo + p.ov_w + c - 16] = 0u;
         }
         const ipp_resample_desc v = descs[im].v;
-        const int phase = p.y & 15;
-        const int ntiles = (v.out_len + phase + 15) >> 4;
-        const int t = (y0 - p.y + phase) >> 4;  // the band's tap tile
-        const int4* thdr = reinterpret_cast<const int4*>(coefs + v.coef_off);
-        const int32_t* tbias = coefs + v.coef_off + 4 * (int64_t)ntiles;
-        const uint4* tblk = reinterpret_cast<const uint4*>(coefs + v.coef_off + 20 * (int64_t)ntiles);
-        const int4 th = thdr[t];
+        const int phase = tap_phase(p.y);
+        const int t = band_tap_tile(y0, p.y, phase);
+        const TapTiles tt = tap_tiles(coefs, v.coef_off, tap_ntiles(v.out_len, phase));
+        const int4 th = tt.hdr[t];
         const int ctiles = (p.ov_w + 15) >> 4;
-        const int gstride = v.src_pitch >> 4;  // uint4 per T group row
+        const int gstride = t_pitch_vecs(v.src_pitch);
         const int x_l = lane & 15;
         // the row biases (added at the last Horner step)
         int32_t rb[4];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) rb[r] = tbias[16 * t + 4 * (lane >> 4) + r];
+        for (int r = 0; r < 4; ++r) rb[r] = tt.bias[kBiasWords * t + 4 * (lane >> 4) + r];
         const u32x4_t* tbase = reinterpret_cast<const u32x4_t*>(tmp + v.src_off);
-        const int gbase = (th.x + 16 * (lane >> 4)) >> 2;
+        const int gbase = t_row_group(th.x + 16 * (lane >> 4));
         // T groups of K step ks of column tile ct: rows th.x + 64 ks + 16 (lane >> 4) .. + 15
         auto tload = [&](int ct, int ks, u32x4_t (&g)[4]) {
             const int xs = min(16 * ct + x_l, p.ov_w - 1);
-            const u32x4_t* tq = tbase + xs + (int64_t)(gbase + 16 * ks) * gstride;
+            const u32x4_t* tq = t_group(tbase, gstride, gbase + kKStepGroups * ks, xs);
 #pragma unroll
             for (int j = 0; j < 4; ++j) g[j] = tq[j * gstride];
         };
@@ -1212,7 +1201,7 @@ __device__ __forceinline__ void vblend_block(uint32_t* __restrict__ orow, const 
                 for (int ks = 0; ks < NK; ++ks)
 #pragma unroll
                     for (int q = 0; q < 3; ++q)
-                        ta[ks][q] = __builtin_bit_cast(i32x4, tblk[th.z + (ks * 3 + q) * 64 + lane]);
+                        ta[ks][q] = __builtin_bit_cast(i32x4, tt.blk[th.z + tap_dense_block(ks, q, lane)]);
                 // the loaded T groups of a tile, turned channel-major
                 auto transpose = [&](const u32x4_t (&g)[NK][4], i32x4 (&bq)[NK][4]) {
 #pragma unroll
@@ -1272,7 +1261,7 @@ __device__ __forceinline__ void vblend_block(uint32_t* __restrict__ orow, const 
                     for (int ks = 0; ks < th.y; ++ks) {
                         i32x4 a[3];
 #pragma unroll
-                        for (int q = 0; q < 3; ++q) a[q] = __builtin_bit_cast(i32x4, tblk[th.z + (ks * 3 + q) * 64 + lane]);
+                        for (int q = 0; q < 3; ++q) a[q] = __builtin_bit_cast(i32x4, tt.blk[th.z + tap_dense_block(ks, q, lane)]);
                         u32x4_t g[4];
                         tload(ct, ks, g);
 #pragma unroll
@@ -1391,7 +1380,7 @@ __global__ void __launch_bounds__(256) IPP_VB_ATTR
 k_pipe_vblend_mfma(const uint8_t* __restrict__ tmp, const uint8_t* __restrict__ bg, uint8_t* __restrict__ dst,
                    const int32_t* __restrict__ coefs, const ipp_pipe_desc* __restrict__ descs, FastDiv tiles_y,
                    int ov_w_max) {
-    extern __shared__ __attribute__((aligned(16))) uint32_t orow[];  // [VBR][orow_stride(ov_w_max)] (+ 256 divisors)
+    extern __shared__ __attribute__((aligned(16))) uint32_t orow[];  // [kBandRows][orow_stride(ov_w_max)] (+ 256 divisors)
     const uint32_t b = xcd_remap(blockIdx.x, gridDim.x);
     const int im = (int)fdiv(b, tiles_y);
     const int ty = (int)(b - (uint32_t)im * tiles_y.d);
@@ -1522,11 +1511,10 @@ static int vblend_entry(const uint8_t* tmp, const uint8_t* bg, uint8_t* dst, con
     if (tap_format != IPP_TAPS_MFMA || max_ov_w <= 0 || max_ov_w > bg_w || max_ov_h <= 0 || max_ov_h > bg_h ||
         max_ov_w > IPP_PIPE_MAX_OV_W)
         return IPP_E_ARG;
-    const size_t rows = (size_t)VBR * orow_stride(max_ov_w) * sizeof(uint32_t);
+    const size_t rows = (size_t)kBandRows * orow_stride(max_ov_w) * sizeof(uint32_t);
     const size_t magic = 256 * sizeof(uint32_t);  // the unpremultiply divisors, when they fit beside the rows
     const bool use_magic = rows + magic <= 64 * 1024;
-    // an overlay of height H at any y spans at most ceil((15 + H) / 16) bands
-    const int tyb = std::min((max_ov_h + 15 + VBR - 1) / VBR, (bg_h + VBR - 1) / VBR);
+    const int tyb = std::min(paste_max_bands(max_ov_h), (bg_h + kBandRows - 1) / kBandRows);
     const int64_t nb = (int64_t)tyb * n_images;
     if (nb >= INT32_MAX) return IPP_E_ARG;
     hipStream_t st = (hipStream_t)stream;

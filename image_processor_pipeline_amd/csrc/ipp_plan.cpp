@@ -29,6 +29,9 @@
 #include <vector>
 
 #include "ipp.h"
+#include "ipp_pipe_layout.h"
+
+using namespace pipe_layout;
 
 namespace {
 
@@ -562,10 +565,10 @@ extern "C" int ipp_plan_pipe_batch(const ipp_pipe_plan_cfg* cfg, ipp_pipe_item* 
         const int32_t nkb_h = ipp_plan_mfma_nk_bound(rw, nw_, ks_h);
         const int32_t nkb_v = ipp_plan_mfma_nk_bound(rh, nh_, ks_v);
         if (!id_h && 64 * (int64_t)nkb_h > ring) return fail(start + i, E_RING);
-        ah = {rw, nw_, id_h ? 1 : 0, 0, 0, nkb_h, 1, (nw_ + 15) / 16, coef_words};  // compact H tiles
+        ah = {rw, nw_, id_h ? 1 : 0, 0, 0, nkb_h, 1, tap_ntiles(nw_, 0), coef_words};  // compact H tiles
         coef_words += (ipp_plan_mfma_size(rw, nw_, ks_h) + 3) / 4 * 4;
-        const int32_t phase = it.y % 16;
-        av = {rh, nh_, id_v ? 1 : 0, (!id_h && !id_v) ? y0 : 0, phase, nkb_v, 0, (nh_ + phase + 15) / 16, coef_words};
+        const int32_t phase = tap_phase(it.y);
+        av = {rh, nh_, id_v ? 1 : 0, (!id_h && !id_v) ? y0 : 0, phase, nkb_v, 0, tap_ntiles(nh_, phase), coef_words};
         coef_words += (ipp_plan_mfma_size(rh, nh_, ks_v) + 3) / 4 * 4;
         max_tiles = std::max(max_tiles, std::max(ah.n_tiles, av.n_tiles));
 
@@ -593,10 +596,8 @@ extern "C" int ipp_plan_pipe_batch(const ipp_pipe_plan_cfg* cfg, ipp_pipe_item* 
         g.off_y = it.cut_y;
         g.flip = c.sym_flip[it.sym];
         ipp_gather_prepare(&g, 1);
-        // T rows are grouped by 4; V tiles read up to 64·nK rows past their
-        // 16-aligned start
-        const int64_t groups = (((int64_t)(rows + 15) / 16) * 16 + 64 * nkb_v + 16) / 4;
-        const int64_t pitch = 16 * (int64_t)nw_;
+        const int64_t groups = t_groups(rows, nkb_v);
+        const int64_t pitch = kTGroupBytes * (int64_t)nw_;
         ipp_resample_desc& h = D.h;
         h.dst_off = tmp_off;
         h.dst_pitch = (int32_t)pitch;
@@ -635,15 +636,12 @@ extern "C" int ipp_plan_pipe_batch(const ipp_pipe_plan_cfg* cfg, ipp_pipe_item* 
         const int64_t t_bytes = pitch * ((rows + 3) / 4);
         algo_h += 3 * (int64_t)hc * wc + t_bytes;
         algo_v += t_bytes + 6 * (int64_t)bh * bw;
-        const int32_t vb0 = (it.y / 16) * 16;
-        const int32_t vb1 = std::max(vb0, std::min(bh, (it.y + nh_ + 15) / 16 * 16));
+        int vb0, vb1, gx0, gx1;
+        paste_bands(p, vb0, vb1);
         copy_rows += bh - (vb1 - vb0);
         // the band rows' 16-pixel groups outside the overlay's, copied by the
-        // H pass too when ipp_pipe.hip's band_cols_split holds (dense rows;
-        // 16-B aligned images assumed)
-        const int32_t gx0 = std::max(it.x, 0) >> 4, gx1 = std::min((it.x + nw_ + 15) >> 4, bw >> 4);
-        const int64_t lr = 3 * (int64_t)(bw >> 4);
-        if ((bw & 15) == 0 && ((int64_t)3 * bh * bw) % 16 == 0 && gx0 < gx1 && (int64_t)bh * lr * lr < (1ll << 32))
+        // H pass too under the column split (16-B aligned images assumed)
+        if (band_cols_split(p, gx0, gx1, [] { return true; }))
             copy_band_bytes += 2 * 48 * (int64_t)(vb1 - vb0) * ((bw >> 4) - (gx1 - gx0));
     }
     // processing order: items grouped by background (stable), see fused.py

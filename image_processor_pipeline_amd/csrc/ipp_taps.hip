@@ -1,8 +1,8 @@
 // ipp_taps.hip — device tap planner of the fused pipe (gfx950).
 //
-// Builds, directly in HBM, the MFMA tile format the pipe kernels read (see
-// ipp_host.cpp ipp_plan_mfma_from_taps for the format): per axis hdr[4T],
-// bias[16T] and the i8 B/A blocks, tile t's blocks at uint4 offset t·nkb·192.
+// Builds, directly in HBM, the MFMA tile format the pipe kernels read
+// (ipp_pipe_layout.h): per axis hdr, bias and the i8 B/A blocks, every tile
+// with nkb K-step slots (tap_tile_block).
 // The taps are Pillow's LANCZOS taps (Resample.c precompute_coeffs +
 // normalize_coeffs_8bpc, reference call site overlays.py:129), computed in
 // fp64 as the host code computes them except for the filter's sines (a short
@@ -31,15 +31,18 @@
 #include <vector>
 
 #include "ipp.h"
+#include "ipp_pipe_layout.h"
 
 namespace {
+
+using namespace pipe_layout;
 
 constexpr int TAP_WAVES = 4;
 constexpr int TAP_CACHE = 64;       // cached weights per output (more: recomputed)
 constexpr int TAP_NI = TAP_CACHE / 4;  // weights per lane in registers (4 lanes per output)
 constexpr int TAP_STAGE_U4 = 16 * TAP_CACHE * 8 / 16;  // per wave: the weight cache = the staging area
-constexpr int TAP_STAGE_K = TAP_STAGE_U4 / 192;         // dense K steps per staging window
-static_assert(TAP_STAGE_U4 >= 196 && TAP_STAGE_K >= 1, "staging area holds a compact tile");
+constexpr int TAP_STAGE_K = TAP_STAGE_U4 / kKStepBlocks;  // dense K steps per staging window
+static_assert(TAP_STAGE_U4 >= kCompactBlocks && TAP_STAGE_K >= 1, "staging area holds a compact tile");
 constexpr int TAP_FLAG_CAP = 1 << 16;
 constexpr double TAP_NEAR = 1.0 / 4194304.0;  // 2^-22
 
@@ -115,11 +118,15 @@ __device__ inline int32_t d_quant(double w, double rww, bool& near) {
 // at uint4 (3s + p)·64 + 16·seg + col of the window that starts at K step s0.
 // Compact: block gbase + (kidx >> 4) - g0 of plane p, after the 4 meta uint4.
 __device__ inline int stage_byte(bool compact, int kidx, int p, int col, int s0, int g0, int gbase) {
-    const int u = compact ? 4 + p * 64 + gbase + (kidx >> 4) - g0
-                          : ((((kidx >> 6) - s0) * 3 + p) * 64 + ((kidx >> 4) & 3) * 16 + col);
+    const int u = compact ? kCompactMeta + p * kKStepCols + gbase + (kidx >> 4) - g0
+                          : ((((kidx >> 6) - s0) * kTapPlanes + p) * kKStepCols + ((kidx >> 4) & 3) * 16 + col);
     return 16 * u + (kidx & 15);
 }
 
+// (k_plan_taps and stage_byte take the format's numbers from
+// ipp_pipe_layout.h as named constants inside index expressions of the shape
+// they always had: the header's index functions here changed the kernel's
+// instruction stream.)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k_plan_taps(
     const ipp_tap_axis* __restrict__ axes, int32_t* __restrict__ coefs, int32_t* __restrict__ ctl,
     int2* __restrict__ flags) {
@@ -132,8 +139,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
     const double fs = scale < 1.0 ? 1.0 : scale;
     const double support = 3.0 * fs, ss = 1.0 / fs;
     int32_t* hdr = coefs + a.coef_off;
-    int32_t* bias = hdr + 4 * (int64_t)a.n_tiles;
-    uint4* blk = reinterpret_cast<uint4*>(hdr + 20 * (int64_t)a.n_tiles);
+    int32_t* bias = hdr + kHdrWords * (int64_t)a.n_tiles;
+    uint4* blk = reinterpret_cast<uint4*>(hdr + (kHdrWords + kBiasWords) * (int64_t)a.n_tiles);
     double* wc = reinterpret_cast<double*>(&s_wave[wave][0]);    // [16][TAP_CACHE]
     uint8_t* stage = reinterpret_cast<uint8_t*>(&s_wave[wave][0]);
     uint4* stage4 = &s_wave[wave][0];
@@ -170,8 +177,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
             nK = a.nkb;
         }
         const int niter = (maxcnt + 3) >> 2;   // lane (seg, col) holds taps q = seg + 4i of output col
-        const int64_t boff = (int64_t)t * a.nkb * 192;
-        // Compact layout (ipp.h, ipp_plan_mfma_tile): the 16 outputs' nonzero
+        const int64_t boff = (int64_t)t * a.nkb * kKStepBlocks;  // tap_tile_block
+        // Compact layout (ipp_pipe_layout.h): the 16 outputs' nonzero
         // 16-column groups g0 .. g0 + len - 1, packed at base = the sum of the
         // earlier outputs' len.
         const bool cval = valid && cnt > 0;
@@ -184,7 +191,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
             nb += lc;
         }
         const bool compact = a.compact && !a.identity && nK >= 2 && nb <= 64;  // wave-uniform
-        if (lane == 0) *reinterpret_cast<int4*>(hdr + 4 * t) = make_int4(K0, nK, (int)boff, compact ? 1 : 0);
+        if (lane == 0) *reinterpret_cast<int4*>(hdr + kHdrWords * t) = make_int4(K0, nK, (int)boff, compact ? 1 : 0);
 
         // ---- filter weights: lane (seg, col) evaluates taps seg + 4i --------
         double ww = 0.0;
@@ -239,24 +246,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
         // ---- assemble the blocks in LDS, window by window, then store ------
         const int sw = compact ? nK : TAP_STAGE_K;
         for (int s0 = 0; s0 < nK; s0 += sw) {
-            const int nu = compact ? 196 : 192 * min(sw, nK - s0);
+            const int nu = compact ? kCompactBlocks : kKStepBlocks * min(sw, nK - s0);
             for (int u = lane; u < nu; u += 64) stage4[u] = make_uint4(0u, 0u, 0u, 0u);
             if (compact && seg == 0) reinterpret_cast<int32_t*>(stage)[col] = g0 | glen << 8 | gbase << 16;
             wave_sync();
             auto put = [&](int kidx, uint32_t b) {
                 asm volatile("" : "+v"(kidx));  // per window: nothing of it hoisted out of the window loop
                 if (kidx < 0 || (!compact && ((kidx >> 6) < s0 || (kidx >> 6) >= s0 + sw))) return;
-                // planes 64 uint4 (1 KB) apart in both layouts
+                // planes kKStepCols uint4 (1 KB) apart in both layouts
                 uint8_t* d = stage + stage_byte(compact, kidx, 0, col, s0, g0, gbase);
                 d[0] = (uint8_t)b;
-                d[1024] = (uint8_t)(b >> 8);
-                d[2048] = (uint8_t)(b >> 16);
+                d[16 * kKStepCols] = (uint8_t)(b >> 8);
+                d[2 * 16 * kKStepCols] = (uint8_t)(b >> 16);
             };
 #pragma unroll
             for (int i = 0; i < TAP_NI; ++i)
                 if (i < niter) put(kx[i], pb[i]);
             wave_sync();
-            for (int u = lane; u < nu; u += 64) blk[boff + 192 * (int64_t)s0 + u] = stage4[u];
+            for (int u = lane; u < nu; u += 64) blk[boff + kKStepBlocks * (int64_t)s0 + u] = stage4[u];
             wave_sync();                        // the next window / tile rewrites the area
         }
         if (niter > TAP_NI) {
@@ -275,16 +282,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
                 const uint32_t b = pack(d_quant(d_weight(q, xmin, center, ss), rww, nr));
                 uint8_t* d = tile + stage_byte(compact, kidx, 0, col, 0, g0, gbase);
                 d[0] = (uint8_t)b;
-                d[1024] = (uint8_t)(b >> 8);
-                d[2048] = (uint8_t)(b >> 16);
+                d[16 * kKStepCols] = (uint8_t)(b >> 8);
+                d[2 * 16 * kKStepCols] = (uint8_t)(b >> 16);
             }
         }
         if (compact)  // the zero tail of the tile's area
-            for (int u = 196 + lane; u < nK * 192; u += 64) blk[boff + u] = make_uint4(0u, 0u, 0u, 0u);
+            for (int u = kCompactBlocks + lane; u < nK * kKStepBlocks; u += 64) blk[boff + u] = make_uint4(0u, 0u, 0u, 0u);
 
         sum += __shfl_xor((long long)sum, 16);
         sum += __shfl_xor((long long)sum, 32);
-        if (seg == 0) bias[16 * t + col] = valid ? (int32_t)((1 << 21) + 128 * sum) : 0;
+        if (seg == 0) bias[kBiasWords * t + col] = valid ? (int32_t)((1 << 21) + 128 * sum) : 0;
         if (__any(near) && lane == 0) {
             const int idx = atomicAdd(ctl, 1);
             if (idx < TAP_FLAG_CAP) flags[idx] = make_int2((int)blockIdx.x, t);
@@ -325,7 +332,7 @@ extern "C" int ipp_pipe_plan_taps_cap(const ipp_tap_axis* axes, int32_t n_axes, 
     for (int32_t j = 0; j < n_axes; ++j) {
         const ipp_tap_axis& a = axes[j];
         if (a.in_size <= 0 || a.out_size <= 0 || a.phase < 0 || a.phase > 15 || a.nkb <= 0 ||
-            a.n_tiles != (a.out_size + a.phase + 15) / 16 || (int64_t)a.n_tiles * a.nkb * 192 > INT32_MAX ||
+            a.n_tiles != tap_ntiles(a.out_size, a.phase) || tap_tile_block(a.n_tiles, a.nkb) > INT32_MAX ||
             a.coef_off < 0 || (a.coef_off & 3))
             return IPP_E_ARG;
     }
@@ -357,14 +364,14 @@ extern "C" int ipp_pipe_plan_taps_cap(const ipp_tap_axis* axes, int32_t n_axes, 
     int maxnk = 1;
     for (const int2& f : fl) maxnk = std::max(maxnk, axes[f.x].nkb);
     std::vector<int32_t> bias(16 * fl.size());
-    std::vector<uint8_t> blocks((size_t)maxnk * 3072 * fl.size());
+    std::vector<uint8_t> blocks((size_t)maxnk * kKStepBytes * fl.size());
     // Every tile is rebuilt before any copy is queued, and the copies (which
     // read `bias` / `blocks`) have completed before this function returns on
     // every path.
     std::vector<int32_t> hdrs(4 * fl.size());
     for (size_t i = 0; i < fl.size(); ++i) {
         const int e = ipp_plan_mfma_tile(&axes[fl[i].x], fl[i].y, hdrs.data() + 4 * i, bias.data() + 16 * i,
-                                         blocks.data() + i * (size_t)maxnk * 3072, (int64_t)maxnk * 3072);
+                                         blocks.data() + i * (size_t)maxnk * kKStepBytes, (int64_t)maxnk * kKStepBytes);
         if (e) return e;
     }
     int rc = IPP_OK;
@@ -373,7 +380,7 @@ extern "C" int ipp_pipe_plan_taps_cap(const ipp_tap_axis* axes, int32_t n_axes, 
     int64_t pbytes = (8 * (1 + (int64_t)fl.size()) + 15) & ~(int64_t)15;
     for (size_t i = 0; i < fl.size(); ++i) {
         recoff[i] = pbytes;
-        pbytes += 32 + 64 + (int64_t)hdrs[4 * i + 1] * 3072;
+        pbytes += 32 + 64 + (int64_t)hdrs[4 * i + 1] * kKStepBytes;
     }
     std::vector<uint8_t> pack;
     if (pbytes <= pack_cap) {
@@ -385,11 +392,11 @@ extern "C" int ipp_pipe_plan_taps_cap(const ipp_tap_axis* axes, int32_t n_axes, 
             const int t = fl[i].y;
             ph[1 + i] = recoff[i];
             int64_t* m = reinterpret_cast<int64_t*>(pack.data() + recoff[i]);
-            m[0] = a.coef_off + 4 * (int64_t)a.n_tiles + 16 * t;
-            m[1] = a.coef_off + 20 * (int64_t)a.n_tiles + 4 * (int64_t)hdrs[4 * i + 2];
-            m[2] = (int64_t)hdrs[4 * i + 1] * 3072;
+            m[0] = a.coef_off + tap_bias_word(a.n_tiles) + kBiasWords * t;
+            m[1] = a.coef_off + tap_block_word(a.n_tiles) + 4 * (int64_t)hdrs[4 * i + 2];
+            m[2] = (int64_t)hdrs[4 * i + 1] * kKStepBytes;
             memcpy(pack.data() + recoff[i] + 32, bias.data() + 16 * i, 64);
-            memcpy(pack.data() + recoff[i] + 96, blocks.data() + i * (size_t)maxnk * 3072, (size_t)m[2]);
+            memcpy(pack.data() + recoff[i] + 96, blocks.data() + i * (size_t)maxnk * kKStepBytes, (size_t)m[2]);
         }
         uint8_t* d_pack = reinterpret_cast<uint8_t*>(d_flags + TAP_FLAG_CAP);
         if (hipMemcpyAsync(d_pack, pack.data(), (size_t)pbytes, hipMemcpyHostToDevice, s) != hipSuccess) {
@@ -404,10 +411,10 @@ extern "C" int ipp_pipe_plan_taps_cap(const ipp_tap_axis* axes, int32_t n_axes, 
             const int t = fl[i].y;
             const int32_t* hdr = hdrs.data() + 4 * i;
             int32_t* base = coefs + a.coef_off;
-            if (hipMemcpyAsync(base + 4 * (int64_t)a.n_tiles + 16 * t, bias.data() + 16 * i, 64,
+            if (hipMemcpyAsync(base + tap_bias_word(a.n_tiles) + kBiasWords * t, bias.data() + 16 * i, 64,
                                hipMemcpyHostToDevice, s) != hipSuccess ||
-                hipMemcpyAsync(base + 20 * (int64_t)a.n_tiles + 4 * (int64_t)hdr[2],
-                               blocks.data() + i * (size_t)maxnk * 3072, (size_t)hdr[1] * 3072, hipMemcpyHostToDevice,
+                hipMemcpyAsync(base + tap_block_word(a.n_tiles) + 4 * (int64_t)hdr[2],
+                               blocks.data() + i * (size_t)maxnk * kKStepBytes, (size_t)hdr[1] * kKStepBytes, hipMemcpyHostToDevice,
                                s) != hipSuccess)
                 rc = IPP_E_LAUNCH;
         }

@@ -372,6 +372,37 @@ def overlap_bounds(n: int, parts: int, ratio: float = 1.0, group: int = N.IPP_PI
     return b
 
 
+def _check_gpu_u8(owner: str, caller: str, src: torch.Tensor, bgs: torch.Tensor, out: torch.Tensor) -> None:
+    """The entry points that take tensors hand their raw pointers to the
+    launches: each must be a contiguous uint8 tensor on the GPU."""
+    for t, name in ((src, "src"), (bgs, "bgs"), (out, "out")):
+        if not (t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()):
+            raise N.NativeUnavailable(f"{owner}.{caller}: {name} must be a contiguous uint8 ROCm tensor")
+
+
+def _launch_hpass_bgcopy(lib, plan: PipePlan, src: int, tmp: int, coefs: int, descs: int, n: int, bgs: int, out: int,
+                         stream: int) -> None:
+    """The H launch (ipp_pipe_hpass_bgcopy) of `n` descriptors at device
+    address `descs`; the other buffers are device addresses too."""
+    N.check(lib.ipp_pipe_hpass_bgcopy(src, tmp, coefs, descs, n, plan.max_out_w, plan.max_rows, 3, N.np_ptr(plan.hsv),
+                                      plan.tap_format, bgs, out, stream), "ipp_pipe_hpass_bgcopy")
+
+
+def _launch_vblend_bands(lib, plan: PipePlan, tmp: int, bgs: int, out: int, coefs: int, descs: int, n: int,
+                         stream: int) -> None:
+    """The V launch (ipp_pipe_vblend_bands) of the same descriptor range."""
+    N.check(lib.ipp_pipe_vblend_bands(tmp, bgs, out, coefs, descs, n, plan.bg_w, plan.bg_h, plan.max_ov_w,
+                                      plan.max_ov_h, plan.tap_format, stream), "ipp_pipe_vblend_bands")
+
+
+def _pipe_status(lib, device) -> int:
+    """Sticky status of the pipe kernels since the last call (ipp_pipe_status;
+    bit 0: an H tile's window exceeded the LDS ring).  Synchronises."""
+    st = np.zeros(1, np.int32)
+    N.check(lib.ipp_pipe_status(N.np_ptr(st), _stream(device)), "ipp_pipe_status")
+    return int(st[0])
+
+
 class PipeRunner:
     """Device-resident plan + scratch for repeated runs of one batch."""
 
@@ -386,21 +417,16 @@ class PipeRunner:
 
     @staticmethod
     def _check_tensors(caller: str, src: torch.Tensor, bgs: torch.Tensor, out: torch.Tensor) -> None:
-        """The entry points that take tensors hand their raw pointers to the
-        launches: each must be a contiguous uint8 tensor on the GPU."""
-        for t, name in ((src, "src"), (bgs, "bgs"), (out, "out")):
-            if not (t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()):
-                raise N.NativeUnavailable(f"PipeRunner.{caller}: {name} must be a contiguous uint8 ROCm tensor")
+        _check_gpu_u8("PipeRunner", caller, src, bgs, out)
 
     def hpass_bgcopy(self, src: torch.Tensor, bgs: torch.Tensor, out: torch.Tensor, items=None) -> None:
         """H pass + the composite rows outside the overlay bands (split form);
         `items` = (first, count) of the descriptors in processing order."""
         p = self.plan
         i0, n = items if items is not None else (0, len(p.descs))
-        N.check(self.lib.ipp_pipe_hpass_bgcopy(src.data_ptr(), self.tmp.data_ptr(), self.coefs.data_ptr(),
-                                               self.descs.data_ptr() + i0 * p.descs.itemsize, n, p.max_out_w,
-                                               p.max_rows, 3, N.np_ptr(p.hsv), p.tap_format, bgs.data_ptr(),
-                                               out.data_ptr(), _stream(self.device)), "ipp_pipe_hpass_bgcopy")
+        _launch_hpass_bgcopy(self.lib, p, src.data_ptr(), self.tmp.data_ptr(), self.coefs.data_ptr(),
+                             self.descs.data_ptr() + i0 * p.descs.itemsize, n, bgs.data_ptr(), out.data_ptr(),
+                             _stream(self.device))
         self._hpass_done = True
 
     def overlay_bboxes(self, alpha_min: int = 1, items=None) -> np.ndarray:
@@ -446,10 +472,8 @@ class PipeRunner:
         """V pass + paste over the 16-row bands the overlay touches (split form)."""
         p = self.plan
         i0, n = items if items is not None else (0, len(p.descs))
-        N.check(self.lib.ipp_pipe_vblend_bands(self.tmp.data_ptr(), bgs.data_ptr(), out.data_ptr(),
-                                               self.coefs.data_ptr(), self.descs.data_ptr() + i0 * p.descs.itemsize,
-                                               n, p.bg_w, p.bg_h, p.max_ov_w, p.max_ov_h, p.tap_format,
-                                               _stream(self.device)), "ipp_pipe_vblend_bands")
+        _launch_vblend_bands(self.lib, p, self.tmp.data_ptr(), bgs.data_ptr(), out.data_ptr(), self.coefs.data_ptr(),
+                             self.descs.data_ptr() + i0 * p.descs.itemsize, n, _stream(self.device))
 
     def run_overlapped(self, src: torch.Tensor, bgs: torch.Tensor, out: torch.Tensor, parts: int,
                        ratio: float = 1.0) -> None:
@@ -484,9 +508,7 @@ class PipeRunner:
     def status(self) -> int:
         """Sticky status of the pipe kernels since the last call (ipp_pipe_status;
         bit 0: an H tile's window exceeded the LDS ring).  Synchronises."""
-        st = np.zeros(1, np.int32)
-        N.check(self.lib.ipp_pipe_status(N.np_ptr(st), _stream(self.device)), "ipp_pipe_status")
-        return int(st[0])
+        return _pipe_status(self.lib, self.device)
 
     @property
     def split(self) -> bool:
@@ -609,16 +631,11 @@ class PipeStream:
                 ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) if record else None
                 if ev:
                     ev[0].record(main)
-                N.check(self.lib.ipp_pipe_hpass_bgcopy(src.data_ptr(), b["tmp"].data_ptr(), b["coefs"].data_ptr(),
-                                                       b["descs"].data_ptr(), len(plan.descs), plan.max_out_w,
-                                                       plan.max_rows, 3, N.np_ptr(plan.hsv), plan.tap_format,
-                                                       bgs.data_ptr(), out.data_ptr(), main.cuda_stream),
-                        "ipp_pipe_hpass_bgcopy")
-                N.check(self.lib.ipp_pipe_vblend_bands(b["tmp"].data_ptr(), bgs.data_ptr(), out.data_ptr(),
-                                                       b["coefs"].data_ptr(), b["descs"].data_ptr(),
-                                                       len(plan.descs), plan.bg_w, plan.bg_h, plan.max_ov_w,
-                                                       plan.max_ov_h, plan.tap_format, main.cuda_stream),
-                        "ipp_pipe_vblend_bands")
+                _launch_hpass_bgcopy(self.lib, plan, src.data_ptr(), b["tmp"].data_ptr(), b["coefs"].data_ptr(),
+                                     b["descs"].data_ptr(), len(plan.descs), bgs.data_ptr(), out.data_ptr(),
+                                     main.cuda_stream)
+                _launch_vblend_bands(self.lib, plan, b["tmp"].data_ptr(), bgs.data_ptr(), out.data_ptr(),
+                                     b["coefs"].data_ptr(), b["descs"].data_ptr(), len(plan.descs), main.cuda_stream)
                 if ev:
                     ev[1].record(main)
                     self.events.append(ev)
@@ -792,9 +809,7 @@ class SceneRunner:
         self._scratch = None
 
     def _check(self, caller: str, src: torch.Tensor, bgs: torch.Tensor, out: torch.Tensor) -> None:
-        for t, name in ((src, "src"), (bgs, "bgs"), (out, "out")):
-            if not (t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()):
-                raise N.NativeUnavailable(f"SceneRunner.{caller}: {name} must be a contiguous uint8 ROCm tensor")
+        _check_gpu_u8("SceneRunner", caller, src, bgs, out)
         p, S, K = self.plan.pipe, self.plan.n_scenes, self.plan.per_scene
         if src.dim() < 1 or src.shape[0] != S * K:
             raise ValueError(f"SceneRunner.{caller}: src holds {src.shape[0] if src.dim() else 0} images, "
@@ -815,17 +830,15 @@ class SceneRunner:
         p, S, K = self.plan.pipe, self.plan.n_scenes, self.plan.per_scene
         st, lib = _stream(self.device), self.lib
         hsv = N.np_ptr(p.hsv)
-        N.check(lib.ipp_pipe_hpass_bgcopy(src.data_ptr(), self.tmp.data_ptr(), self.coefs.data_ptr(), self._dptr(0),
-                                          S, p.max_out_w, p.max_rows, 3, hsv, p.tap_format, bgs.data_ptr(),
-                                          out.data_ptr(), st), "ipp_pipe_hpass_bgcopy")
+        _launch_hpass_bgcopy(lib, p, src.data_ptr(), self.tmp.data_ptr(), self.coefs.data_ptr(), self._dptr(0), S,
+                             bgs.data_ptr(), out.data_ptr(), st)
         if K > 1:
             N.check(lib.ipp_pipe_hpass(src.data_ptr(), self.tmp.data_ptr(), self.coefs.data_ptr(), self._dptr(S),
                                        S * (K - 1), p.max_out_w, p.max_rows, 3, hsv, p.tap_format, st),
                     "ipp_pipe_hpass")
         self._hpass_done = True
-        N.check(lib.ipp_pipe_vblend_bands(self.tmp.data_ptr(), bgs.data_ptr(), out.data_ptr(), self.coefs.data_ptr(),
-                                          self._dptr(0), S, p.bg_w, p.bg_h, p.max_ov_w, p.max_ov_h, p.tap_format,
-                                          st), "ipp_pipe_vblend_bands")
+        _launch_vblend_bands(lib, p, self.tmp.data_ptr(), bgs.data_ptr(), out.data_ptr(), self.coefs.data_ptr(),
+                             self._dptr(0), S, st)
         # one launch per later layer: two overlays of a scene never share a launch (ipp.h)
         for k in range(1, K):
             N.check(lib.ipp_pipe_vblend_over(self.tmp.data_ptr(), out.data_ptr(), self.coefs.data_ptr(),
@@ -835,9 +848,7 @@ class SceneRunner:
 
     def status(self) -> int:
         """Sticky status of the pipe kernels since the last call (``PipeRunner.status``).  Synchronises."""
-        st = np.zeros(1, np.int32)
-        N.check(self.lib.ipp_pipe_status(N.np_ptr(st), _stream(self.device)), "ipp_pipe_status")
-        return int(st[0])
+        return _pipe_status(self.lib, self.device)
 
     def _launch_boxes(self, alpha_min: int, cover_min: int) -> torch.Tensor:
         if not self._hpass_done:

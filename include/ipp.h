@@ -423,7 +423,8 @@ int ipp_plan_pipe_axes(int32_t n, const int32_t* in_sizes, const int32_t* out_si
                        const int32_t* identity, const int32_t* shift_first,
                        const int32_t* transposed, const int64_t* offsets, int32_t* out,
                        int32_t* first_last, int32_t n_threads);
-/* MFMA tile format of a pipe axis (v_mfma_i32_16x16x64_i8; see ipp_host.cpp):
+/* MFMA tile format of a pipe axis (v_mfma_i32_16x16x64_i8; stated in
+ * csrc/ipp_pipe_layout.h):
  * size bound in int32 for (in, out, ksize), bound on K steps per tile, and the
  * conversion from standard Pillow taps (input indices minus `shift`, tiles
  * offset by `phase` outputs).  ipp_plan_pipe_axes writes this format for axes
@@ -543,16 +544,9 @@ int ipp_pipe_plan_taps(const ipp_tap_axis* axes, int32_t n_axes, int32_t* coefs,
 int ipp_pipe_plan_taps_cap(const ipp_tap_axis* axes, int32_t n_axes, int32_t* coefs, void* scratch,
                            int64_t* stats, int64_t pack_cap, void* stream);
 /* Host restatement of one tile of that format (Resample.c taps, libm sin):
- * hdr[4], bias[16], blocks (nK·3072 bytes, ≤ blocks_cap).
- * Compact layout (axis->compact, nK >= 2 and at most 64 nonzero 16-column
- * groups over the tile's 16 outputs; hdr[3] = 1): bytes 0..63 hold
- * meta[16], meta[n] = g0 | len << 8 | base << 16 (output n's taps lie in the
- * 16-column groups g0 .. g0 + len - 1 counted from K0; base = the sum of len
- * over the outputs before n); plane p's group block i (16 signed bytes) sits
- * at byte 64 + (64 p + i)·16, block base + j holding output n's group g0 + j;
- * everything else is zero.  The H pass loads one block per lane and plane and
- * builds each K step's B operand by ds_bpermute (ipp_pipe.hip), 3 loads per
- * tile instead of 3·nK. */
+ * hdr[4], bias[16], blocks (nK·3072 bytes, ≤ blocks_cap); dense, or compact
+ * (hdr[3] = 1) where axis->compact allows it: both layouts are stated in
+ * csrc/ipp_pipe_layout.h. */
 int ipp_plan_mfma_tile(const ipp_tap_axis* axis, int32_t t, int32_t hdr[4], int32_t bias[16],
                        uint8_t* blocks, int64_t blocks_cap);
 /* Pieces of ipp_plan_pipe_batch exposed for the tests: the division-free
