@@ -16,6 +16,10 @@
 //   pixel counts (the same channel-3 V pass, stored as alpha planes, then a
 //   pass that compares the planes by composite coordinate).
 //
+//   ipp_pipe_scene_map: the same rule's per-pixel answer — one visibility map
+//   per composite, bit k = layer k visible (instance masks), from the same
+//   planes; optionally the boxes with it.
+//
 // All follow ipp_alpha_bbox's convention (ipp_gather.hip): the boxes are
 // pre-set to (INT_MAX, INT_MAX, -1, -1), every wave that saw a visible pixel
 // issues four device-scope atomics, and a finish kernel turns an untouched row
@@ -316,6 +320,146 @@ k_scene_visible(const ipp_pipe_desc* __restrict__ descs, const int32_t* __restri
     }
 }
 
+// ---------------------------------------------------------------------------
+// ipp_pipe_scene_map: the visibility rule's per-pixel answer (instance masks).
+// Byte (Y, X) of scene s's map holds bit k iff layer k is mapped, has a plane,
+// its rectangle clipped to the background holds (X, Y), A_k >= alpha_min there
+// and no later layer with a plane has A_j >= cover_min there.
+//
+// Composite-centric: a block is MT_H rows × MT_W columns of one scene's map,
+// a thread MT_PX consecutive pixels of one row, stored as one aligned 16-B
+// vector (the map and its pitch are 16-B aligned, so a vector never crosses
+// the pitch).  Every byte of every slot has exactly one writer, so there are
+// no atomics and the caller clears nothing.  The scene's slot entries and
+// rectangles are block-uniform (scalar loads); the layers are walked from the
+// top down with a per-pixel `covered` bit, and a layer whose clipped rectangle
+// misses the wave's rows or the block's columns is not touched: a block no
+// layer meets stores zeros and reads no plane.  Plane bytes are read by
+// composite coordinate with byte loads (cx = X - x_k is unaligned), each
+// guarded by the clipped rectangle: 0 <= cy < ov_h <= max_ov_h and 0 <= cx <
+// ov_w <= max_ov_w, so every access lies in the plane of a descriptor in
+// [0, n), and the rows it reads are the ones k_scene_alpha wrote (the
+// overlay's rows inside the background).
+// ---------------------------------------------------------------------------
+constexpr int MT_W = 256, MT_H = 16, MT_PX = 16;
+constexpr int kSceneMapMaxLayers = IPP_SCENE_MAP_MAX_LAYERS;
+static_assert(kSceneMapMaxLayers == 8, "one bit per layer in a map byte");
+static_assert(MT_PX == 16 && MT_W == 16 * MT_PX && MT_H * (MT_W / MT_PX) == 256, "k_scene_map's thread map");
+
+// The slot table alone, for a map without boxes (k_scene_init fills it beside the rows).
+__global__ void k_scene_table(int32_t* __restrict__ table, const int32_t* __restrict__ scene_layer, int n,
+                              int n_scenes, int K) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int s = scene_layer[2 * i], k = scene_layer[2 * i + 1];
+    if ((unsigned)s < (unsigned)n_scenes && (unsigned)k < (unsigned)K) table[(int64_t)s * K + k] = i;
+}
+
+__global__ void __launch_bounds__(256)
+k_scene_map(const ipp_pipe_desc* __restrict__ descs, const int32_t* __restrict__ table,
+            const uint8_t* __restrict__ planes, FastDiv tiles, FastDiv tiles_x, int n, int K, int bg_w, int bg_h,
+            int max_ov_w, int max_ov_h, int alpha_min, int cover_min, uint8_t* __restrict__ map,
+            int64_t map_pitch) {
+    const uint32_t b = xcd_remap(blockIdx.x, gridDim.x);
+    const int scene = (int)fdiv(b, tiles);
+    const uint32_t t = b - (uint32_t)scene * tiles.d;
+    const int ty = (int)fdiv(t, tiles_x), tx = (int)(t - (uint32_t)ty * tiles_x.d);
+    const int bx0 = tx * MT_W;                                                  // the block's columns
+    const int wy0 = ty * MT_H + 4 * __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // the wave's 4 rows
+    const int Y = ty * MT_H + (int)(threadIdx.x >> 4);
+    const int X0 = bx0 + MT_PX * (int)(threadIdx.x & 15);
+    const int64_t pitch = scene_pitch(max_ov_w), psize = (int64_t)max_ov_h * pitch;
+
+    // Phase 1 (block-uniform): each layer's descriptor and paste position; d[k]
+    // stays -1 unless the layer's clipped rectangle meets the wave's pixels.
+    int d[kSceneMapMaxLayers], px[kSceneMapMaxLayers], py[kSceneMapMaxLayers], pw[kSceneMapMaxLayers],
+        ph[kSceneMapMaxLayers];
+#pragma unroll
+    for (int k = 0; k < kSceneMapMaxLayers; ++k) {
+        d[k] = -1;
+        px[k] = py[k] = pw[k] = ph[k] = 0;
+        if (k >= K) continue;
+        const int dk = table[(int64_t)scene * K + k];
+        if ((unsigned)dk >= (unsigned)n) continue;  // no descriptor in this slot
+        const ipp_paste_desc p = descs[dk].p;
+        if (p.ov_w <= 0 || p.ov_h <= 0 || p.ov_w > max_ov_w || p.ov_h > max_ov_h) continue;  // no plane
+        // the rectangle clipped to the background (64-bit: x + ov_w of a foreign descriptor must not wrap)
+        const int64_t rx0 = max((int64_t)p.x, (int64_t)0), rx1 = min((int64_t)p.x + p.ov_w, (int64_t)bg_w);
+        const int64_t ry0 = max((int64_t)p.y, (int64_t)0), ry1 = min((int64_t)p.y + p.ov_h, (int64_t)bg_h);
+        if (rx0 >= (int64_t)bx0 + MT_W || rx1 <= bx0 || ry0 >= (int64_t)wy0 + 4 || ry1 <= wy0) continue;
+        d[k] = dk;
+        px[k] = p.x, py[k] = p.y, pw[k] = p.ov_w, ph[k] = p.ov_h;
+    }
+
+    if (Y >= bg_h || X0 >= map_pitch) return;  // (no barrier below)
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+    uint32_t covered = 0u;  // bit i: a later layer covers pixel X0 + i
+    // Phase 2: top down.
+#pragma unroll
+    for (int k = kSceneMapMaxLayers - 1; k >= 0; --k) {
+        if (d[k] < 0) continue;  // wave-uniform
+        const int cy = Y - py[k];
+        if ((unsigned)cy >= (unsigned)ph[k]) continue;
+        const uint8_t* row = planes + (int64_t)d[k] * psize + (int64_t)cy * pitch;
+        const int cx0 = X0 - px[k];  // (X0 < map_pitch and |x| of a met rectangle are far below 2^31)
+        const int xlim = min(pw[k], bg_w - px[k]);  // columns of the overlay inside the background
+#pragma unroll
+        for (int i = 0; i < MT_PX; ++i) {
+            const int cx = cx0 + i;
+            if (cx >= 0 && cx < xlim) {
+                const int a = row[cx];
+                if (!((covered >> i) & 1u) && a >= alpha_min) w[i >> 2] |= (1u << k) << (8 * (i & 3));
+                if (a >= cover_min) covered |= 1u << i;
+            }
+        }
+    }
+    store16<0>(map + ((int64_t)scene * bg_h + Y) * map_pitch + X0, 16, true, w);
+}
+
+// The launches of ipp_pipe_scene_boxes and ipp_pipe_scene_map after their
+// argument checks: the slot table, the alpha planes, then the boxes (`rows`)
+// and / or the map, whichever is given.
+int scene_launches(const uint8_t* tmp, const int32_t* coefs, const ipp_pipe_desc* descs, const int32_t* scene_layer,
+                   int n_images, int n_scenes, int per_scene, int bg_w, int bg_h, int max_ov_w, int max_ov_h,
+                   int alpha_min, int cover_min, uint8_t* scratch, int32_t* rows, uint8_t* map, int64_t map_pitch,
+                   hipStream_t s) {
+    const int tyb = paste_max_bands(max_ov_h), strips = (max_ov_h + SVR - 1) / SVR;
+    const int64_t slots = (int64_t)n_scenes * per_scene;
+    if ((int64_t)tyb * n_images >= INT32_MAX || (int64_t)strips * n_images >= INT32_MAX || slots >= INT32_MAX)
+        return IPP_E_ARG;
+    int mtx = 0, mty = 0;
+    if (map) {
+        mtx = (int)((map_pitch + MT_W - 1) / MT_W), mty = (bg_h + MT_H - 1) / MT_H;
+        if ((int64_t)mtx * mty * n_scenes >= INT32_MAX) return IPP_E_ARG;
+    }
+    int32_t* table = reinterpret_cast<int32_t*>(scratch);
+    uint8_t* planes = scratch + scene_table_bytes(slots);
+    if (slots > 0 && hipMemsetAsync(table, 0xFF, 4 * (size_t)slots, s) != hipSuccess) return IPP_E_LAUNCH;
+    if (n_images > 0) {
+        const int ib = (n_images + 255) / 256;
+        if (rows)
+            hipLaunchKernelGGL(k_scene_init, dim3(ib), dim3(256), 0, s, rows, table, scene_layer, n_images, n_scenes,
+                               per_scene);
+        else
+            hipLaunchKernelGGL(k_scene_table, dim3(ib), dim3(256), 0, s, table, scene_layer, n_images, n_scenes,
+                               per_scene);
+        hipLaunchKernelGGL(k_scene_alpha, dim3((uint32_t)(tyb * n_images)), dim3(256), 0, s, tmp, coefs, descs,
+                           fast_div((uint32_t)tyb), max_ov_w, max_ov_h, planes);
+        if (rows) {
+            hipLaunchKernelGGL(k_scene_visible, dim3((uint32_t)(strips * n_images)), dim3(256), 0, s, descs,
+                               scene_layer, table, planes, fast_div((uint32_t)strips), n_images, n_scenes, per_scene,
+                               max_ov_w, max_ov_h, alpha_min, cover_min, rows);
+            hipLaunchKernelGGL(k_scene_finish, dim3(ib), dim3(256), 0, s, rows, n_images);
+        }
+    }
+    if (map && n_scenes > 0)
+        hipLaunchKernelGGL(k_scene_map, dim3((uint32_t)(mtx * mty * n_scenes)), dim3(256), 0, s, descs, table, planes,
+                           fast_div((uint32_t)(mtx * mty)), fast_div((uint32_t)mtx), n_images, per_scene, bg_w, bg_h,
+                           max_ov_w, max_ov_h, alpha_min, cover_min, map, map_pitch);
+    IPP_CHECK_LAUNCH();
+    return IPP_OK;
+}
+
 }  // namespace
 
 extern "C" int ipp_pipe_overlay_bbox(const uint8_t* tmp, const int32_t* coefs, const ipp_pipe_desc* descs,
@@ -373,22 +517,24 @@ extern "C" int ipp_pipe_scene_boxes(const uint8_t* tmp, const int32_t* coefs, co
         return IPP_E_ARG;
     if ((reinterpret_cast<uintptr_t>(scratch) & 15u) != 0) return IPP_E_ARG;  // the planes are read by dwords
     if (n_images == 0) return IPP_OK;
-    const int tyb = paste_max_bands(max_ov_h), strips = (max_ov_h + SVR - 1) / SVR;
-    const int64_t slots = (int64_t)n_scenes * per_scene;
-    if ((int64_t)tyb * n_images >= INT32_MAX || slots >= INT32_MAX) return IPP_E_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    int32_t* table = reinterpret_cast<int32_t*>(scratch);
-    uint8_t* planes = scratch + scene_table_bytes(slots);
-    if (slots > 0 && hipMemsetAsync(table, 0xFF, 4 * (size_t)slots, s) != hipSuccess) return IPP_E_LAUNCH;
-    const int ib = (n_images + 255) / 256;
-    hipLaunchKernelGGL(k_scene_init, dim3(ib), dim3(256), 0, s, out, table, scene_layer, n_images, n_scenes,
-                       per_scene);
-    hipLaunchKernelGGL(k_scene_alpha, dim3((uint32_t)(tyb * n_images)), dim3(256), 0, s, tmp, coefs, descs,
-                       fast_div((uint32_t)tyb), max_ov_w, max_ov_h, planes);
-    hipLaunchKernelGGL(k_scene_visible, dim3((uint32_t)(strips * n_images)), dim3(256), 0, s, descs, scene_layer,
-                       table, planes, fast_div((uint32_t)strips), n_images, n_scenes, per_scene, max_ov_w, max_ov_h,
-                       alpha_min, cover_min, out);
-    hipLaunchKernelGGL(k_scene_finish, dim3(ib), dim3(256), 0, s, out, n_images);
-    IPP_CHECK_LAUNCH();
-    return IPP_OK;
+    return scene_launches(tmp, coefs, descs, scene_layer, n_images, n_scenes, per_scene, 0, 0, max_ov_w, max_ov_h,
+                          alpha_min, cover_min, scratch, out, nullptr, 0, (hipStream_t)stream);
+}
+
+extern "C" int ipp_pipe_scene_map(const uint8_t* tmp, const int32_t* coefs, const ipp_pipe_desc* descs,
+                                  const int32_t* scene_layer, int32_t n_images, int32_t n_scenes, int32_t per_scene,
+                                  int32_t bg_w, int32_t bg_h, int32_t max_ov_w, int32_t max_ov_h, int32_t alpha_min,
+                                  int32_t cover_min, int32_t tap_format, uint8_t* scratch, int32_t* rows,
+                                  uint8_t* map, int64_t map_pitch, void* stream) {
+    if (alpha_min < 1 || alpha_min > 255 || cover_min < 1 || cover_min > 255 || tap_format != IPP_TAPS_MFMA)
+        return IPP_E_ARG;
+    if (!tmp || !coefs || !descs || !scene_layer || !scratch || !map || n_images < 0 || n_scenes < 0 ||
+        per_scene < 1 || per_scene > IPP_SCENE_MAP_MAX_LAYERS || max_ov_w <= 0 || max_ov_h <= 0)
+        return IPP_E_ARG;
+    if (bg_w <= 0 || bg_h <= 0 || map_pitch < bg_w || (map_pitch & 15) != 0 || map_pitch > INT32_MAX)
+        return IPP_E_ARG;
+    // the planes are read by dwords, the map is stored by 16-B vectors
+    if (((reinterpret_cast<uintptr_t>(scratch) | reinterpret_cast<uintptr_t>(map)) & 15u) != 0) return IPP_E_ARG;
+    return scene_launches(tmp, coefs, descs, scene_layer, n_images, n_scenes, per_scene, bg_w, bg_h, max_ov_w,
+                          max_ov_h, alpha_min, cover_min, scratch, rows, map, map_pitch, (hipStream_t)stream);
 }

@@ -26,6 +26,9 @@ Scenes (an addition; the reference pastes one overlay per composite):
 order — layer 0 as above, every later layer by an H launch without the copy
 (``ipp_pipe_hpass``) and an in-place V launch (``ipp_pipe_vblend_over``) — and
 label each overlay by what no later layer covers (``ipp_pipe_scene_boxes``).
+``SceneRunner.scene_masks`` keeps that rule's per-pixel answer: one visibility
+map per composite, bit k = layer k visible (``ipp_pipe_scene_map``;
+``instance_ids`` and ``scene_instance_masks`` turn it into instance masks).
 """
 from __future__ import annotations
 
@@ -793,6 +796,56 @@ def scene_labels(boxes: np.ndarray, bg_w: int, bg_h: int, class_ids=0, min_visib
     return out
 
 
+def scene_map_pitch(bg_w: int) -> int:
+    """Row pitch in bytes of a visibility map (``SceneRunner.scene_masks``): ⌈bg_w / 16⌉·16."""
+    return (int(bg_w) + 15) // 16 * 16
+
+
+# instance id of a visibility-map byte: 0 = nothing visible, else 1 + its topmost set bit
+_INSTANCE_LUT = np.array([v.bit_length() for v in range(256)], np.uint8)
+
+
+def instance_ids(vis_map):
+    """Instance-id image of a visibility map (``SceneRunner.scene_masks``), a
+    torch or numpy uint8 array of any shape: 0 where no overlay is visible,
+    otherwise 1 + the topmost layer whose bit is set (1 + layer within the
+    scene).  The result has the input's type, shape and device."""
+    if isinstance(vis_map, torch.Tensor):
+        if vis_map.dtype != torch.uint8:
+            raise ValueError(f"instance_ids: a uint8 map expected, got {vis_map.dtype}")
+        return torch.from_numpy(_INSTANCE_LUT).to(vis_map.device)[vis_map.long()]
+    vis_map = np.asarray(vis_map)
+    if vis_map.dtype != np.uint8:
+        raise ValueError(f"instance_ids: a uint8 map expected, got {vis_map.dtype}")
+    return _INSTANCE_LUT[vis_map]
+
+
+def scene_instance_masks(vis_map, rows) -> List[List[Optional[np.ndarray]]]:
+    """Per-overlay instance masks from a copied-back visibility map (S, bg_h,
+    bg_w) and the (S, K, 6) rows of ``scene_boxes``: masks[s] lists, in layer
+    order, the boolean array of bit k cropped to overlay k's box (y1 - y0, x1
+    - x0), or None for an overlay without a visible pixel.  Host code; a
+    device map is copied back first (synchronises)."""
+    if isinstance(vis_map, torch.Tensor):
+        vis_map = vis_map.cpu().numpy()
+    vis_map, rows = np.asarray(vis_map), np.asarray(rows)
+    if rows.ndim != 3 or rows.shape[2] != 6:
+        raise ValueError(f"rows of shape {rows.shape}: (scenes, layers, 6) expected")
+    S, K = rows.shape[:2]
+    if vis_map.dtype != np.uint8 or vis_map.ndim != 3 or vis_map.shape[0] != S:
+        raise ValueError(f"a uint8 map of {S} scenes (S, bg_h, bg_w) expected, got {vis_map.dtype} {vis_map.shape}")
+    if K > N.IPP_SCENE_MAP_MAX_LAYERS:
+        raise ValueError(f"{K} layers: a visibility map holds at most {N.IPP_SCENE_MAP_MAX_LAYERS}")
+    out: List[List[Optional[np.ndarray]]] = []
+    for s in range(S):
+        masks: List[Optional[np.ndarray]] = []
+        for k in range(K):
+            x0, y0, x1, y1 = (int(v) for v in rows[s, k, :4])
+            masks.append(None if x0 < 0 else ((vis_map[s, y0:y1, x0:x1] >> k) & 1).astype(bool))
+        out.append(masks)
+    return out
+
+
 class SceneRunner:
     """Device-resident scene plan + scratch for repeated runs of one batch:
     2 + K launches on the current stream (2 when K = 1, the pipe's own)."""
@@ -850,23 +903,60 @@ class SceneRunner:
         """Sticky status of the pipe kernels since the last call (``PipeRunner.status``).  Synchronises."""
         return _pipe_status(self.lib, self.device)
 
-    def _launch_boxes(self, alpha_min: int, cover_min: int) -> torch.Tensor:
+    def _scene_scratch(self, caller: str) -> None:
+        """The guard and the (once allocated) scratch shared by the label and the map launches."""
         if not self._hpass_done:
-            raise N.NativeError("SceneRunner.scene_boxes: no H launch (run) has run on this runner")
-        p, S, K = self.plan.pipe, self.plan.n_scenes, self.plan.per_scene
-        n = S * K
+            raise N.NativeError(f"SceneRunner.{caller}: no H launch (run) has run on this runner")
         if self._scratch is None:
-            nb = self.lib.ipp_pipe_scene_scratch_bytes(n, S, K, p.max_ov_w, p.max_ov_h)
+            p, S, K = self.plan.pipe, self.plan.n_scenes, self.plan.per_scene
+            nb = self.lib.ipp_pipe_scene_scratch_bytes(S * K, S, K, p.max_ov_w, p.max_ov_h)
             if nb < 0:
                 raise N.NativeError(f"ipp_pipe_scene_scratch_bytes failed with code {nb}")
             self._scratch = torch.empty(int(nb), dtype=torch.uint8, device=self.device)
             self._scene_layer = _to_dev(self.plan.scene_layer, self.device)
+
+    def _launch_boxes(self, alpha_min: int, cover_min: int) -> torch.Tensor:
+        self._scene_scratch("scene_boxes")
+        p, S, K = self.plan.pipe, self.plan.n_scenes, self.plan.per_scene
+        n = S * K
         rows = torch.empty(6 * n, dtype=torch.int32, device=self.device)
         N.check(self.lib.ipp_pipe_scene_boxes(self.tmp.data_ptr(), self.coefs.data_ptr(), self._dptr(0),
                                               self._scene_layer.data_ptr(), n, S, K, p.max_ov_w, p.max_ov_h,
                                               alpha_min, cover_min, p.tap_format, self._scratch.data_ptr(),
                                               rows.data_ptr(), _stream(self.device)), "ipp_pipe_scene_boxes")
         return rows
+
+    def _check_map(self, caller: str, out: Optional[torch.Tensor]) -> None:
+        """Everything ``scene_masks`` refuses with ValueError, before any launch."""
+        p, S, K = self.plan.pipe, self.plan.n_scenes, self.plan.per_scene
+        if K > N.IPP_SCENE_MAP_MAX_LAYERS:
+            raise ValueError(f"SceneRunner.{caller}: {K} layers per scene, a visibility map holds at most "
+                             f"{N.IPP_SCENE_MAP_MAX_LAYERS} (one bit per layer)")
+        if out is None:
+            return
+        shape = (S, p.bg_h, scene_map_pitch(p.bg_w))
+        same_dev = isinstance(out, torch.Tensor) and out.device.type == self.device.type and \
+            self.device.index in (None, out.device.index)
+        if not same_dev or out.dtype != torch.uint8 or tuple(out.shape) != shape or not out.is_contiguous() or \
+                out.data_ptr() % 16:
+            raise ValueError(f"SceneRunner.{caller}: out must be a contiguous uint8 tensor {shape} on {self.device}, "
+                             f"16-B aligned (the row pitch is scene_map_pitch(bg_w))")
+
+    def _launch_map(self, caller: str, alpha_min: int, cover_min: int, with_boxes: bool,
+                    out: Optional[torch.Tensor]) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        """One ipp_pipe_scene_map call: the (S, bg_h, pitch) map buffer and, with
+        ``with_boxes``, the device rows in descriptor order."""
+        self._scene_scratch(caller)
+        p, S, K = self.plan.pipe, self.plan.n_scenes, self.plan.per_scene
+        n, pitch = S * K, scene_map_pitch(p.bg_w)
+        buf = out if out is not None else torch.empty((S, p.bg_h, pitch), dtype=torch.uint8, device=self.device)
+        rows = torch.empty(6 * n, dtype=torch.int32, device=self.device) if with_boxes else None
+        N.check(self.lib.ipp_pipe_scene_map(self.tmp.data_ptr(), self.coefs.data_ptr(), self._dptr(0),
+                                            self._scene_layer.data_ptr(), n, S, K, p.bg_w, p.bg_h, p.max_ov_w,
+                                            p.max_ov_h, alpha_min, cover_min, p.tap_format, self._scratch.data_ptr(),
+                                            rows.data_ptr() if with_boxes else None, buf.data_ptr(), pitch,
+                                            _stream(self.device)), "ipp_pipe_scene_map")
+        return buf, rows
 
     def _rows_by_scene(self, rows: torch.Tensor) -> np.ndarray:
         """Copy the rows back (synchronises): (S, K, 6) in scene, layer order."""
@@ -886,13 +976,42 @@ class SceneRunner:
         alpha_min, cover_min = _check_level("alpha_min", alpha_min), _check_level("cover_min", cover_min)
         return self._rows_by_scene(self._launch_boxes(alpha_min, cover_min))
 
+    def scene_masks(self, alpha_min: int = 1, cover_min: int = 128, with_boxes: bool = False,
+                    out: Optional[torch.Tensor] = None):
+        """The visibility maps of the batch (ipp_pipe_scene_map): a device uint8
+        tensor (S, bg_h, bg_w) in scene order (slot s belongs to composite
+        ``out[s]`` of ``run``), bit k of a byte set iff layer k of the scene is
+        visible at that pixel — alpha >= alpha_min and no later layer with alpha
+        >= cover_min there, the rule of ``scene_boxes``.  A byte may hold
+        several bits (``instance_ids`` keeps the topmost).  It is a view of an
+        (S, bg_h, pitch) buffer, pitch = ``scene_map_pitch(bg_w)``, whose padding
+        columns are 0; ``out`` supplies that buffer (contiguous CUDA uint8, any
+        contents: every byte is written).  It runs after ``run`` on the current
+        stream, stays on the device and does not synchronise.  With
+        ``with_boxes`` it returns (map, rows), rows = the (S, K, 6) array of
+        ``scene_boxes`` from the same alpha pass; that copy back synchronises.
+        Scenes of more than 8 layers are refused (ValueError)."""
+        alpha_min, cover_min = _check_level("alpha_min", alpha_min), _check_level("cover_min", cover_min)
+        self._check_map("scene_masks", out)
+        buf, rows = self._launch_map("scene_masks", alpha_min, cover_min, with_boxes, out)
+        vis = buf[:, :, :self.plan.bg_w]
+        return (vis, self._rows_by_scene(rows)) if with_boxes else vis
+
     def run_labelled(self, src: torch.Tensor, bgs: torch.Tensor, out: torch.Tensor, class_ids=0,
-                     alpha_min: int = 1, cover_min: int = 128,
-                     min_visible: float = 0.0) -> Tuple[torch.Tensor, List[List[str]]]:
+                     alpha_min: int = 1, cover_min: int = 128, min_visible: float = 0.0, masks: bool = False):
         """``run`` plus the YOLO lines of every scene (``scene_labels``):
         labels[s] lists scene s's lines in layer order, one per overlay with
-        visible > 0 and visible / area >= min_visible."""
+        visible > 0 and visible / area >= min_visible.  Returns (out, labels);
+        with ``masks`` (out, labels, map), the map of ``scene_masks`` from the
+        same launch as the boxes."""
         alpha_min, cover_min = _check_level("alpha_min", alpha_min), _check_level("cover_min", cover_min)
+        if masks:
+            self._check_map("run_labelled", None)
         self.run(src, bgs, out)
+        if masks:
+            buf, rows = self._launch_map("run_labelled", alpha_min, cover_min, True, None)
+            boxes = self._rows_by_scene(rows)
+            labels = scene_labels(boxes, self.plan.bg_w, self.plan.bg_h, class_ids, min_visible)
+            return out, labels, buf[:, :, :self.plan.bg_w]
         boxes = self._rows_by_scene(self._launch_boxes(alpha_min, cover_min))
         return out, scene_labels(boxes, self.plan.bg_w, self.plan.bg_h, class_ids, min_visible)

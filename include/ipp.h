@@ -338,6 +338,34 @@ int ipp_pipe_scene_boxes(const uint8_t* tmp, const int32_t* coefs, const ipp_pip
                          int32_t per_scene, int32_t max_ov_w, int32_t max_ov_h, int32_t alpha_min,
                          int32_t cover_min, int32_t tap_format, uint8_t* scratch, int32_t* out,
                          void* stream);
+/* Instance masks of scenes: the per-pixel answer of the rule above.  The
+ * VISIBILITY MAP of scene s is a uint8 image of bg_h rows of map_pitch bytes at
+ * map + s * bg_h * map_pitch.  Bit k of byte (Y, X) is 1 iff layer k of scene
+ * s is mapped by scene_layer and has a plane (ov_w <= max_ov_w and ov_h <=
+ * max_ov_h, as for the boxes), (X, Y) lies in its rectangle clipped to the
+ * bg_w x bg_h background, A_k >= alpha_min there, and every later layer j > k
+ * of the scene that has a plane and whose rectangle holds (X, Y) has A_j <
+ * cover_min there.  A byte may hold several bits (a faint upper layer is
+ * visible and does not cover the one below); with alpha_min > cover_min a
+ * pixel inside a rectangle may hold none.  Columns [bg_w, map_pitch) are 0, a
+ * scene slot without a descriptor is all 0, and the launch writes EVERY byte
+ * of all n_scenes slots (n_images == 0 included): the caller clears nothing.
+ * Per descriptor, the number of its bits in its scene's map is `visible` of
+ * ipp_pipe_scene_boxes and their bounding box is its (x0, y0, x1, y1).
+ * rows: NULL, or device int32[n_images][6] that receives exactly what
+ * ipp_pipe_scene_boxes writes to `out` (boxes and map from one alpha pass).
+ * scratch: as for ipp_pipe_scene_boxes (ipp_pipe_scene_scratch_bytes).  map:
+ * device, 16-B aligned; map_pitch >= bg_w, a multiple of 16, below 2^31.
+ * 1 <= per_scene <= IPP_SCENE_MAP_MAX_LAYERS: more layers are refused
+ * (IPP_E_ARG), not truncated.  Same place in the stream as the boxes: after
+ * the H launches, before tmp is refilled. */
+#define IPP_SCENE_MAP_MAX_LAYERS 8
+int ipp_pipe_scene_map(const uint8_t* tmp, const int32_t* coefs, const ipp_pipe_desc* descs,
+                       const int32_t* scene_layer, int32_t n_images, int32_t n_scenes, int32_t per_scene,
+                       int32_t bg_w, int32_t bg_h, int32_t max_ov_w, int32_t max_ov_h,
+                       int32_t alpha_min, int32_t cover_min, int32_t tap_format,
+                       uint8_t* scratch, int32_t* rows /* may be NULL */,
+                       uint8_t* map, int64_t map_pitch, void* stream);
 
 /* ------------------------------------------------------------------------ */
 /* K10-K13: pixels_isolés.keep_largest_component                             */

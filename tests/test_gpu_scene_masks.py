@@ -1,0 +1,316 @@
+"""GPU: per-pixel instance masks of scenes (ipp_pipe_scene_map /
+SceneRunner.scene_masks, run_labelled(masks=True)) on the inputs of
+tests/test_gpu_scenes.py.  Every map buffer is pre-filled with 0xA5 and handed
+in through ``out=``; the whole (S, bg_h, pitch) buffer, padding included, is
+compared byte for byte with the CPU restatement of the definition
+(tests/scene_mask_refs.scene_map), and its per-bit counts and boxes with the
+rows of ``scene_boxes`` from a separate call."""
+import numpy as np
+import pytest
+
+torch = pytest.importorskip("torch")
+
+from tests import label_refs as R
+from tests import scene_mask_refs as MR
+from tests import scene_refs as SR
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+POISON = 0xA5
+
+
+@pytest.fixture(scope="module")
+def fused():
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from image_processor_pipeline_amd import fused as F
+    return F
+
+
+def _t(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+
+
+class Scenes:
+    """One scene batch after its run, with the oracle's overlays and the reference maps."""
+
+    def __init__(self, fused, batch):
+        self.fused = fused
+        self.src, self.bgs, self.plan, self.cfg = batch
+        self.runner = fused.SceneRunner(self.plan, DEV)
+        self.dsrc, self.dbgs = _t(self.src), _t(self.bgs)
+        self.out = torch.full((self.plan.n_scenes,) + self.bgs.shape[1:], 77, dtype=torch.uint8, device=DEV)
+        self.runner.run(self.dsrc, self.dbgs, self.out)
+        self.overlays = SR.scene_overlays(self.src, self.plan, self.cfg)
+        self.shape = (self.plan.n_scenes, self.plan.bg_h, MR.pitch_of(self.plan.bg_w))
+        self._refs = {}
+
+    def ref(self, alpha_min, cover_min):
+        key = (alpha_min, cover_min)
+        if key not in self._refs:
+            self._refs[key] = MR.scene_map(self.plan, self.overlays, alpha_min, cover_min)
+            self._refs[key].setflags(write=False)
+        return self._refs[key]
+
+    def poisoned(self):
+        return torch.full(self.shape, POISON, dtype=torch.uint8, device=DEV)
+
+    def check(self, alpha_min, cover_min, with_boxes=False):
+        """scene_masks into a poisoned buffer: the whole buffer equals the
+        reference; returns the device buffer's copy (and the rows)."""
+        buf = self.poisoned()
+        got = self.runner.scene_masks(alpha_min, cover_min, with_boxes=with_boxes, out=buf)
+        vis, rows = got if with_boxes else (got, None)
+        assert vis.dtype == torch.uint8 and tuple(vis.shape) == self.shape[:2] + (self.plan.bg_w,)
+        assert vis.data_ptr() == buf.data_ptr() and vis.stride() == buf.stride()          # a view of `out`
+        host, exp = buf.cpu().numpy(), self.ref(alpha_min, cover_min)
+        assert np.array_equal(host, exp), (alpha_min, cover_min, int((host != exp).sum()))
+        return (host, rows) if with_boxes else host
+
+
+def _check_against_boxes(b, alpha_min, cover_min):
+    """With and without the rows; the rows are scene_boxes' own; the device
+    map has their counts and boxes."""
+    boxes = b.runner.scene_boxes(alpha_min, cover_min)
+    host = b.check(alpha_min, cover_min)
+    host2, rows = b.check(alpha_min, cover_min, with_boxes=True)
+    assert np.array_equal(host, host2)
+    assert rows.dtype == np.int32 and rows.shape == boxes.shape and rows.tobytes() == boxes.tobytes()
+    assert np.array_equal(MR.map_rows(host, b.plan.per_scene), boxes[..., [0, 1, 2, 3, 5]])
+    return host
+
+
+# --- 1: noise scenes ---------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def noise(fused):
+    return Scenes(fused, MR.noise_scenes(fused))
+
+
+@pytest.mark.parametrize("alpha_min,cover_min", MR.LEVELS)
+def test_noise_scenes(noise, alpha_min, cover_min):
+    host = _check_against_boxes(noise, alpha_min, cover_min)
+    if (alpha_min, cover_min) == (1, 128):
+        assert (np.unpackbits(host[..., None], axis=-1).sum(axis=-1) >= 2).any()
+        assert all(((host >> k) & 1).any() for k in range(3))
+
+
+def test_default_buffer_and_levels(noise):
+    """No ``out``: the runner allocates the pitched buffer; defaults (1, 128)."""
+    vis = noise.runner.scene_masks()
+    assert vis.is_cuda and tuple(vis.shape) == (4, 128, 160) and vis.stride() == (128 * 160, 160, 1)
+    assert np.array_equal(vis.cpu().numpy(), noise.ref(1, 128)[:, :, :160])
+    masks = noise.fused.scene_instance_masks(vis, noise.runner.scene_boxes())
+    exp = SR.scene_rows(noise.plan, noise.overlays, 1, 128)
+    for s in range(4):
+        for k in range(3):
+            assert (masks[s][k] is None) == (exp[s, k, 5] == 0)
+            if masks[s][k] is not None:
+                assert masks[s][k].shape == (exp[s, k, 3] - exp[s, k, 1], exp[s, k, 2] - exp[s, k, 0])
+                assert int(masks[s][k].sum()) == exp[s, k, 5]
+
+
+# --- 2: odd background: padding columns, a partial last band -------------------------------
+def test_odd_background(fused):
+    b = Scenes(fused, MR.odd_scenes(fused))
+    assert b.shape == (3, 97, 128) and b.plan.bg_w == 125
+    for a, c in MR.LEVELS:
+        host = _check_against_boxes(b, a, c)
+        assert not host[:, :, 125:].any()
+
+
+# --- 3: neighbours in one 16-pixel group and one 16-row band -------------------------------
+def test_neighbours_share_a_group_and_a_band(fused):
+    b = Scenes(fused, MR.neighbour_scenes(fused))
+    it = b.plan.items
+    x, y, w, h = (it[k].astype(int) for k in ("x", "y", "ov_w", "ov_h"))
+    assert x[1] == x[0] + w[0] and x[1] // 16 == (x[0] + w[0] - 1) // 16
+    assert y[3] == y[2] + h[2] and y[3] // 16 == (y[2] + h[2] - 1) // 16
+    host = _check_against_boxes(b, 1, 128)
+    assert (np.unpackbits(host[..., None], axis=-1).sum(axis=-1) <= 1).all()       # no byte holds two bits
+    assert (host == 1).any() and (host == 2).any()
+
+
+# --- 4: full, partial and faint cover --------------------------------------------------------
+def test_full_partial_and_faint_cover(fused):
+    b = Scenes(fused, MR.cover_scenes(fused))
+    host = _check_against_boxes(b, 1, 128)
+    assert not (host[0] & 1).any() and (host[0] & 2).any()                     # scene 0: bit 0 nowhere
+    assert (host[1] & 1).any() and (host[1] & 2).any()                         # scene 1: partly hidden
+    faint = b.overlays[5][..., 3]
+    assert 32 <= faint.max() < 128
+    line = np.zeros(host.shape[1:], bool)
+    line[20:20 + faint.shape[0], 30:30 + faint.shape[1]] = faint >= 32
+    assert (host[2][line] == 3).any()                                          # both bits under the faint line
+    low = _check_against_boxes(b, 1, 32)
+    assert not (low[2][line] & 1).any() and (low[2][line] & 2).all()           # bit 0 cleared under it
+
+
+# --- 5: overlays ending in the background's last row and column -------------------------------
+def test_overlays_in_the_last_row_and_column(fused):
+    b = Scenes(fused, MR.edge_scenes(fused))
+    it = b.plan.items
+    for i in (0, 3):
+        assert it["x"][i] + it["ov_w"][i] == 160 and it["y"][i] + it["ov_h"][i] == 128
+    host = _check_against_boxes(b, 1, 128)
+    assert host[0, 127, :160].any() and host[0, :, 159].any()                  # bits in the last row and column
+    assert host[1, 127, :160].any() and host[1, :, 159].any()
+
+
+# --- 6: eight layers; nine are refused ----------------------------------------------------------
+def test_eight_layers(fused):
+    b = Scenes(fused, MR.layered_scene(fused, 8))
+    for a, c in MR.LEVELS[:2]:
+        host = _check_against_boxes(b, a, c)
+        assert (host & 128).any()                                              # bit 7
+    ids = fused.instance_ids(b.runner.scene_masks())
+    assert ids.is_cuda and int(ids.max()) == 8
+    assert np.array_equal(ids.cpu().numpy(), fused.instance_ids(b.ref(1, 128)[:, :, :128]))
+
+
+def test_nine_layers_are_refused(fused):
+    from image_processor_pipeline_amd import _native as N
+    b = Scenes(fused, MR.layered_scene(fused, 9))
+    assert b.runner.scene_boxes().shape == (1, 9, 6)                           # the boxes have no such limit
+    buf = torch.full((1, 96, 128), POISON, dtype=torch.uint8, device=DEV)
+    with pytest.raises(ValueError):
+        b.runner.scene_masks(out=buf)
+    with pytest.raises(ValueError):
+        b.runner.scene_masks()
+    with pytest.raises(ValueError):
+        b.runner.run_labelled(b.dsrc, b.dbgs, b.out, masks=True)
+    r, p = b.runner, b.plan.pipe
+    assert N.load().ipp_pipe_scene_map(
+        r.tmp.data_ptr(), r.coefs.data_ptr(), r.descs.data_ptr(), r._scene_layer.data_ptr(), 9, 1, 9, p.bg_w, p.bg_h,
+        p.max_ov_w, p.max_ov_h, 1, 128, p.tap_format, r._scratch.data_ptr(), None, buf.data_ptr(), 128,
+        torch.cuda.current_stream().cuda_stream) == N.IPP_E_ARG
+    torch.cuda.synchronize()
+    assert bool((buf == POISON).all())
+
+
+# --- 7: one overlay per scene is the flat batch ----------------------------------------------------
+def test_one_overlay_per_scene(fused):
+    """The `small` batch of tests/test_gpu_labels.py: instance id > 0 has the
+    tight boxes of PipeRunner.overlay_bboxes, shifted to the paste position."""
+    cfg = fused.PipeConfig(margins=(0.05, 9, 0.1, 3))
+    src, bgs, pplan = R.noise_batch(fused, 10, 150, 170, 3, 128, 160, cfg, 7)
+    plan = fused.plan_scenes((150, 170), 10, 1, (128, 160), 3, cfg, seed=7)
+    assert plan.descs.tobytes() == pplan.descs.tobytes()
+    dsrc, dbgs = _t(src), _t(bgs)
+    out = torch.empty((10, 128, 160, 3), dtype=torch.uint8, device=DEV)
+    prun = fused.PipeRunner(pplan, DEV)
+    prun.run(dsrc, dbgs, out)
+    tight = prun.overlay_bboxes(1)
+    srun = fused.SceneRunner(plan, DEV)
+    srun.run(dsrc, dbgs, out)
+    buf = torch.full((10, 128, 160), POISON, dtype=torch.uint8, device=DEV)
+    ids = fused.instance_ids(srun.scene_masks(out=buf)).cpu().numpy()
+    assert set(np.unique(ids).tolist()) == {0, 1}
+    xy = np.stack([pplan.items["x"], pplan.items["y"]] * 2, axis=1)
+    assert (tight[:, 0] >= 0).all()
+    assert np.array_equal(np.stack([R.np_box(ids[s] > 0) for s in range(10)]), tight + xy)
+
+
+# --- 8: a layer without a plane ---------------------------------------------------------------------
+def test_a_layer_without_a_plane(noise):
+    from image_processor_pipeline_amd import _native as N
+    lib, r, p, plan = N.load(), noise.runner, noise.plan.pipe, noise.plan
+    n, mw = len(plan.descs), p.max_ov_w - 1
+    widest = [i for i, ov in enumerate(noise.overlays) if ov.shape[1] > mw]
+    assert widest and all(i % 3 > 0 for i in widest)                           # it is a later layer of its scene
+    nb = lib.ipp_pipe_scene_scratch_bytes(n, 4, 3, mw, p.max_ov_h)
+    assert nb == 256 + n * p.max_ov_h * MR.pitch_of(mw)
+    scratch = torch.full((nb,), POISON, dtype=torch.uint8, device=DEV)
+    sl = _t(plan.scene_layer)
+    buf = noise.poisoned()
+    rows = torch.full((6 * n,), 99, dtype=torch.int32, device=DEV)
+    N.check(lib.ipp_pipe_scene_map(r.tmp.data_ptr(), r.coefs.data_ptr(), r.descs.data_ptr(), sl.data_ptr(), n, 4, 3,
+                                   p.bg_w, p.bg_h, mw, p.max_ov_h, 1, 128, p.tap_format, scratch.data_ptr(),
+                                   rows.data_ptr(), buf.data_ptr(), 160, torch.cuda.current_stream().cuda_stream),
+            "ipp_pipe_scene_map")
+    host = buf.cpu().numpy()
+    exp = MR.scene_map(plan, noise.overlays, 1, 128, max_ov=(mw, p.max_ov_h))
+    assert np.array_equal(host, exp), int((host != exp).sum())
+    assert not np.array_equal(exp, noise.ref(1, 128))                          # the layers below show through
+    for i in widest:
+        assert not ((host[i // 3] >> (i % 3)) & 1).any()                       # it sets no bit
+    by_item = np.empty((n, 6), np.int32)
+    by_item[plan.desc_item] = rows.cpu().numpy().reshape(n, 6)
+    assert np.array_equal(MR.map_rows(host, 3), by_item.reshape(4, 3, 6)[..., [0, 1, 2, 3, 5]])
+
+
+# --- 9: run_labelled(masks=True) ---------------------------------------------------------------------
+def test_run_labelled_with_masks(noise):
+    ids = list(range(12))
+    out_a, out_b = torch.full_like(noise.out, 5), torch.full_like(noise.out, 6)
+    plain = noise.runner.run_labelled(noise.dsrc, noise.dbgs, out_a, class_ids=ids, min_visible=0.5)
+    assert len(plain) == 2
+    got_out, labels, vis = noise.runner.run_labelled(noise.dsrc, noise.dbgs, out_b, class_ids=ids, min_visible=0.5,
+                                                     masks=True)
+    assert got_out is out_b and torch.equal(out_b, out_a) and torch.equal(out_b, noise.out)
+    assert labels == plain[1] and len(labels) == 4
+    assert labels == noise.fused.scene_labels(SR.scene_rows(noise.plan, noise.overlays, 1, 128), 160, 128, ids, 0.5)
+    assert vis.is_cuda and tuple(vis.shape) == (4, 128, 160)
+    assert np.array_equal(vis.cpu().numpy(), noise.ref(1, 128)[:, :, :160])
+
+
+# --- 10: guards ----------------------------------------------------------------------------------------
+def test_guards(fused, noise):
+    from image_processor_pipeline_amd import _native as N
+    fresh = fused.SceneRunner(noise.plan, DEV)
+    buf = noise.poisoned()
+    with pytest.raises(N.NativeError):
+        fresh.scene_masks(out=buf)                                             # no H launch
+    bad_out = [torch.full((4, 128, 176), POISON, dtype=torch.uint8, device=DEV),          # wrong pitch
+               torch.full((3, 128, 160), POISON, dtype=torch.uint8, device=DEV),          # wrong shape
+               torch.full((4, 128, 160), POISON, dtype=torch.uint8, device=DEV).view(torch.int8),     # wrong dtype
+               torch.full((4, 128, 160), POISON, dtype=torch.uint8),                      # wrong device
+               torch.full((4, 128, 320), POISON, dtype=torch.uint8, device=DEV)[:, :, ::2]]     # not contiguous
+    for o in bad_out:
+        with pytest.raises(ValueError):
+            noise.runner.scene_masks(out=o)
+        assert bool((o.view(torch.uint8) == POISON).all())
+    for kw in (dict(alpha_min=0), dict(cover_min=256), dict(cover_min=1.5), dict(alpha_min=None)):
+        with pytest.raises(ValueError):
+            noise.runner.scene_masks(out=buf, **kw)
+        with pytest.raises(ValueError):
+            noise.runner.run_labelled(noise.dsrc, noise.dbgs, torch.empty_like(noise.out), masks=True, **kw)
+    torch.cuda.synchronize()
+    assert bool((buf == POISON).all())                                         # refused before any launch
+
+
+def test_c_entry_point_refuses_bad_arguments(noise):
+    from image_processor_pipeline_amd import _native as N
+    lib, r, p, plan = N.load(), noise.runner, noise.plan.pipe, noise.plan
+    n = len(plan.descs)
+    st = torch.cuda.current_stream().cuda_stream
+    nb = lib.ipp_pipe_scene_scratch_bytes(n, 4, 3, p.max_ov_w, p.max_ov_h)
+    scratch = torch.empty(nb + 16, dtype=torch.uint8, device=DEV)
+    sl = _t(plan.scene_layer)
+    buf = torch.full((4 * 128 * 160 + 16,), POISON, dtype=torch.uint8, device=DEV)
+    rows = torch.full((6 * n,), 99, dtype=torch.int32, device=DEV)
+    assert scratch.data_ptr() % 16 == 0 and buf.data_ptr() % 16 == 0
+    good = dict(tmp=r.tmp.data_ptr(), coefs=r.coefs.data_ptr(), descs=r.descs.data_ptr(), sl=sl.data_ptr(), n=n, S=4,
+                K=3, bw=p.bg_w, bh=p.bg_h, mw=p.max_ov_w, mh=p.max_ov_h, a=1, c=128, fmt=p.tap_format,
+                scratch=scratch.data_ptr(), rows=rows.data_ptr(), map=buf.data_ptr(), pitch=160)
+    bad = [dict(tmp=None), dict(coefs=None), dict(descs=None), dict(sl=None), dict(scratch=None), dict(map=None),
+           dict(a=0), dict(a=256), dict(c=0), dict(c=256), dict(fmt=0), dict(fmt=2),
+           dict(K=0), dict(K=9), dict(bw=0), dict(bh=0), dict(bw=-1), dict(bh=-1),
+           dict(pitch=144), dict(pitch=159), dict(pitch=168),                  # below bg_w; not a multiple of 16
+           dict(map=buf.data_ptr() + 8), dict(scratch=scratch.data_ptr() + 8),
+           dict(S=1 << 28)]                                                    # 8 row tiles × 2^28 scenes = 2^31 blocks
+    for kw in bad:
+        a = dict(good)
+        a.update(kw)
+        rc = lib.ipp_pipe_scene_map(a["tmp"], a["coefs"], a["descs"], a["sl"], a["n"], a["S"], a["K"], a["bw"],
+                                    a["bh"], a["mw"], a["mh"], a["a"], a["c"], a["fmt"], a["scratch"], a["rows"],
+                                    a["map"], a["pitch"], st)
+        assert rc == N.IPP_E_ARG, kw
+    torch.cuda.synchronize()
+    assert bool((buf == POISON).all()) and bool((rows == 99).all())            # nothing was launched
+    # rows may be NULL, and no descriptors at all still zeroes every slot
+    a = dict(good, rows=None, n=0)
+    assert lib.ipp_pipe_scene_map(a["tmp"], a["coefs"], a["descs"], a["sl"], 0, 4, 3, a["bw"], a["bh"], a["mw"],
+                                  a["mh"], 1, 128, a["fmt"], a["scratch"], None, a["map"], 160, st) == N.IPP_OK
+    torch.cuda.synchronize()
+    assert not bool(buf[:4 * 128 * 160].any()) and bool((buf[4 * 128 * 160:] == POISON).all())

@@ -6,9 +6,11 @@
 Workload: S scenes × K overlays of size² sources on size² backgrounds with the
 config-3 parameters (fused.PipeConfig()), against PipeRunner.run on the flat
 S·K-item batch of the same sources.  The two runs alternate step by step on
-one device; every time is taken with HIP events on the current stream.  A
-second series times each launch of the scene run and the label launch
-(ipp_pipe_scene_boxes) on their own.  Prints one JSON line."""
+one device; every time is taken with HIP events on the current stream.  The
+same steps time the label launch (ipp_pipe_scene_boxes) and the visibility-map
+launch (ipp_pipe_scene_map) without and with the boxes, one after the other.
+A second series times each launch of the scene run on its own.  Prints one
+JSON line."""
 import argparse
 import json
 import statistics
@@ -60,16 +62,26 @@ def main():
         b.record()
         return a, b
 
-    ms_flat, ms_scene, ms_label = [], [], []
+    # the visibility maps (at most 8 layers per scene): one buffer, written whole by every launch
+    with_map = K <= N.IPP_SCENE_MAP_MAX_LAYERS
+    vis = torch.empty((S, Z, fused.scene_map_pitch(Z)), dtype=torch.uint8, device=dev) if with_map else None
+
+    ms_flat, ms_scene, ms_label, ms_map, ms_both = [], [], [], [], []
     for step in range(args.warmup + args.steps):
         ef = timed(lambda: flat.run(src, bgs, out_flat))
         es = timed(lambda: scene.run(src, bgs, out_scene))
         el = timed(lambda: scene._launch_boxes(1, 128))
+        if with_map:
+            em = timed(lambda: scene._launch_map("scene_masks", 1, 128, False, vis))
+            eb = timed(lambda: scene._launch_map("scene_masks", 1, 128, True, vis))
         torch.cuda.synchronize(dev)
         if step >= args.warmup:
             ms_flat.append(ef[0].elapsed_time(ef[1]))
             ms_scene.append(es[0].elapsed_time(es[1]))
             ms_label.append(el[0].elapsed_time(el[1]))
+            if with_map:
+                ms_map.append(em[0].elapsed_time(em[1]))
+                ms_both.append(eb[0].elapsed_time(eb[1]))
 
     # per launch: the scene run's own sequence, an event pair around each launch
     p, lib, st = scene_plan.pipe, scene.lib, _stream(dev)
@@ -104,6 +116,9 @@ def main():
         "steps": args.steps, "warmup": args.warmup,
         "plan_host_ms": {"flat": round((t1 - t0) * 1e3, 1), "scenes": round((t2 - t1) * 1e3, 1)},
         "flat_step": summary(ms_flat), "scene_step": summary(ms_scene), "label_launch": summary(ms_label),
+        "map_launch": summary(ms_map) if with_map else None,
+        "boxes_and_map_launch": summary(ms_both) if with_map else None,
+        "map_bytes": int(vis.numel()) if with_map else 0,
         "scene_launches": {name: summary(v) for name, v in per.items()},
         "copy_read_bytes": {"flat": flat_plan.copy_read_bytes, "scenes": scene_plan.copy_read_bytes},
         "composite_bytes": {"flat": out_flat.numel(), "scenes": out_scene.numel()},
