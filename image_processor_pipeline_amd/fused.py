@@ -29,6 +29,9 @@ label each overlay by what no later layer covers (``ipp_pipe_scene_boxes``).
 ``SceneRunner.scene_masks`` keeps that rule's per-pixel answer: one visibility
 map per composite, bit k = layer k visible (``ipp_pipe_scene_map``;
 ``instance_ids`` and ``scene_instance_masks`` turn it into instance masks).
+``SceneRunner.scene_polygons`` traces each overlay's outer contour from that
+map on the device (``ipp_scene_contours``); ``scene_seg_labels`` formats the
+YOLO segmentation lines.
 """
 from __future__ import annotations
 
@@ -846,6 +849,63 @@ def scene_instance_masks(vis_map, rows) -> List[List[Optional[np.ndarray]]]:
     return out
 
 
+def scene_contour_capacity(plan) -> int:
+    """Default ``max_edges`` of ``SceneRunner.scene_polygons``: 8·(max_ov_w +
+    max_ov_h) rounded up to 256 — four times the 2(w + h) boundary edges of a
+    monotone outline filling the largest overlay's box."""
+    p = plan.pipe if hasattr(plan, "pipe") else plan
+    return (8 * (int(p.max_ov_w) + int(p.max_ov_h)) + 255) // 256 * 256
+
+
+def seg_label(class_id: int, poly, bg_w: int, bg_h: int) -> str:
+    """One YOLO segmentation line for the (V, 2) lattice polygon `poly` on a
+    bg_w×bg_h composite: the class, then x / bg_w and y / bg_h of every vertex,
+    in the number format of ``yolo_label``."""
+    poly = np.asarray(poly)
+    if poly.ndim != 2 or poly.shape[1] != 2 or len(poly) < 3:
+        raise ValueError(f"a polygon of shape {poly.shape}: (V >= 3, 2) expected")
+    return " ".join([str(class_id)] + [f"{int(x) / bg_w:.6f} {int(y) / bg_h:.6f}" for x, y in poly])
+
+
+def scene_seg_labels(polys, info, rows, bg_w: int, bg_h: int, class_ids=0, min_visible: float = 0.0) -> List[List[str]]:
+    """YOLO segmentation lines of every scene from what
+    ``SceneRunner.scene_polygons`` returns: labels[s] lists, in layer order,
+    one line (``seg_label``) per overlay that ``scene_labels`` gives a line —
+    visible > 0 and visible / area >= min_visible.  ``class_ids`` as there.
+    An overlay that would get a line but overflowed ``max_edges`` (header
+    flags bit 0) raises ValueError naming the ``max_edges`` it needs: a label
+    is never dropped or truncated."""
+    info, rows = np.asarray(info), np.asarray(rows)
+    if rows.ndim != 3 or rows.shape[2] != 6:
+        raise ValueError(f"rows of shape {rows.shape}: (scenes, layers, 6) expected")
+    S, K = rows.shape[:2]
+    if info.shape != (S, K, N.IPP_CONTOUR_HDR):
+        raise ValueError(f"info of shape {info.shape}: ({S}, {K}, {N.IPP_CONTOUR_HDR}) expected")
+    if len(polys) != S or any(len(p) != K for p in polys):
+        raise ValueError(f"polys does not hold {S} scenes of {K} overlays")
+    if isinstance(class_ids, (int, np.integer)):
+        ids = [int(class_ids)] * (S * K)
+    else:
+        ids = [int(c) for c in class_ids]
+        if len(ids) != S * K:
+            raise ValueError(f"{len(ids)} class ids for {S * K} overlays")
+    out: List[List[str]] = []
+    for s in range(S):
+        lines = []
+        for k in range(K):
+            area, vis = int(rows[s, k, 4]), int(rows[s, k, 5])
+            if not (vis > 0 and vis >= min_visible * area):
+                continue
+            if int(info[s, k, 7]) & 1:
+                raise ValueError(f"scene {s} layer {k}: its contour has {int(info[s, k, 0])} boundary edges, "
+                                 f"scene_polygons needs max_edges >= {int(info[s, k, 0])}")
+            if polys[s][k] is None:
+                raise ValueError(f"scene {s} layer {k}: {vis} visible pixels but no polygon")
+            lines.append(seg_label(ids[s * K + k], polys[s][k], bg_w, bg_h))
+        out.append(lines)
+    return out
+
+
 class SceneRunner:
     """Device-resident scene plan + scratch for repeated runs of one batch:
     2 + K launches on the current stream (2 when K = 1, the pipe's own)."""
@@ -860,6 +920,7 @@ class SceneRunner:
         self._hpass_done = False   # the H launches have filled tmp (scene_boxes needs it)
         self._scene_layer = None
         self._scratch = None
+        self._contour_scratch = None   # (max_edges, buffer) of scene_polygons
 
     def _check(self, caller: str, src: torch.Tensor, bgs: torch.Tensor, out: torch.Tensor) -> None:
         _check_gpu_u8("SceneRunner", caller, src, bgs, out)
@@ -997,21 +1058,96 @@ class SceneRunner:
         vis = buf[:, :, :self.plan.bg_w]
         return (vis, self._rows_by_scene(rows)) if with_boxes else vis
 
+    def _check_max_edges(self, caller: str, max_edges) -> int:
+        if max_edges is None:
+            return scene_contour_capacity(self.plan)
+        if isinstance(max_edges, bool) or not isinstance(max_edges, (int, np.integer)) or \
+                not 4 <= max_edges <= 1 << 22:
+            raise ValueError(f"SceneRunner.{caller}: max_edges {max_edges!r}: an integer in 4..2^22")
+        return int(max_edges)
+
+    def _polygons(self, buf: torch.Tensor, rows: torch.Tensor, max_edges: int):
+        """The tracer, the header copy-back, the pack and the packed copy-back
+        on the map and device rows of one ``_launch_map``: (polys, info), both
+        in scene, layer order.  Synchronises."""
+        p, S, K = self.plan.pipe, self.plan.n_scenes, self.plan.per_scene
+        n, lib, st = S * K, self.lib, _stream(self.device)
+        if self._contour_scratch is None or self._contour_scratch[0] != max_edges:
+            nb = lib.ipp_scene_contours_scratch_bytes(n, max_edges)
+            if nb < 0:
+                raise N.NativeError(f"ipp_scene_contours_scratch_bytes failed with code {nb}")
+            self._contour_scratch = (max_edges, torch.empty(int(nb), dtype=torch.uint8, device=self.device))
+        scratch = self._contour_scratch[1]
+        hdr = torch.empty(N.IPP_CONTOUR_HDR * n, dtype=torch.int32, device=self.device)
+        N.check(lib.ipp_scene_contours(buf.data_ptr(), buf.shape[2], p.bg_w, p.bg_h, rows.data_ptr(),
+                                       self._scene_layer.data_ptr(), n, S, K, max_edges, scratch.data_ptr(),
+                                       hdr.data_ptr(), st), "ipp_scene_contours")
+        by_desc = hdr.cpu().numpy().reshape(n, N.IPP_CONTOUR_HDR)      # synchronises
+        nv = by_desc[:, 3].astype(np.int64)
+        offsets = np.concatenate([[0], np.cumsum(nv)[:-1]]).astype(np.int64)
+        total = int(nv.sum())
+        packed = np.empty((0, 2), np.int32)
+        if total:
+            verts = torch.empty(2 * total, dtype=torch.int32, device=self.device)
+            N.check(lib.ipp_scene_contours_pack(scratch.data_ptr(), hdr.data_ptr(),
+                                                _to_dev(offsets, self.device).data_ptr(), n, max_edges,
+                                                verts.data_ptr(), st), "ipp_scene_contours_pack")
+            packed = verts.cpu().numpy().reshape(total, 2)
+        info = np.empty_like(by_desc)
+        info[self.plan.desc_item] = by_desc
+        polys: List[List[Optional[np.ndarray]]] = [[None] * K for _ in range(S)]
+        for d, item in enumerate(self.plan.desc_item.tolist()):
+            if nv[d]:
+                polys[item // K][item % K] = packed[offsets[d]:offsets[d] + nv[d]].copy()
+        return polys, info.reshape(S, K, N.IPP_CONTOUR_HDR)
+
+    def scene_polygons(self, alpha_min: int = 1, cover_min: int = 128, max_edges: Optional[int] = None):
+        """The outer contour of every overlay's visible pixels, traced on the
+        device from the visibility map (ipp_pipe_scene_map with boxes, then
+        ipp_scene_contours and ipp_scene_contours_pack; include/ipp.h states
+        the contour's definition).  Returns (polys, info, rows): polys[s][k] is
+        the (V, 2) int32 polygon of scene s, layer k in composite lattice
+        coordinates — the largest 8-connected visible part's outline, holes
+        not cut out — or None when the overlay has no visible pixel or has
+        more boundary edges than ``max_edges`` (default
+        ``scene_contour_capacity(plan)``); info is the (S, K, 8) headers
+        {n_edges, n_outer, n_holes, n_vertices, area2, start_x, start_y,
+        flags}, flags bit 0 = overflowed; rows is ``scene_boxes``' (S, K, 6)
+        from the same alpha pass.  Runs after ``run`` on the current stream;
+        only the headers and the packed vertices are copied back (it
+        synchronises).  Scenes of more than 8 layers are refused."""
+        alpha_min, cover_min = _check_level("alpha_min", alpha_min), _check_level("cover_min", cover_min)
+        self._check_map("scene_polygons", None)
+        max_edges = self._check_max_edges("scene_polygons", max_edges)
+        buf, rows = self._launch_map("scene_polygons", alpha_min, cover_min, True, None)
+        polys, info = self._polygons(buf, rows, max_edges)
+        return polys, info, self._rows_by_scene(rows)
+
     def run_labelled(self, src: torch.Tensor, bgs: torch.Tensor, out: torch.Tensor, class_ids=0,
-                     alpha_min: int = 1, cover_min: int = 128, min_visible: float = 0.0, masks: bool = False):
+                     alpha_min: int = 1, cover_min: int = 128, min_visible: float = 0.0, masks: bool = False,
+                     polygons: bool = False, max_edges: Optional[int] = None):
         """``run`` plus the YOLO lines of every scene (``scene_labels``):
         labels[s] lists scene s's lines in layer order, one per overlay with
         visible > 0 and visible / area >= min_visible.  Returns (out, labels);
         with ``masks`` (out, labels, map), the map of ``scene_masks`` from the
-        same launch as the boxes."""
+        same launch as the boxes.  With ``polygons`` the tuple gains, as its
+        last element, the segmentation lines of ``scene_seg_labels`` (polygons
+        of ``scene_polygons`` with ``max_edges``), traced from that same map
+        launch."""
         alpha_min, cover_min = _check_level("alpha_min", alpha_min), _check_level("cover_min", cover_min)
-        if masks:
+        if masks or polygons:
             self._check_map("run_labelled", None)
+        if polygons:
+            max_edges = self._check_max_edges("run_labelled", max_edges)
         self.run(src, bgs, out)
-        if masks:
+        if masks or polygons:
             buf, rows = self._launch_map("run_labelled", alpha_min, cover_min, True, None)
             boxes = self._rows_by_scene(rows)
             labels = scene_labels(boxes, self.plan.bg_w, self.plan.bg_h, class_ids, min_visible)
-            return out, labels, buf[:, :, :self.plan.bg_w]
+            res = (out, labels) + ((buf[:, :, :self.plan.bg_w],) if masks else ())
+            if polygons:
+                polys, info = self._polygons(buf, rows, max_edges)
+                res += (scene_seg_labels(polys, info, boxes, self.plan.bg_w, self.plan.bg_h, class_ids, min_visible),)
+            return res
         boxes = self._rows_by_scene(self._launch_boxes(alpha_min, cover_min))
         return out, scene_labels(boxes, self.plan.bg_w, self.plan.bg_h, class_ids, min_visible)

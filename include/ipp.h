@@ -367,6 +367,67 @@ int ipp_pipe_scene_map(const uint8_t* tmp, const int32_t* coefs, const ipp_pipe_
                        uint8_t* scratch, int32_t* rows /* may be NULL */,
                        uint8_t* map, int64_t map_pitch, void* stream);
 
+/* Polygons of scenes: the outer contour of each overlay's visible pixels,
+ * traced on the device from the visibility maps.  map, map_pitch, rows (device
+ * int32[n_images][6], descriptor order) and scene_layer are what
+ * ipp_pipe_scene_map takes and writes; only the map and the rows are read (not
+ * tmp), so this may run any time after the map launch on the same stream.
+ *
+ * For descriptor i = (scene s, layer k) the foreground F is the pixels of the
+ * half-open box rows[i][0:4] whose byte in scene s's map has bit k set;
+ * everything else is background.  Pixel (X, Y) is the unit square (X, Y) ..
+ * (X+1, Y+1), y down.  A BOUNDARY EDGE is a unit lattice edge between a pixel
+ * of F and one not in F, directed with F on its right: a foreground pixel's
+ * top edge runs +x, its right edge +y, its bottom edge -x, its left edge -y.
+ * The SUCCESSOR of an edge is the boundary edge leaving its head vertex, taken
+ * in the order left turn (from +x: -y), straight on, right turn: foreground is
+ * 8-connected and a contour crosses a saddle vertex to the diagonal pixel.
+ * Every edge has one successor and one predecessor: the edges split into
+ * directed cycles.  area2 of a cycle = sum over its edges of x_tail·y_head -
+ * x_head·y_tail; cycles with area2 > 0 are OUTER contours (one per 8-connected
+ * component, area2 / 2 = its pixels with its holes filled), those with area2 <
+ * 0 HOLES (one per 4-connected background region enclosed by F).  A cycle's
+ * START EDGE is its least top edge in (y, x) order (its tail is a corner).
+ * The CHOSEN cycle is the outer cycle of largest area2, ties to the lesser
+ * start edge.  The POLYGON is the chosen cycle's corner vertices — the tails
+ * of the edges whose direction differs from their predecessor's — in
+ * traversal order from the start edge's tail, not closed, a pinch vertex once
+ * per pass: an even number >= 4 of lattice points in 0..bg_w x 0..bg_h.
+ *
+ * hdr (device int32[n_images][IPP_CONTOUR_HDR]) receives {n_edges, n_outer,
+ * n_holes, n_vertices, area2, start_x, start_y, flags} per descriptor:
+ * n_edges = all its boundary edges; n_vertices, area2, start_x, start_y = the
+ * chosen cycle's.  A descriptor whose row is (-1,-1,-1,-1) (or whose box does
+ * not lie in the map) or that scene_layer does not map into n_scenes x
+ * per_scene gets all zeros.  Every word of every header is written.  A
+ * descriptor with n_edges > max_edges is REFUSED, not truncated: flags bit 0
+ * set, its true n_edges, every other word 0; it touches only its own scratch
+ * slot.  The results do not depend on the order of any atomic.
+ * scratch: device, 16-B aligned, ipp_scene_contours_scratch_bytes(n_images,
+ * max_edges) bytes = 32 B per descriptor (rounded up to 256 B in all) + 2
+ * arrays of n_images·max_edges edge records of 32 B (the ping-pong of the
+ * list ranking: ⌈log2 max_edges⌉ launches, one per round).
+ * IPP_E_ARG, before any launch: a NULL pointer; map or scratch not 16-B
+ * aligned; per_scene outside 1..IPP_SCENE_MAP_MAX_LAYERS; map_pitch < bg_w or
+ * not a multiple of 16; bg_w·bg_h >= 2^30 (area2 must fit int32); max_edges
+ * outside 4..2^22; n_images·⌈max_edges / 256⌉ >= 2^31 - 1 (the grid).
+ *
+ * ipp_scene_contours_pack, after it on the same stream with the same scratch
+ * and max_edges: writes descriptor i's polygon as n_vertices (x, y) int32
+ * pairs at verts + 2·offsets[i] (offsets: device int64[n_images], computed by
+ * the caller from the copied-back headers, e.g. the running sum of
+ * n_vertices, so the packed buffer is exactly as large as the polygons).  It
+ * writes nothing for a descriptor whose header has n_vertices == 0 or flags
+ * != 0, and nothing else. */
+#define IPP_CONTOUR_HDR 8
+int64_t ipp_scene_contours_scratch_bytes(int32_t n_images, int32_t max_edges);
+int ipp_scene_contours(const uint8_t* map, int64_t map_pitch, int32_t bg_w, int32_t bg_h,
+                       const int32_t* rows, const int32_t* scene_layer, int32_t n_images,
+                       int32_t n_scenes, int32_t per_scene, int32_t max_edges,
+                       uint8_t* scratch, int32_t* hdr, void* stream);
+int ipp_scene_contours_pack(const uint8_t* scratch, const int32_t* hdr, const int64_t* offsets,
+                            int32_t n_images, int32_t max_edges, int32_t* verts, void* stream);
+
 /* ------------------------------------------------------------------------ */
 /* K10-K13: pixels_isolés.keep_largest_component                             */
 /* :32 threshold(α,1,255) :35 connectedComponentsWithStats(8) :38-55 keep    */

@@ -8,8 +8,10 @@ config-3 parameters (fused.PipeConfig()), against PipeRunner.run on the flat
 S·K-item batch of the same sources.  The two runs alternate step by step on
 one device; every time is taken with HIP events on the current stream.  The
 same steps time the label launch (ipp_pipe_scene_boxes) and the visibility-map
-launch (ipp_pipe_scene_map) without and with the boxes, one after the other.
-A second series times each launch of the scene run on its own.  Prints one
+launch (ipp_pipe_scene_map) without and with the boxes, one after the other,
+then the contour tracer (ipp_scene_contours) and its pack launch
+(ipp_scene_contours_pack) on that map and those rows, with --max-edges slots
+per overlay (default fused.scene_contour_capacity).  A second series times each launch of the scene run on its own.  Prints one
 JSON line."""
 import argparse
 import json
@@ -30,6 +32,7 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--max-edges", type=int, default=0)
     args = ap.parse_args()
 
     import torch
@@ -66,15 +69,51 @@ def main():
     with_map = K <= N.IPP_SCENE_MAP_MAX_LAYERS
     vis = torch.empty((S, Z, fused.scene_map_pitch(Z)), dtype=torch.uint8, device=dev) if with_map else None
 
-    ms_flat, ms_scene, ms_label, ms_map, ms_both = [], [], [], [], []
+    # the contour tracer on the map and rows of the boxes-and-map launch; the pack's offsets come from the
+    # headers of the last step (the same every step: the inputs do not change)
+    import numpy as np
+    max_edges = args.max_edges or fused.scene_contour_capacity(scene_plan)
+    tracer = {}
+    if with_map:
+        nb = scene.lib.ipp_scene_contours_scratch_bytes(n, max_edges)
+        tracer = dict(scratch=torch.empty(int(nb), dtype=torch.uint8, device=dev),
+                      hdr=torch.zeros(N.IPP_CONTOUR_HDR * n, dtype=torch.int32, device=dev),
+                      offsets=torch.zeros(n, dtype=torch.int64, device=dev),
+                      verts=torch.empty(2, dtype=torch.int32, device=dev), rows=None)
+
+    def trace():
+        N.check(scene.lib.ipp_scene_contours(vis.data_ptr(), vis.shape[2], Z, Z, tracer["rows"].data_ptr(),
+                                             scene._scene_layer.data_ptr(), n, S, K, max_edges,
+                                             tracer["scratch"].data_ptr(), tracer["hdr"].data_ptr(), _stream(dev)),
+                "ipp_scene_contours")
+
+    def pack():
+        N.check(scene.lib.ipp_scene_contours_pack(tracer["scratch"].data_ptr(), tracer["hdr"].data_ptr(),
+                                                  tracer["offsets"].data_ptr(), n, max_edges,
+                                                  tracer["verts"].data_ptr(), _stream(dev)),
+                "ipp_scene_contours_pack")
+
+    ms_flat, ms_scene, ms_label, ms_map, ms_both, ms_trace, ms_pack = [], [], [], [], [], [], []
+    hdrs = None
     for step in range(args.warmup + args.steps):
         ef = timed(lambda: flat.run(src, bgs, out_flat))
         es = timed(lambda: scene.run(src, bgs, out_scene))
         el = timed(lambda: scene._launch_boxes(1, 128))
         if with_map:
             em = timed(lambda: scene._launch_map("scene_masks", 1, 128, False, vis))
-            eb = timed(lambda: scene._launch_map("scene_masks", 1, 128, True, vis))
+            eb = timed(lambda: tracer.__setitem__("rows", scene._launch_map("scene_masks", 1, 128, True, vis)[1]))
+            et = timed(trace)
+            if hdrs is not None:
+                ep = timed(pack)
         torch.cuda.synchronize(dev)
+        if with_map:
+            if hdrs is not None and step >= args.warmup:
+                ms_pack.append(ep[0].elapsed_time(ep[1]))
+            if hdrs is None:                  # the first step's headers size the packed buffer of all later steps
+                hdrs = tracer["hdr"].cpu().numpy().reshape(n, N.IPP_CONTOUR_HDR)
+                nv = hdrs[:, 3].astype(np.int64)
+                tracer["offsets"] = torch.from_numpy(np.concatenate([[0], np.cumsum(nv)[:-1]]).astype(np.int64)).to(dev)
+                tracer["verts"] = torch.empty(2 * max(int(nv.sum()), 1), dtype=torch.int32, device=dev)
         if step >= args.warmup:
             ms_flat.append(ef[0].elapsed_time(ef[1]))
             ms_scene.append(es[0].elapsed_time(es[1]))
@@ -82,6 +121,7 @@ def main():
             if with_map:
                 ms_map.append(em[0].elapsed_time(em[1]))
                 ms_both.append(eb[0].elapsed_time(eb[1]))
+                ms_trace.append(et[0].elapsed_time(et[1]))
 
     # per launch: the scene run's own sequence, an event pair around each launch
     p, lib, st = scene_plan.pipe, scene.lib, _stream(dev)
@@ -119,6 +159,12 @@ def main():
         "map_launch": summary(ms_map) if with_map else None,
         "boxes_and_map_launch": summary(ms_both) if with_map else None,
         "map_bytes": int(vis.numel()) if with_map else 0,
+        "contour_launch": summary(ms_trace) if with_map else None,
+        "contour_pack_launch": summary(ms_pack) if with_map and ms_pack else None,
+        "contours": None if hdrs is None else {
+            "max_edges": max_edges, "largest_n_edges": int(hdrs[:, 0].max()), "largest_n_vertices": int(hdrs[:, 3].max()),
+            "overflowed": int((hdrs[:, 7] & 1).sum()), "packed_bytes": int(8 * hdrs[:, 3].astype(np.int64).sum()),
+            "header_bytes": int(hdrs.nbytes), "scratch_bytes": int(tracer["scratch"].numel())},
         "scene_launches": {name: summary(v) for name, v in per.items()},
         "copy_read_bytes": {"flat": flat_plan.copy_read_bytes, "scenes": scene_plan.copy_read_bytes},
         "composite_bytes": {"flat": out_flat.numel(), "scenes": out_scene.numel()},
