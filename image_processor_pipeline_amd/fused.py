@@ -857,6 +857,21 @@ def scene_contour_capacity(plan) -> int:
     return (8 * (int(p.max_ov_w) + int(p.max_ov_h)) + 255) // 256 * 256
 
 
+SIMPLIFY_MAX_SIDE = 16384   # largest background side ipp_polygons_simplify takes (ipp.h: the overflow bounds)
+
+
+def simplify_tolerance(eps) -> int:
+    """``eps_q`` of ipp_polygons_simplify for a tolerance of `eps` pixels: a
+    real number that is a multiple of 0.25 in 0.25..1024 (the rule works in
+    exact quarter pixels).  Anything else raises ValueError."""
+    if isinstance(eps, (bool, np.bool_)) or not isinstance(eps, (int, float, np.integer, np.floating)):
+        raise ValueError(f"simplify tolerance {eps!r}: a real number of pixels expected")
+    q = float(eps) * 4.0
+    if not (q == q and 1.0 <= q <= 4096.0 and q == int(q)):
+        raise ValueError(f"simplify tolerance {eps!r}: a multiple of 0.25 in 0.25..1024 pixels expected")
+    return int(q)
+
+
 def seg_label(class_id: int, poly, bg_w: int, bg_h: int) -> str:
     """One YOLO segmentation line for the (V, 2) lattice polygon `poly` on a
     bg_w×bg_h composite: the class, then x / bg_w and y / bg_h of every vertex,
@@ -921,6 +936,7 @@ class SceneRunner:
         self._scene_layer = None
         self._scratch = None
         self._contour_scratch = None   # (max_edges, buffer) of scene_polygons
+        self._simplify_scratch = None  # buffer of scene_polygons(simplify=...), grown on demand
 
     def _check(self, caller: str, src: torch.Tensor, bgs: torch.Tensor, out: torch.Tensor) -> None:
         _check_gpu_u8("SceneRunner", caller, src, bgs, out)
@@ -1066,10 +1082,24 @@ class SceneRunner:
             raise ValueError(f"SceneRunner.{caller}: max_edges {max_edges!r}: an integer in 4..2^22")
         return int(max_edges)
 
-    def _polygons(self, buf: torch.Tensor, rows: torch.Tensor, max_edges: int):
+    def _check_simplify(self, caller: str, simplify) -> Optional[int]:
+        """``eps_q`` of a ``simplify`` tolerance (None: no simplification), refusing what the device would."""
+        if simplify is None:
+            return None
+        eps_q = simplify_tolerance(simplify)
+        p = self.plan.pipe
+        if p.bg_w > SIMPLIFY_MAX_SIDE or p.bg_h > SIMPLIFY_MAX_SIDE:
+            raise ValueError(f"SceneRunner.{caller}: simplify on a {p.bg_w}x{p.bg_h} background: bg_w and bg_h must "
+                             f"not exceed {SIMPLIFY_MAX_SIDE} (ipp_polygons_simplify's exact integer bounds)")
+        return eps_q
+
+    def _polygons(self, buf: torch.Tensor, rows: torch.Tensor, max_edges: int, eps_q: Optional[int] = None):
         """The tracer, the header copy-back, the pack and the packed copy-back
         on the map and device rows of one ``_launch_map``: (polys, info), both
-        in scene, layer order.  Synchronises."""
+        in scene, layer order.  Synchronises.  With ``eps_q`` the packed
+        vertices stay on the device: ipp_polygons_simplify, the counts'
+        copy-back, ipp_polygons_simplify_pack, and only the kept vertices
+        come back."""
         p, S, K = self.plan.pipe, self.plan.n_scenes, self.plan.per_scene
         n, lib, st = S * K, self.lib, _stream(self.device)
         if self._contour_scratch is None or self._contour_scratch[0] != max_edges:
@@ -1092,7 +1122,10 @@ class SceneRunner:
             N.check(lib.ipp_scene_contours_pack(scratch.data_ptr(), hdr.data_ptr(),
                                                 _to_dev(offsets, self.device).data_ptr(), n, max_edges,
                                                 verts.data_ptr(), st), "ipp_scene_contours_pack")
-            packed = verts.cpu().numpy().reshape(total, 2)
+            if eps_q is None:
+                packed = verts.cpu().numpy().reshape(total, 2)
+            else:
+                nv, offsets, packed = self._simplified(verts, offsets, hdr, total, eps_q)
         info = np.empty_like(by_desc)
         info[self.plan.desc_item] = by_desc
         polys: List[List[Optional[np.ndarray]]] = [[None] * K for _ in range(S)]
@@ -1101,7 +1134,32 @@ class SceneRunner:
                 polys[item // K][item % K] = packed[offsets[d]:offsets[d] + nv[d]].copy()
         return polys, info.reshape(S, K, N.IPP_CONTOUR_HDR)
 
-    def scene_polygons(self, alpha_min: int = 1, cover_min: int = 128, max_edges: Optional[int] = None):
+    def _simplified(self, verts: torch.Tensor, offsets: np.ndarray, hdr: torch.Tensor, total: int, eps_q: int):
+        """(counts, out_offsets, kept vertices (sum counts, 2)) of the packed device polygons."""
+        p, lib, st = self.plan.pipe, self.lib, _stream(self.device)
+        n = self.plan.n_scenes * self.plan.per_scene
+        nb = lib.ipp_polygons_simplify_scratch_bytes(n, total)
+        if nb < 0:
+            raise N.NativeError(f"ipp_polygons_simplify_scratch_bytes failed with code {nb}")
+        if self._simplify_scratch is None or self._simplify_scratch.numel() < nb:
+            self._simplify_scratch = torch.empty(int(nb), dtype=torch.uint8, device=self.device)
+        scratch = self._simplify_scratch
+        d_off = _to_dev(offsets, self.device)
+        counts = torch.empty(n, dtype=torch.int32, device=self.device)
+        N.check(lib.ipp_polygons_simplify(verts.data_ptr(), d_off.data_ptr(), hdr.data_ptr(), n, total, p.bg_w,
+                                          p.bg_h, eps_q, scratch.data_ptr(), counts.data_ptr(), st),
+                "ipp_polygons_simplify")
+        kept = counts.cpu().numpy().astype(np.int64)                   # synchronises
+        out_offsets = np.concatenate([[0], np.cumsum(kept)[:-1]]).astype(np.int64)
+        total_kept = int(kept.sum())
+        out = torch.empty(2 * max(total_kept, 1), dtype=torch.int32, device=self.device)
+        N.check(lib.ipp_polygons_simplify_pack(verts.data_ptr(), d_off.data_ptr(), hdr.data_ptr(), scratch.data_ptr(),
+                                               counts.data_ptr(), _to_dev(out_offsets, self.device).data_ptr(), n,
+                                               out.data_ptr(), st), "ipp_polygons_simplify_pack")
+        return kept, out_offsets, out[:2 * total_kept].cpu().numpy().reshape(total_kept, 2)
+
+    def scene_polygons(self, alpha_min: int = 1, cover_min: int = 128, max_edges: Optional[int] = None,
+                       simplify: Optional[float] = None):
         """The outer contour of every overlay's visible pixels, traced on the
         device from the visibility map (ipp_pipe_scene_map with boxes, then
         ipp_scene_contours and ipp_scene_contours_pack; include/ipp.h states
@@ -1115,30 +1173,42 @@ class SceneRunner:
         flags}, flags bit 0 = overflowed; rows is ``scene_boxes``' (S, K, 6)
         from the same alpha pass.  Runs after ``run`` on the current stream;
         only the headers and the packed vertices are copied back (it
-        synchronises).  Scenes of more than 8 layers are refused."""
+        synchronises).  Scenes of more than 8 layers are refused.  With
+        ``simplify`` = a tolerance in pixels (``simplify_tolerance``: a
+        multiple of 0.25) the polygons are simplified on the device by the
+        Douglas–Peucker rule of include/ipp.h (ipp_polygons_simplify): polys
+        holds the kept vertices, at least 3 each, info and rows are unchanged
+        (n_vertices stays the traced count), and the unsimplified vertices
+        never leave the device — the counts and the kept vertices do.
+        Backgrounds of more than 16384 pixels on a side are then refused."""
         alpha_min, cover_min = _check_level("alpha_min", alpha_min), _check_level("cover_min", cover_min)
         self._check_map("scene_polygons", None)
         max_edges = self._check_max_edges("scene_polygons", max_edges)
+        eps_q = self._check_simplify("scene_polygons", simplify)
         buf, rows = self._launch_map("scene_polygons", alpha_min, cover_min, True, None)
-        polys, info = self._polygons(buf, rows, max_edges)
+        polys, info = self._polygons(buf, rows, max_edges, eps_q)
         return polys, info, self._rows_by_scene(rows)
 
     def run_labelled(self, src: torch.Tensor, bgs: torch.Tensor, out: torch.Tensor, class_ids=0,
                      alpha_min: int = 1, cover_min: int = 128, min_visible: float = 0.0, masks: bool = False,
-                     polygons: bool = False, max_edges: Optional[int] = None):
+                     polygons: bool = False, max_edges: Optional[int] = None, simplify: Optional[float] = None):
         """``run`` plus the YOLO lines of every scene (``scene_labels``):
         labels[s] lists scene s's lines in layer order, one per overlay with
         visible > 0 and visible / area >= min_visible.  Returns (out, labels);
         with ``masks`` (out, labels, map), the map of ``scene_masks`` from the
         same launch as the boxes.  With ``polygons`` the tuple gains, as its
         last element, the segmentation lines of ``scene_seg_labels`` (polygons
-        of ``scene_polygons`` with ``max_edges``), traced from that same map
-        launch."""
+        of ``scene_polygons`` with ``max_edges`` and ``simplify``), traced from
+        that same map launch.  ``simplify`` without ``polygons`` is refused."""
         alpha_min, cover_min = _check_level("alpha_min", alpha_min), _check_level("cover_min", cover_min)
+        if simplify is not None and not polygons:
+            raise ValueError("SceneRunner.run_labelled: simplify needs polygons=True")
         if masks or polygons:
             self._check_map("run_labelled", None)
+        eps_q = None
         if polygons:
             max_edges = self._check_max_edges("run_labelled", max_edges)
+            eps_q = self._check_simplify("run_labelled", simplify)
         self.run(src, bgs, out)
         if masks or polygons:
             buf, rows = self._launch_map("run_labelled", alpha_min, cover_min, True, None)
@@ -1146,7 +1216,7 @@ class SceneRunner:
             labels = scene_labels(boxes, self.plan.bg_w, self.plan.bg_h, class_ids, min_visible)
             res = (out, labels) + ((buf[:, :, :self.plan.bg_w],) if masks else ())
             if polygons:
-                polys, info = self._polygons(buf, rows, max_edges)
+                polys, info = self._polygons(buf, rows, max_edges, eps_q)
                 res += (scene_seg_labels(polys, info, boxes, self.plan.bg_w, self.plan.bg_h, class_ids, min_visible),)
             return res
         boxes = self._rows_by_scene(self._launch_boxes(alpha_min, cover_min))

@@ -428,6 +428,78 @@ int ipp_scene_contours(const uint8_t* map, int64_t map_pitch, int32_t bg_w, int3
 int ipp_scene_contours_pack(const uint8_t* scratch, const int32_t* hdr, const int64_t* offsets,
                             int32_t n_images, int32_t max_edges, int32_t* verts, void* stream);
 
+/* Simplification of the packed polygons on the device: line-distance
+ * Douglas–Peucker, this project's own normative definition in exact integers.
+ *
+ * INPUT.  A ring P[0..n-1] of lattice points, not closed.  For traced polygons
+ * this is the chosen cycle's corner vertices, P[0] being the start vertex.
+ * Let P[n] = P[0].
+ * TOLERANCE.  eps_q is an integer in quarter pixels, eps = eps_q / 4, with
+ * 1 <= eps_q <= 4096.
+ * OVERFLOW BOUNDS.  All arithmetic is exact integer.  Coordinates must lie in
+ * 0..16384 on both axes: the entry takes bg_w and bg_h and returns IPP_E_ARG
+ * when either exceeds 16384.  With those bounds |cross| <= 2^28, 16·cross² <=
+ * 2^60 and eps_q²·len² <= 2^53, so 64-bit unsigned arithmetic suffices (a
+ * measure fits 32 bits).  The coordinate range is the CALLER'S CONTRACT: bg_w
+ * and bg_h are checked, the vertices (device data) are not.  Vertices outside
+ * 0..16384 give an unspecified selection (the LDS path packs x and y into 16
+ * bits each), but no access outside the rings, the scratch and counts.
+ * ANCHORS.  A = 0.  B is the index in 1..n-1 with the largest squared
+ * Euclidean distance from P[0], ties to the least index.  Both anchors are
+ * kept.  The two chains are indices A..B and B..n.
+ * SPLIT of a segment (a, b), b > a + 1.  For each interior j, cross_j =
+ * (P[b]-P[a]) × (P[j]-P[a]) and len2 = |P[b]-P[a]|².  The measure m_j is
+ * |cross_j| when len2 > 0; when len2 = 0 it is |P[j]-P[a]|² (a pinch vertex
+ * visited twice).  The candidate is the j of largest m_j, ties to the least
+ * j.  It is kept, and both halves (a, j) and (j, b) are split in turn, iff
+ * 16·cross_j² > eps_q²·len2; when len2 = 0 the condition is 16·m_j > eps_q².
+ * Otherwise every interior vertex of the segment is dropped.
+ * AT LEAST A TRIANGLE.  If only A and B are kept after both chains, the vertex
+ * of largest |cross| against (A, B) over the whole ring is also kept, ties to
+ * the least index, provided that value is non-zero.  A traced polygon has
+ * positive area, so it always ends with at least 3 vertices.
+ * OUTPUT.  The kept vertices in ring order from P[0].  A ring with n < 3 is
+ * returned whole.
+ * EQUIVALENCE.  Each segment's split depends on that segment alone, so "split
+ * every open segment once per round until none is open" gives exactly the
+ * recursive result; the device works level by level.
+ *
+ * ipp_polygons_simplify: verts, offsets and hdr are exactly what
+ * ipp_scene_contours_pack took and wrote (ring i = hdr[i].n_vertices pairs at
+ * verts + 2·offsets[i]); it runs on the same stream after the pack.  The rings
+ * must be disjoint and lie below total_vertices: offsets[i] + n_vertices <=
+ * total_vertices (the scratch is indexed like verts).  counts (device
+ * int32[n_images]) receives the kept vertices of every descriptor, 0 where the
+ * header has n_vertices == 0 or flags != 0; every word of counts is written.
+ * Each vertex's keep mark is left in the scratch: uint32 at scratch + 4·(
+ * offsets[i] + j), 0 = dropped, else 1 + its position among the ring's kept.
+ * One workgroup per ring; a ring of at most IPP_SIMPLIFY_LDS_VERTS vertices
+ * keeps its state in LDS, a longer one (the tracer emits up to max_edges) runs
+ * the same rounds on the scratch: never refused, never truncated.  The only
+ * atomics are integer max: the results do not depend on their order.
+ * scratch: device, 16-B aligned, ipp_polygons_simplify_scratch_bytes(n_images,
+ * total_vertices) = 4·total_vertices rounded up to 256 B (the marks) + 16 B
+ * per vertex (the long rings' slot, a and b arrays).
+ * ipp_polygons_simplify_pack, after it on the same stream with the same
+ * arguments: writes descriptor i's kept vertices, in order, as counts[i] int32
+ * pairs at out + 2·out_offsets[i] (out_offsets: device int64[n_images], computed
+ * by the caller from the copied-back counts, so the final buffer is exactly as
+ * large as the simplified polygons), and nothing else.
+ * IPP_E_ARG, before any launch: a NULL pointer; scratch not 16-B, offsets or
+ * out_offsets not 8-B, another pointer not 4-B aligned; eps_q outside 1..4096;
+ * bg_w or bg_h outside 1..16384; n_images or total_vertices negative;
+ * n_images >= 2^24 (the grid: 256 threads per ring below 2^32 threads);
+ * total_vertices > 2^40. */
+#define IPP_SIMPLIFY_LDS_VERTS 2048
+#define IPP_SIMPLIFY_THREADS 256 /* threads of a ring's workgroup: thread t owns vertices t, t + 256, ... */
+int64_t ipp_polygons_simplify_scratch_bytes(int32_t n_images, int64_t total_vertices);
+int ipp_polygons_simplify(const int32_t* verts, const int64_t* offsets, const int32_t* hdr, int32_t n_images,
+                          int64_t total_vertices, int32_t bg_w, int32_t bg_h, int32_t eps_q, uint8_t* scratch,
+                          int32_t* counts, void* stream);
+int ipp_polygons_simplify_pack(const int32_t* verts, const int64_t* offsets, const int32_t* hdr,
+                               const uint8_t* scratch, const int32_t* counts, const int64_t* out_offsets,
+                               int32_t n_images, int32_t* out, void* stream);
+
 /* ------------------------------------------------------------------------ */
 /* K10-K13: pixels_isolés.keep_largest_component                             */
 /* :32 threshold(α,1,255) :35 connectedComponentsWithStats(8) :38-55 keep    */

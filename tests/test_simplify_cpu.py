@@ -1,0 +1,196 @@
+"""CPU: the polygon simplification's rule (include/ipp.h, ipp_polygons_simplify).
+The recursive reference of tests/simplify_refs.py against its level-by-level
+restatement (the equivalence the device relies on), the rule's properties in
+exact integers, the tolerance guard, the ABI and the kernels' resources."""
+import ctypes
+import math
+import os
+import re
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+from tests import contour_refs as C
+from tests import simplify_refs as R
+
+ROOT = Path(__file__).resolve().parents[1]
+HANDMADE = C.handmade()
+
+
+def _random_masks(count=200, seed=411):
+    rng = np.random.default_rng(seed)
+    for _ in range(count):
+        h, w = int(rng.integers(3, 25)), int(rng.integers(3, 25))
+        yield rng.random((h, w)) < rng.choice([0.35, 0.55, 0.8])
+
+
+@pytest.fixture(scope="module")
+def traced_rings():
+    rings = []
+    for fg in _random_masks():
+        _, poly, _ = C.trace(fg)
+        if poly is not None:
+            rings.append(poly)
+    assert len(rings) >= 190
+    return rings
+
+
+@pytest.fixture(scope="module")
+def handmade_rings():
+    out = []
+    for case in HANDMADE:
+        _, polys, _ = case.ref()
+        out += [(case.name, p) for p in polys if p is not None]
+    return out
+
+
+# --- 1: the level-by-level form is the recursive one ---------------------------------------------------------
+def test_levels_equal_recursion_on_traced_masks(traced_rings):
+    for ring in traced_rings:
+        for eps_q in (1, 4, 6, 16):
+            assert R.simplify_levels(ring, eps_q)[0] == R.simplify(ring, eps_q)
+
+
+def test_levels_equal_recursion_on_small_rings():
+    deep = 0
+    for k, ring in enumerate(R.random_small_rings()):
+        eps_q = R.EPS_QS[k % 4]
+        got, rounds = R.simplify_levels(ring, eps_q)
+        assert got == R.simplify(ring, eps_q), (k, ring.tolist())
+        deep = max(deep, rounds)
+    assert deep >= 4
+    for ring in R.degenerate_rings() + R.extreme_rings():
+        for eps_q in R.EPS_QS:
+            assert R.simplify_levels(ring, eps_q)[0] == R.simplify(ring, eps_q), ring.tolist()
+
+
+# --- 2: properties --------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("eps_q", R.EPS_QS)
+def test_properties(traced_rings, handmade_rings, eps_q):
+    rings = traced_rings + [p for _, p in handmade_rings]
+    for ring in rings:
+        kept = R.simplify(ring, eps_q)
+        assert kept[0] == 0 and kept == sorted(set(kept)) and kept[-1] < len(ring)     # an ordered subset from P[0]
+        assert R.spanning_error_ok(ring, kept, eps_q)
+        assert len(kept) >= 3                                                          # a traced ring has area
+    # arbitrary rings: the triangle's apex is added after the split and moves the spans of what the
+    # chains dropped, so the error bound is the chains' own
+    for ring in R.random_small_rings(300, seed=5) + R.extreme_rings():
+        kept = R.simplify(ring, eps_q)
+        assert kept[0] == 0 and kept == sorted(set(kept))
+        assert R.spanning_error_ok(ring, R.simplify(ring, eps_q, triangle=False), eps_q)
+    if eps_q == 4096:
+        for name, ring in handmade_rings:
+            assert len(R.simplify(ring, eps_q)) == 3, name                             # 1024 px: nothing splits
+
+
+def test_both_anchors_are_kept_at_every_tolerance(handmade_rings):
+    for _, ring in handmade_rings:
+        B = R.anchor_b([tuple(int(v) for v in p) for p in ring])
+        for eps_q in R.EPS_QS:
+            assert {0, B} <= set(R.simplify(ring, eps_q))
+
+
+def test_unit_square_by_hand():
+    """The single pixel's outline: its two off-diagonal corners lie 0.707 px from the diagonal (A, B)."""
+    sq = np.array([(5, 9), (6, 9), (6, 10), (5, 10)], np.int32)
+    assert R.simplify(sq, 1) == [0, 1, 2, 3]
+    assert R.simplify(sq, 2) == [0, 1, 2, 3]           # the corners are 0.707 px from the diagonal
+    assert R.simplify(sq, 3) == [0, 1, 2]              # 0.75 px: the diagonal's first corner is the triangle's apex
+
+
+def test_pinch_and_degenerate_rings():
+    pinch = R.pinch_ring()
+    assert (pinch[0] == pinch[4]).all()
+    assert R.simplify(pinch, 1) == list(range(8))
+    assert len(R.simplify(pinch, 4096)) == 3
+    same = np.array([(1, 1)] * 4, np.int32)
+    assert R.simplify(same, 1) == [0, 1]               # len2 = 0 on both chains, every measure 0, no triangle
+    line = np.array([(0, 0), (2, 2), (4, 4), (3, 3), (1, 1)], np.int32)
+    assert R.simplify(line, 1) == [0, 2]
+    assert R.simplify(np.array([(5, 7), (9, 1)], np.int32), 4) == [0, 1]
+    assert R.simplify(np.array([(5, 7)], np.int32).reshape(1, 2), 4) == [0]
+
+
+def test_comb_has_four_vertices_per_tooth():
+    for teeth in (2, 5, 64):
+        _, poly, _ = C.trace(R.comb(teeth))
+        assert len(poly) == 4 * teeth
+
+
+# --- 3: the tolerance guard ---------------------------------------------------------------------------------------
+def test_simplify_tolerance_guards():
+    from image_processor_pipeline_amd import fused
+    assert fused.simplify_tolerance(0.25) == 1 and fused.simplify_tolerance(1) == 4
+    assert fused.simplify_tolerance(1.5) == 6 and fused.simplify_tolerance(1024) == 4096
+    assert fused.simplify_tolerance(np.float32(2.75)) == 11 and fused.simplify_tolerance(np.int64(3)) == 12
+    for bad in (True, False, None, "1.0", 0, 0.0, -1.0, 0.1, 0.3, 1024.25, 2048, math.nan, math.inf, -math.inf,
+                [1.0], 1 + 0j, np.bool_(True)):
+        with pytest.raises(ValueError):
+            fused.simplify_tolerance(bad)
+
+
+def test_large_backgrounds_are_refused_by_name():
+    """The check scene_polygons and run_labelled make before any launch, on a stand-in for the runner."""
+    from types import SimpleNamespace as NS
+    from image_processor_pipeline_amd import fused
+    check = fused.SceneRunner._check_simplify
+    ok = NS(plan=NS(pipe=NS(bg_w=16384, bg_h=16384)))
+    assert check(ok, "scene_polygons", None) is None and check(ok, "scene_polygons", 1.0) == 4
+    for w, h in ((16385, 100), (100, 16385)):
+        big = NS(plan=NS(pipe=NS(bg_w=w, bg_h=h)))
+        assert check(big, "scene_polygons", None) is None                      # not asked for: nothing to refuse
+        with pytest.raises(ValueError, match="16384"):
+            check(big, "scene_polygons", 1.0)
+
+
+# --- 4: the ABI ----------------------------------------------------------------------------------------------------
+NAMES = ("ipp_polygons_simplify_scratch_bytes", "ipp_polygons_simplify", "ipp_polygons_simplify_pack")
+
+
+def test_library_exports_and_binds_the_entries():
+    from image_processor_pipeline_amd import _native as N
+    if not Path(N.LIB_PATH).exists():
+        pytest.skip("libipp.so is not built")
+    header = (ROOT / "include" / "ipp.h").read_text()
+    raw = ctypes.CDLL(str(N.LIB_PATH))
+    lib = N.load()
+    for name in NAMES:
+        assert re.search(r"\b" + name + r"\s*\(", header), name
+        assert hasattr(raw, name), name
+        assert name in N.SIGNATURES and getattr(lib, name).argtypes == N.SIGNATURES[name][1]
+    lds = int(re.search(r"#define IPP_SIMPLIFY_LDS_VERTS (\d+)", header).group(1))
+    assert lds == N.IPP_SIMPLIFY_LDS_VERTS
+    assert int(re.search(r"#define IPP_SIMPLIFY_THREADS (\d+)", header).group(1)) == N.IPP_SIMPLIFY_THREADS
+    # the size entries run on the host: the documented formula, and the guards
+    f = lib.ipp_polygons_simplify_scratch_bytes
+    for total in (0, 1, 63, 64, 65, 100000):
+        assert f(3, total) == (4 * total + 255) // 256 * 256 + 16 * total
+    assert f(-1, 10) == N.IPP_E_ARG and f(3, -1) == N.IPP_E_ARG and f(1 << 24, 10) == N.IPP_E_ARG
+    assert f(3, (1 << 40) + 1) == N.IPP_E_ARG and f(3, 1 << 40) == 20 << 40
+
+
+# --- 5: the kernels' resources ---------------------------------------------------------------------------------
+def test_simplify_kernels_no_spills_no_private_segment(tmp_path):
+    from tests.test_scene_kernel_resources import HIPCC, LDS_MAX, _kernels
+    if not os.path.exists(HIPCC):
+        pytest.skip("hipcc not available")
+    want = ("k_simplify_pack", "k_simplify")
+    ks, _ = _kernels("ipp_simplify", tmp_path)
+    seen = {}
+    for k in ks:
+        name = k.get("name") or ""
+        hit = [w for w in want if w in name]
+        if not hit:
+            continue
+        seen[hit[0]] = k
+        assert int(k.get("vgpr_spill_count", 0)) == 0, name
+        assert int(k.get("sgpr_spill_count", 0)) == 0, name
+        assert int(k.get("private_segment_fixed_size", 0)) == 0, name
+        assert int(k.get("group_segment_fixed_size", 0)) <= LDS_MAX, name
+    assert set(seen) == set(want)
+    # the LDS ring: 20 B per vertex (points, a, b, the 64-bit slot) and a few words of block state
+    from image_processor_pipeline_amd import _native as N
+    lds = int(seen["k_simplify"]["group_segment_fixed_size"])
+    assert 20 * N.IPP_SIMPLIFY_LDS_VERTS <= lds <= 20 * N.IPP_SIMPLIFY_LDS_VERTS + 512

@@ -1,7 +1,7 @@
 """Scene batch against the flat batch of the same overlays ("Scenes").
 
     python tools/scene_probe.py [--scenes 1024] [--per-scene 4] [--size 1024] [--backgrounds 16]
-                                [--steps 20] [--warmup 3] [--seed 0]
+                                [--steps 20] [--warmup 3] [--seed 0] [--simplify EPS]
 
 Workload: S scenes × K overlays of size² sources on size² backgrounds with the
 config-3 parameters (fused.PipeConfig()), against PipeRunner.run on the flat
@@ -11,7 +11,11 @@ same steps time the label launch (ipp_pipe_scene_boxes) and the visibility-map
 launch (ipp_pipe_scene_map) without and with the boxes, one after the other,
 then the contour tracer (ipp_scene_contours) and its pack launch
 (ipp_scene_contours_pack) on that map and those rows, with --max-edges slots
-per overlay (default fused.scene_contour_capacity).  A second series times each launch of the scene run on its own.  Prints one
+per overlay (default fused.scene_contour_capacity).  With --simplify EPS (pixels)
+the same steps time the simplification of those packed polygons
+(ipp_polygons_simplify) and its pack launch (ipp_polygons_simplify_pack) next
+to the tracer's, and the report gains the vertices before and after and the
+bytes copied back.  A second series times each launch of the scene run on its own.  Prints one
 JSON line."""
 import argparse
 import json
@@ -33,6 +37,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--max-edges", type=int, default=0)
+    ap.add_argument("--simplify", type=float, default=None, metavar="EPS")
     args = ap.parse_args()
 
     import torch
@@ -93,8 +98,27 @@ def main():
                                                   tracer["verts"].data_ptr(), _stream(dev)),
                 "ipp_scene_contours_pack")
 
+    # the simplification of the packed polygons; its scratch and the counts are sized with the packed buffer,
+    # the second pack's offsets come from the counts of the step after (the same every step)
+    eps_q = None if args.simplify is None else fused.simplify_tolerance(args.simplify)
+    simp = {}
+
+    def simplify():
+        N.check(scene.lib.ipp_polygons_simplify(tracer["verts"].data_ptr(), tracer["offsets"].data_ptr(),
+                                                tracer["hdr"].data_ptr(), n, simp["total"], Z, Z, eps_q,
+                                                simp["scratch"].data_ptr(), simp["counts"].data_ptr(), _stream(dev)),
+                "ipp_polygons_simplify")
+
+    def simplify_pack():
+        N.check(scene.lib.ipp_polygons_simplify_pack(tracer["verts"].data_ptr(), tracer["offsets"].data_ptr(),
+                                                     tracer["hdr"].data_ptr(), simp["scratch"].data_ptr(),
+                                                     simp["counts"].data_ptr(), simp["out_offsets"].data_ptr(), n,
+                                                     simp["out"].data_ptr(), _stream(dev)),
+                "ipp_polygons_simplify_pack")
+
     ms_flat, ms_scene, ms_label, ms_map, ms_both, ms_trace, ms_pack = [], [], [], [], [], [], []
-    hdrs = None
+    ms_simp, ms_simp_pack = [], []
+    hdrs = kept = None
     for step in range(args.warmup + args.steps):
         ef = timed(lambda: flat.run(src, bgs, out_flat))
         es = timed(lambda: scene.run(src, bgs, out_scene))
@@ -105,15 +129,32 @@ def main():
             et = timed(trace)
             if hdrs is not None:
                 ep = timed(pack)
+                if eps_q is not None:
+                    ey = timed(simplify)
+                    if kept is not None:
+                        ez = timed(simplify_pack)
         torch.cuda.synchronize(dev)
         if with_map:
             if hdrs is not None and step >= args.warmup:
                 ms_pack.append(ep[0].elapsed_time(ep[1]))
+                if eps_q is not None:
+                    ms_simp.append(ey[0].elapsed_time(ey[1]))
+                    if kept is not None:
+                        ms_simp_pack.append(ez[0].elapsed_time(ez[1]))
+            if hdrs is not None and eps_q is not None and kept is None:
+                kept = simp["counts"].cpu().numpy().astype(np.int64)
+                simp["out_offsets"] = torch.from_numpy(np.concatenate([[0], np.cumsum(kept)[:-1]]).astype(np.int64)).to(dev)
+                simp["out"] = torch.empty(2 * max(int(kept.sum()), 1), dtype=torch.int32, device=dev)
             if hdrs is None:                  # the first step's headers size the packed buffer of all later steps
                 hdrs = tracer["hdr"].cpu().numpy().reshape(n, N.IPP_CONTOUR_HDR)
                 nv = hdrs[:, 3].astype(np.int64)
                 tracer["offsets"] = torch.from_numpy(np.concatenate([[0], np.cumsum(nv)[:-1]]).astype(np.int64)).to(dev)
                 tracer["verts"] = torch.empty(2 * max(int(nv.sum()), 1), dtype=torch.int32, device=dev)
+                if eps_q is not None:
+                    simp["total"] = int(nv.sum())
+                    nb = scene.lib.ipp_polygons_simplify_scratch_bytes(n, simp["total"])
+                    simp["scratch"] = torch.empty(max(int(nb), 16), dtype=torch.uint8, device=dev)
+                    simp["counts"] = torch.zeros(n, dtype=torch.int32, device=dev)
         if step >= args.warmup:
             ms_flat.append(ef[0].elapsed_time(ef[1]))
             ms_scene.append(es[0].elapsed_time(es[1]))
@@ -165,6 +206,13 @@ def main():
             "max_edges": max_edges, "largest_n_edges": int(hdrs[:, 0].max()), "largest_n_vertices": int(hdrs[:, 3].max()),
             "overflowed": int((hdrs[:, 7] & 1).sum()), "packed_bytes": int(8 * hdrs[:, 3].astype(np.int64).sum()),
             "header_bytes": int(hdrs.nbytes), "scratch_bytes": int(tracer["scratch"].numel())},
+        "simplify_launch": summary(ms_simp) if ms_simp else None,
+        "simplify_pack_launch": summary(ms_simp_pack) if ms_simp_pack else None,
+        "simplify": None if kept is None else {
+            "eps_px": args.simplify, "eps_q": eps_q, "vertices_before": int(hdrs[:, 3].astype(np.int64).sum()),
+            "vertices_after": int(kept.sum()), "largest_before": int(hdrs[:, 3].max()),
+            "largest_after": int(kept.max()), "largest_before_ring_after": int(kept[int(hdrs[:, 3].argmax())]), "counts_bytes": int(4 * n), "kept_bytes": int(8 * kept.sum()),
+            "bytes_back": int(hdrs.nbytes + 4 * n + 8 * kept.sum()), "scratch_bytes": int(simp["scratch"].numel())},
         "scene_launches": {name: summary(v) for name, v in per.items()},
         "copy_read_bytes": {"flat": flat_plan.copy_read_bytes, "scenes": scene_plan.copy_read_bytes},
         "composite_bytes": {"flat": out_flat.numel(), "scenes": out_scene.numel()},
