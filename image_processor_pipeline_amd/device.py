@@ -27,6 +27,11 @@ def _to_dev(a: np.ndarray, device) -> torch.Tensor:
     return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).to(device)
 
 
+def exclusive_offsets(counts) -> np.ndarray:
+    """int64 exclusive prefix sum: where each run of `counts` starts in a packed buffer."""
+    return np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.int64)
+
+
 def _keep(*tensors: torch.Tensor) -> None:
     """Tie small device buffers (descriptors, taps) to the current stream so
     the caching allocator cannot hand their memory to a later H2D copy before

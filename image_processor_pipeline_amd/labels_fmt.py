@@ -1,0 +1,185 @@
+"""Label and mask formatting of the batched pipe: pure host code, no library
+call and no GPU.
+
+``yolo_label(s)`` write the reference's one label per composite (overlays.py:141-149),
+from its rectangle or from the tight boxes of ``PipeRunner.overlay_bboxes``.  For the
+scenes of scenes.py, ``scene_labels`` formats the box lines and ``scene_seg_labels`` the
+YOLO segmentation lines, both for the overlays ``_label_lines`` names; ``instance_ids`` and
+``scene_instance_masks`` turn a visibility map into instance masks.  ``fused`` re-exports it all.
+"""
+from __future__ import annotations
+
+from typing import List, Optional, Tuple
+
+import numpy as np
+
+from . import _native as N
+from .labels_math import xyxy2xywhn
+
+
+def yolo_label(class_id: int, box: Tuple[int, int, int, int], bg_w: int, bg_h: int) -> str:
+    """One YOLO label line for the pixel box (x0, y0, x1, y1) on a bg_w×bg_h
+    composite, formatted as the reference does (overlays.py:143-149)."""
+    cx, cy, w, h = xyxy2xywhn(np.array(box).reshape(1, 4), bg_w, bg_h)[0]
+    return f"{class_id} {cx:.6f} {cy:.6f} {w:.6f} {h:.6f}"
+
+
+def yolo_labels(plan, class_id: int = 0, boxes: Optional[np.ndarray] = None) -> List[Optional[str]]:
+    """The YOLO label of every item's composite, in item order.
+
+    ``boxes=None``: the reference's label, the resized overlay's rectangle
+    (x, y, x + ov_w, y + ov_h) (overlays.py:141-149) — byte for byte what the
+    per-file plugin writes.  ``boxes`` = the (n, 4) array of
+    ``PipeRunner.overlay_bboxes`` (overlay coordinates): the tight label, the
+    box (x + x0, y + y0, x + x1, y + y1) through the same conversion.  An
+    item whose row is all -1 has no visible overlay pixel and gets ``None``:
+    the caller writes an empty label file for it, the YOLO convention for an
+    image without objects."""
+    it = plan.items
+    n = len(it)
+    if boxes is not None:
+        boxes = np.asarray(boxes)
+        if boxes.shape != (n, 4):
+            raise ValueError(f"boxes of shape {boxes.shape} for {n} items")
+    out: List[Optional[str]] = []
+    for i in range(n):
+        x, y = int(it["x"][i]), int(it["y"][i])
+        x0, y0, x1, y1 = (0, 0, int(it["ov_w"][i]), int(it["ov_h"][i])) if boxes is None else (int(v) for v in boxes[i])
+        out.append(None if x0 < 0 else yolo_label(class_id, (x + x0, y + y0, x + x1, y + y1), plan.bg_w, plan.bg_h))
+    return out
+
+
+def _scene_rows(rows, name: str) -> Tuple[np.ndarray, int, int]:
+    """The (S, K, 6) rows of ``SceneRunner.scene_boxes`` as an array, with S and K."""
+    rows = np.asarray(rows)
+    if rows.ndim != 3 or rows.shape[2] != 6:
+        raise ValueError(f"{name} of shape {rows.shape}: (scenes, layers, 6) expected")
+    return (rows,) + rows.shape[:2]
+
+
+def _label_lines(rows: np.ndarray, class_ids, min_visible: float):
+    """(s, k, class id, row) of every overlay that gets a label line, in scene, layer order: those with
+    visible > 0 and visible / area >= min_visible.  ``class_ids``: an int, or one per overlay (S·K, scene-major)."""
+    S, K = rows.shape[:2]
+    if isinstance(class_ids, (int, np.integer)):
+        ids = [int(class_ids)] * (S * K)
+    else:
+        ids = [int(c) for c in class_ids]
+        if len(ids) != S * K:
+            raise ValueError(f"{len(ids)} class ids for {S * K} overlays")
+    for s in range(S):
+        for k in range(K):
+            area, vis = int(rows[s, k, 4]), int(rows[s, k, 5])
+            if vis > 0 and vis >= min_visible * area:
+                yield s, k, ids[s * K + k], rows[s, k]
+
+
+def scene_labels(boxes: np.ndarray, bg_w: int, bg_h: int, class_ids=0, min_visible: float = 0.0) -> List[List[str]]:
+    """YOLO lines of every scene from the (S, K, 6) rows (x0, y0, x1, y1, area,
+    visible) of ``SceneRunner.scene_boxes``: labels[s] lists, in layer order,
+    one line (``yolo_label``) per overlay with visible > 0 and visible / area
+    >= min_visible (``_label_lines``, ``class_ids`` too); an empty list = an empty label file."""
+    boxes, S, _ = _scene_rows(boxes, "boxes")
+    out: List[List[str]] = [[] for _ in range(S)]
+    for s, _, class_id, row in _label_lines(boxes, class_ids, min_visible):
+        out[s].append(yolo_label(class_id, tuple(int(v) for v in row[:4]), bg_w, bg_h))
+    return out
+
+
+def scene_map_pitch(bg_w: int) -> int:
+    """Row pitch in bytes of a visibility map (``SceneRunner.scene_masks``): ⌈bg_w / 16⌉·16."""
+    return (int(bg_w) + 15) // 16 * 16
+
+
+# instance id of a visibility-map byte: 0 = nothing visible, else 1 + its topmost set bit
+_INSTANCE_LUT = np.array([v.bit_length() for v in range(256)], np.uint8)
+
+
+def instance_ids(vis_map):
+    """Instance-id image of a visibility map (``SceneRunner.scene_masks``), a
+    torch or numpy uint8 array of any shape: 0 where no overlay is visible,
+    otherwise 1 + the topmost layer whose bit is set (1 + layer within the
+    scene).  The result has the input's type, shape and device."""
+    import torch
+    on_torch = isinstance(vis_map, torch.Tensor)
+    vis_map = vis_map if on_torch else np.asarray(vis_map)
+    if vis_map.dtype != (torch.uint8 if on_torch else np.uint8):
+        raise ValueError(f"instance_ids: a uint8 map expected, got {vis_map.dtype}")
+    return torch.from_numpy(_INSTANCE_LUT).to(vis_map.device)[vis_map.long()] if on_torch else _INSTANCE_LUT[vis_map]
+
+
+def scene_instance_masks(vis_map, rows) -> List[List[Optional[np.ndarray]]]:
+    """Per-overlay instance masks from a copied-back visibility map (S, bg_h,
+    bg_w) and the (S, K, 6) rows of ``scene_boxes``: masks[s] lists, in layer
+    order, the boolean array of bit k cropped to overlay k's box (y1 - y0, x1
+    - x0), or None for an overlay without a visible pixel.  Host code; a
+    device map is copied back first (synchronises)."""
+    import torch
+    if isinstance(vis_map, torch.Tensor):
+        vis_map = vis_map.cpu().numpy()
+    vis_map = np.asarray(vis_map)
+    rows, S, K = _scene_rows(rows, "rows")
+    if vis_map.dtype != np.uint8 or vis_map.ndim != 3 or vis_map.shape[0] != S:
+        raise ValueError(f"a uint8 map of {S} scenes (S, bg_h, bg_w) expected, got {vis_map.dtype} {vis_map.shape}")
+    if K > N.IPP_SCENE_MAP_MAX_LAYERS:
+        raise ValueError(f"{K} layers: a visibility map holds at most {N.IPP_SCENE_MAP_MAX_LAYERS}")
+
+    def mask(s: int, k: int) -> Optional[np.ndarray]:
+        x0, y0, x1, y1 = (int(v) for v in rows[s, k, :4])
+        return None if x0 < 0 else ((vis_map[s, y0:y1, x0:x1] >> k) & 1).astype(bool)
+
+    return [[mask(s, k) for k in range(K)] for s in range(S)]
+
+
+def scene_contour_capacity(plan) -> int:
+    """Default ``max_edges`` of ``SceneRunner.scene_polygons``: 8·(max_ov_w +
+    max_ov_h) rounded up to 256 — four times the 2(w + h) boundary edges of a
+    monotone outline filling the largest overlay's box."""
+    p = plan.pipe if hasattr(plan, "pipe") else plan
+    return (8 * (int(p.max_ov_w) + int(p.max_ov_h)) + 255) // 256 * 256
+
+
+def simplify_tolerance(eps) -> int:
+    """``eps_q`` of ipp_polygons_simplify for a tolerance of `eps` pixels: a
+    real number that is a multiple of 0.25 in 0.25..1024 (the rule works in
+    exact quarter pixels).  Anything else raises ValueError."""
+    if isinstance(eps, (bool, np.bool_)) or not isinstance(eps, (int, float, np.integer, np.floating)):
+        raise ValueError(f"simplify tolerance {eps!r}: a real number of pixels expected")
+    q = float(eps) * 4.0
+    if not (q == q and 1.0 <= q <= 4096.0 and q == int(q)):
+        raise ValueError(f"simplify tolerance {eps!r}: a multiple of 0.25 in 0.25..1024 pixels expected")
+    return int(q)
+
+
+def seg_label(class_id: int, poly, bg_w: int, bg_h: int) -> str:
+    """One YOLO segmentation line for the (V, 2) lattice polygon `poly` on a
+    bg_w×bg_h composite: the class, then x / bg_w and y / bg_h of every vertex,
+    in the number format of ``yolo_label``."""
+    poly = np.asarray(poly)
+    if poly.ndim != 2 or poly.shape[1] != 2 or len(poly) < 3:
+        raise ValueError(f"a polygon of shape {poly.shape}: (V >= 3, 2) expected")
+    return " ".join([str(class_id)] + [f"{int(x) / bg_w:.6f} {int(y) / bg_h:.6f}" for x, y in poly])
+
+
+def scene_seg_labels(polys, info, rows, bg_w: int, bg_h: int, class_ids=0, min_visible: float = 0.0) -> List[List[str]]:
+    """YOLO segmentation lines of every scene from what
+    ``SceneRunner.scene_polygons`` returns: labels[s] lists, in layer order,
+    one line (``seg_label``) per overlay that ``scene_labels`` gives a line
+    (``_label_lines``).  ``class_ids`` as there.  An overlay that would get a
+    line but overflowed ``max_edges`` (header flags bit 0) raises ValueError
+    naming the ``max_edges`` it needs: a label is never dropped or truncated."""
+    info = np.asarray(info)
+    rows, S, K = _scene_rows(rows, "rows")
+    if info.shape != (S, K, N.IPP_CONTOUR_HDR):
+        raise ValueError(f"info of shape {info.shape}: ({S}, {K}, {N.IPP_CONTOUR_HDR}) expected")
+    if len(polys) != S or any(len(p) != K for p in polys):
+        raise ValueError(f"polys does not hold {S} scenes of {K} overlays")
+    out: List[List[str]] = [[] for _ in range(S)]
+    for s, k, class_id, row in _label_lines(rows, class_ids, min_visible):
+        if int(info[s, k, 7]) & 1:
+            raise ValueError(f"scene {s} layer {k}: its contour has {int(info[s, k, 0])} boundary edges, "
+                             f"scene_polygons needs max_edges >= {int(info[s, k, 0])}")
+        if polys[s][k] is None:
+            raise ValueError(f"scene {s} layer {k}: {int(row[5])} visible pixels but no polygon")
+        out[s].append(seg_label(class_id, polys[s][k], bg_w, bg_h))
+    return out

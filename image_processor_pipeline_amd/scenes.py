@@ -1,0 +1,422 @@
+"""Scenes: K overlays per composite in the batched pipe, with occlusion-aware
+labels (an addition: the reference pastes one overlay per composite).
+
+``plan_scenes`` / ``SceneRunner`` paste the overlays in layer order — layer 0
+as the pipe of fused.py does, every later layer by an H launch without the
+copy (``ipp_pipe_hpass``) and an in-place V launch (``ipp_pipe_vblend_over``)
+— and label each overlay by what no later layer covers (``scene_boxes``).
+``scene_masks`` keeps that rule's per-pixel answer, one visibility map per
+composite, and ``scene_polygons`` traces (and simplifies) each overlay's outer
+contour from it on the device.  labels_fmt.py formats the lines and masks;
+every public name here is also reachable as ``fused.X``.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _native as N
+from .device import _stream, _to_dev, exclusive_offsets
+from .device import check_alpha_min as _check_alpha_min
+from .fused import (ItemParams, PipeConfig, PipePlan, _launch_hpass_bgcopy, _launch_vblend_bands, _Runner,
+                    draw_params, plan_pipe)
+from .labels_fmt import scene_contour_capacity, scene_labels, scene_map_pitch, scene_seg_labels, simplify_tolerance
+
+
+def draw_scene_params(n_scenes_global: int, stop_scene: int, per_scene: int, src_hw: Tuple[int, int],
+                      bg_hw: Tuple[int, int], n_bg: int, cfg: PipeConfig, seed) -> List[ItemParams]:
+    """The seeded parameters of overlay items 0 .. stop_scene·per_scene - 1 of
+    a batch of scenes: exactly ``draw_params``'s stream over n_scenes_global ·
+    per_scene items (all angles, all symmetries, the background shuffle, then
+    per item ratio, x, y); overlay item i = scene·per_scene + layer, and the
+    background of item i is order[(i // per_scene) % n_bg], one per scene."""
+    K = per_scene
+    angles, syms, order, drawn = draw_params(n_scenes_global * K, stop_scene * K, src_hw, bg_hw, n_bg, cfg, seed)
+    return [ItemParams(angles[i], syms[i], order[(i // K) % n_bg], drawn[i][0], drawn[i][1], drawn[i][2])
+            for i in range(stop_scene * K)]
+
+
+@dataclass
+class ScenePlan:
+    """A batch of S scenes of K overlays each.  Overlay item i = s·K + k
+    (scene s, layer k; layer K-1 on top) is built from source image i.
+
+    ``descs`` is layer-major: descriptors [k·S, (k+1)·S) are layer k's, each
+    layer in the same scene order — scenes grouped by background (stable), so
+    layer 0's grouped copy keeps its shared loads.  ``desc_item[d]`` is the
+    overlay item of descriptor d (``pipe.order`` does not describe this
+    order).  Every descriptor's ``p.dst_off`` is its scene's composite slot;
+    layers >= 1 have ``p.bg_off = p.dst_off`` and ``p.bg_pitch = p.dst_pitch``
+    (they blend in place).  With K = 1 the descriptors are ``plan_pipe``'s."""
+    pipe: PipePlan               # the S·K overlay items (items, axes, hsv, totals)
+    descs: np.ndarray            # PIPE_DESC[S·K], layer-major
+    desc_item: np.ndarray        # int32[S·K]
+    n_scenes: int
+    per_scene: int
+    copy_read_bytes: int = 0     # background bytes layer 0's grouped copy loads
+
+    # read through to the overlay items' plan
+    items = property(lambda self: self.pipe.items)
+    axes = property(lambda self: self.pipe.axes)
+    params = property(lambda self: self.pipe.params)
+    bg_w = property(lambda self: self.pipe.bg_w)
+    bg_h = property(lambda self: self.pipe.bg_h)
+
+    @property
+    def scene_layer(self) -> np.ndarray:
+        """int32 (S·K, 2): (scene, layer) of each descriptor."""
+        return np.stack([self.desc_item // self.per_scene, self.desc_item % self.per_scene], axis=1).astype(np.int32)
+
+
+def plan_scenes(src_hw: Tuple[int, int], n_scenes: int, per_scene: int, bg_hw: Tuple[int, int], n_bg: int,
+                cfg: PipeConfig, seed: int = 0, src_pitch: Optional[int] = None,
+                item_range: Optional[Tuple[int, int]] = None, n_scenes_global: Optional[int] = None,
+                params: Optional[Sequence[ItemParams]] = None, n_threads: int = 0) -> ScenePlan:
+    """Plan `n_scenes` scenes of `per_scene` overlays.  ``item_range`` and
+    ``n_scenes_global`` count SCENES: a rank plans scenes [start, stop) of the
+    global batch and sees the parameters a single process would
+    (``draw_scene_params``).  ``params``: one ItemParams per overlay item
+    (n_scenes·per_scene, scene-major), nothing is drawn; the items of a scene
+    must name the same background.  With ``per_scene=1`` this is ``plan_pipe``
+    with the same arguments."""
+    K, S = per_scene, n_scenes
+    if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or K < 1:
+        raise ValueError(f"per_scene {per_scene!r}: an integer >= 1")
+    start, stop = item_range if item_range is not None else (0, S)
+    if stop - start != S or start < 0 or S <= 0:
+        raise ValueError(f"item_range {item_range} does not hold {S} scenes")
+    sg = stop if n_scenes_global is None else n_scenes_global
+    if sg < stop:
+        raise ValueError(f"n_scenes_global {sg} < item_range stop {stop}")
+    if params is not None:
+        if len(params) != S * K:
+            raise ValueError(f"{len(params)} ItemParams for {S} scenes of {K} overlays")
+        for s in range(S):
+            if len({int(q.bg_index) for q in params[s * K:(s + 1) * K]}) != 1:
+                raise ValueError(f"scene {start + s}: its overlays name different backgrounds")
+    if K == 1:
+        pipe = plan_pipe(src_hw, S, bg_hw, n_bg, cfg, seed, src_pitch, (start, stop), sg, params, n_threads)
+    else:
+        given = params
+        if given is None:
+            given = draw_scene_params(sg, stop, K, src_hw, bg_hw, n_bg, cfg, seed)[start * K:]
+        pipe = plan_pipe(src_hw, S * K, bg_hw, n_bg, cfg, seed, src_pitch, (start * K, stop * K), sg * K, given,
+                         n_threads)
+    # plan_pipe's descriptor d holds item pipe.order[d], with p.dst_off = the
+    # item's own slot: re-point it at the scene's slot and reorder layer-major
+    by_item = np.empty_like(pipe.descs)
+    by_item[pipe.order] = pipe.descs
+    slot = int(pipe.descs[0]["p"]["bg_h"]) * int(pipe.descs[0]["p"]["dst_pitch"])    # bytes of one composite
+    scene_order = np.argsort(pipe.items["bg_index"][::K], kind="stable")             # scenes grouped by background
+    desc_item = (scene_order[None, :] * K + np.arange(K)[:, None]).reshape(-1).astype(np.int32)
+    descs = by_item[desc_item]
+    descs["p"]["dst_off"] = (desc_item // K).astype(np.int64) * slot
+    descs["p"]["bg_off"][S:] = descs["p"]["dst_off"][S:]
+    descs["p"]["bg_pitch"][S:] = descs["p"]["dst_pitch"][S:]
+    # one background load per run of same-background layer-0 descriptors in a copy group (IPP_PT_COPY_READS)
+    bgi = pipe.items["bg_index"][desc_item[:S]]
+    runs = sum(1 for d in range(S) if d % N.IPP_PIPE_COPY_GROUP == 0 or bgi[d] != bgi[d - 1])
+    return ScenePlan(pipe, descs, desc_item, S, K, runs * 3 * pipe.bg_w * pipe.bg_h)
+
+
+def _check_level(name: str, v) -> int:
+    """alpha_min / cover_min: an integer in 1..255 (check_alpha_min's rule)."""
+    try:
+        return _check_alpha_min(v)
+    except ValueError:
+        raise ValueError(f"{name} {v!r}: an integer in 1..255") from None
+
+
+SIMPLIFY_MAX_SIDE = 16384   # largest background side ipp_polygons_simplify takes (ipp.h: the overflow bounds)
+
+
+class SceneRunner(_Runner):
+    """Device-resident scene plan + scratch for repeated runs of one batch:
+    2 + K launches on the current stream (2 when K = 1, the pipe's own)."""
+
+    _scene_layer = _scratch = None   # of the label and map launches; these four are allocated on first use
+    _contour_scratch = None          # (max_edges, buffer) of scene_polygons
+    _simplify_scratch = None         # buffer of scene_polygons(simplify=...), grown on demand
+
+    def _check(self, caller: str, src: torch.Tensor, bgs: torch.Tensor, out: torch.Tensor) -> None:
+        self._check_tensors(caller, src, bgs, out)
+        p, S, K = self.plan.pipe, self.plan.n_scenes, self.plan.per_scene
+        if src.dim() < 1 or src.shape[0] != S * K:
+            raise ValueError(f"SceneRunner.{caller}: src holds {src.shape[0] if src.dim() else 0} images, "
+                             f"{S} scenes of {K} overlays take {S * K}")
+        if tuple(out.shape) != (S, p.bg_h, p.bg_w, 3):
+            raise ValueError(f"SceneRunner.{caller}: out of shape {tuple(out.shape)}, {S} composites "
+                             f"({S}, {p.bg_h}, {p.bg_w}, 3) expected")
+        if bgs.dim() != 4 or tuple(bgs.shape[1:]) != (p.bg_h, p.bg_w, 3) or \
+                bgs.shape[0] <= int(p.items["bg_index"].max()):
+            raise ValueError(f"SceneRunner.{caller}: bgs of shape {tuple(bgs.shape)} does not hold the plan's "
+                             f"backgrounds (n, {p.bg_h}, {p.bg_w}, 3)")
+
+    def run(self, src: torch.Tensor, bgs: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+        self._check("run", src, bgs, out)
+        p, S, K = self.plan.pipe, self.plan.n_scenes, self.plan.per_scene
+        st, lib = _stream(self.device), self.lib
+        _launch_hpass_bgcopy(lib, p, src.data_ptr(), self.tmp.data_ptr(), self.coefs.data_ptr(), self._dptr(0), S,
+                             bgs.data_ptr(), out.data_ptr(), st)
+        if K > 1:
+            N.check(lib.ipp_pipe_hpass(src.data_ptr(), self.tmp.data_ptr(), self.coefs.data_ptr(), self._dptr(S),
+                                       S * (K - 1), p.max_out_w, p.max_rows, 3, N.np_ptr(p.hsv), p.tap_format, st),
+                    "ipp_pipe_hpass")
+        self._hpass_done = True
+        _launch_vblend_bands(lib, p, self.tmp.data_ptr(), bgs.data_ptr(), out.data_ptr(), self.coefs.data_ptr(),
+                             self._dptr(0), S, st)
+        # one launch per later layer: two overlays of a scene never share a launch (ipp.h)
+        for k in range(1, K):
+            N.check(lib.ipp_pipe_vblend_over(self.tmp.data_ptr(), out.data_ptr(), self.coefs.data_ptr(),
+                                             self._dptr(k * S), S, p.bg_w, p.bg_h, p.max_ov_w, p.max_ov_h,
+                                             p.tap_format, st), "ipp_pipe_vblend_over")
+        return out
+
+    def _scratch_bytes(self, entry: str, *args) -> int:
+        """What the library's `entry` (a ``*_scratch_bytes`` function) asks for these arguments."""
+        nb = getattr(self.lib, entry)(*args)
+        if nb < 0:
+            raise N.NativeError(f"{entry} failed with code {nb}")
+        return int(nb)
+
+    def _scene_scratch(self, caller: str) -> None:
+        """The guard and the (once allocated) scratch shared by the label and the map launches."""
+        if not self._hpass_done:
+            raise N.NativeError(f"SceneRunner.{caller}: no H launch (run) has run on this runner")
+        if self._scratch is None:
+            p, S, K = self.plan.pipe, self.plan.n_scenes, self.plan.per_scene
+            nb = self._scratch_bytes("ipp_pipe_scene_scratch_bytes", S * K, S, K, p.max_ov_w, p.max_ov_h)
+            self._scratch = torch.empty(nb, dtype=torch.uint8, device=self.device)
+            self._scene_layer = _to_dev(self.plan.scene_layer, self.device)
+
+    def _rows(self) -> torch.Tensor:   # of one label or map launch: 6 int32 per descriptor
+        return torch.empty(6 * len(self.plan.descs), dtype=torch.int32, device=self.device)
+
+    def _launch_boxes(self, alpha_min: int, cover_min: int) -> torch.Tensor:
+        self._scene_scratch("scene_boxes")
+        p, S, K = self.plan.pipe, self.plan.n_scenes, self.plan.per_scene
+        rows = self._rows()
+        N.check(self.lib.ipp_pipe_scene_boxes(self.tmp.data_ptr(), self.coefs.data_ptr(), self._dptr(0),
+                                              self._scene_layer.data_ptr(), S * K, S, K, p.max_ov_w, p.max_ov_h,
+                                              alpha_min, cover_min, p.tap_format, self._scratch.data_ptr(),
+                                              rows.data_ptr(), _stream(self.device)), "ipp_pipe_scene_boxes")
+        return rows
+
+    def _check_map(self, caller: str, out: Optional[torch.Tensor]) -> None:
+        """Everything ``scene_masks`` refuses with ValueError, before any launch."""
+        p, S, K = self.plan.pipe, self.plan.n_scenes, self.plan.per_scene
+        if K > N.IPP_SCENE_MAP_MAX_LAYERS:
+            raise ValueError(f"SceneRunner.{caller}: {K} layers per scene, a visibility map holds at most "
+                             f"{N.IPP_SCENE_MAP_MAX_LAYERS} (one bit per layer)")
+        if out is None:
+            return
+        shape = (S, p.bg_h, scene_map_pitch(p.bg_w))
+        same_dev = isinstance(out, torch.Tensor) and out.device.type == self.device.type and \
+            self.device.index in (None, out.device.index)
+        if not same_dev or out.dtype != torch.uint8 or tuple(out.shape) != shape or not out.is_contiguous() or \
+                out.data_ptr() % 16:
+            raise ValueError(f"SceneRunner.{caller}: out must be a contiguous uint8 tensor {shape} on {self.device}, "
+                             f"16-B aligned (the row pitch is scene_map_pitch(bg_w))")
+
+    def _launch_map(self, caller: str, alpha_min: int, cover_min: int, with_boxes: bool,
+                    out: Optional[torch.Tensor]) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        """One ipp_pipe_scene_map call: the (S, bg_h, pitch) map buffer and, with
+        ``with_boxes``, the device rows in descriptor order."""
+        self._scene_scratch(caller)
+        p, S, K = self.plan.pipe, self.plan.n_scenes, self.plan.per_scene
+        pitch = scene_map_pitch(p.bg_w)
+        buf = out if out is not None else torch.empty((S, p.bg_h, pitch), dtype=torch.uint8, device=self.device)
+        rows = self._rows() if with_boxes else None
+        N.check(self.lib.ipp_pipe_scene_map(self.tmp.data_ptr(), self.coefs.data_ptr(), self._dptr(0),
+                                            self._scene_layer.data_ptr(), S * K, S, K, p.bg_w, p.bg_h, p.max_ov_w,
+                                            p.max_ov_h, alpha_min, cover_min, p.tap_format, self._scratch.data_ptr(),
+                                            rows.data_ptr() if with_boxes else None, buf.data_ptr(), pitch,
+                                            _stream(self.device)), "ipp_pipe_scene_map")
+        return buf, rows
+
+    def _rows_by_scene(self, rows: torch.Tensor) -> np.ndarray:
+        """Copy the rows back (synchronises): (S, K, 6) in scene, layer order."""
+        by_desc = rows.cpu().numpy().reshape(-1, 6)
+        out = np.empty_like(by_desc)
+        out[self.plan.desc_item] = by_desc
+        return out.reshape(self.plan.n_scenes, self.plan.per_scene, 6)
+
+    def scene_boxes(self, alpha_min: int = 1, cover_min: int = 128) -> np.ndarray:
+        """(S, K, 6) int32 rows (x0, y0, x1, y1, area, visible) in scene, layer
+        order (ipp_pipe_scene_boxes): the half-open tight box, in composite
+        coordinates, of the overlay's visible pixels — alpha >= alpha_min and
+        not covered by a later layer's alpha >= cover_min — or (-1,-1,-1,-1);
+        area = pixels with alpha >= alpha_min, visible = the visible ones.  It
+        reads the H launches' scratch, so it runs after ``run`` on the current
+        stream, and synchronises for the copy back."""
+        alpha_min, cover_min = _check_level("alpha_min", alpha_min), _check_level("cover_min", cover_min)
+        return self._rows_by_scene(self._launch_boxes(alpha_min, cover_min))
+
+    def scene_masks(self, alpha_min: int = 1, cover_min: int = 128, with_boxes: bool = False,
+                    out: Optional[torch.Tensor] = None):
+        """The visibility maps of the batch (ipp_pipe_scene_map): a device uint8
+        tensor (S, bg_h, bg_w) in scene order (slot s belongs to composite
+        ``out[s]`` of ``run``), bit k of a byte set iff layer k of the scene is
+        visible at that pixel — alpha >= alpha_min and no later layer with alpha
+        >= cover_min there, the rule of ``scene_boxes``.  A byte may hold
+        several bits (``instance_ids`` keeps the topmost).  It is a view of an
+        (S, bg_h, pitch) buffer, pitch = ``scene_map_pitch(bg_w)``, whose padding
+        columns are 0; ``out`` supplies that buffer (contiguous CUDA uint8, any
+        contents: every byte is written).  It runs after ``run`` on the current
+        stream, stays on the device and does not synchronise.  With
+        ``with_boxes`` it returns (map, rows), rows = the (S, K, 6) array of
+        ``scene_boxes`` from the same alpha pass; that copy back synchronises.
+        Scenes of more than 8 layers are refused (ValueError)."""
+        alpha_min, cover_min = _check_level("alpha_min", alpha_min), _check_level("cover_min", cover_min)
+        self._check_map("scene_masks", out)
+        buf, rows = self._launch_map("scene_masks", alpha_min, cover_min, with_boxes, out)
+        vis = buf[:, :, :self.plan.bg_w]
+        return (vis, self._rows_by_scene(rows)) if with_boxes else vis
+
+    def _check_max_edges(self, caller: str, max_edges) -> int:
+        if max_edges is None:
+            return scene_contour_capacity(self.plan)
+        if isinstance(max_edges, bool) or not isinstance(max_edges, (int, np.integer)) or \
+                not 4 <= max_edges <= 1 << 22:
+            raise ValueError(f"SceneRunner.{caller}: max_edges {max_edges!r}: an integer in 4..2^22")
+        return int(max_edges)
+
+    def _check_simplify(self, caller: str, simplify) -> Optional[int]:
+        """``eps_q`` of a ``simplify`` tolerance (None: no simplification), refusing what the device would."""
+        if simplify is None:
+            return None
+        eps_q = simplify_tolerance(simplify)
+        p = self.plan.pipe
+        if p.bg_w > SIMPLIFY_MAX_SIDE or p.bg_h > SIMPLIFY_MAX_SIDE:
+            raise ValueError(f"SceneRunner.{caller}: simplify on a {p.bg_w}x{p.bg_h} background: bg_w and bg_h must "
+                             f"not exceed {SIMPLIFY_MAX_SIDE} (ipp_polygons_simplify's exact integer bounds)")
+        return eps_q
+
+    def _polygons(self, buf: torch.Tensor, rows: torch.Tensor, max_edges: int, eps_q: Optional[int] = None):
+        """The tracer, the header copy-back, the pack and the packed copy-back
+        on the map and device rows of one ``_launch_map``: (polys, info), both
+        in scene, layer order.  Synchronises.  With ``eps_q`` the packed
+        vertices stay on the device: ipp_polygons_simplify, the counts'
+        copy-back, ipp_polygons_simplify_pack, and only the kept vertices
+        come back."""
+        p, S, K = self.plan.pipe, self.plan.n_scenes, self.plan.per_scene
+        n, lib, st = S * K, self.lib, _stream(self.device)
+        if self._contour_scratch is None or self._contour_scratch[0] != max_edges:
+            nb = self._scratch_bytes("ipp_scene_contours_scratch_bytes", n, max_edges)
+            self._contour_scratch = (max_edges, torch.empty(nb, dtype=torch.uint8, device=self.device))
+        scratch = self._contour_scratch[1]
+        hdr = torch.empty(N.IPP_CONTOUR_HDR * n, dtype=torch.int32, device=self.device)
+        N.check(lib.ipp_scene_contours(buf.data_ptr(), buf.shape[2], p.bg_w, p.bg_h, rows.data_ptr(),
+                                       self._scene_layer.data_ptr(), n, S, K, max_edges, scratch.data_ptr(),
+                                       hdr.data_ptr(), st), "ipp_scene_contours")
+        by_desc = hdr.cpu().numpy().reshape(n, N.IPP_CONTOUR_HDR)      # synchronises
+        nv = by_desc[:, 3].astype(np.int64)
+        offsets = exclusive_offsets(nv)
+        total = int(nv.sum())
+        packed = np.empty((0, 2), np.int32)
+        if total:
+            verts = torch.empty(2 * total, dtype=torch.int32, device=self.device)
+            N.check(lib.ipp_scene_contours_pack(scratch.data_ptr(), hdr.data_ptr(),
+                                                _to_dev(offsets, self.device).data_ptr(), n, max_edges,
+                                                verts.data_ptr(), st), "ipp_scene_contours_pack")
+            if eps_q is None:
+                packed = verts.cpu().numpy().reshape(total, 2)
+            else:
+                nv, offsets, packed = self._simplified(verts, offsets, hdr, total, eps_q)
+        info = np.empty_like(by_desc)
+        info[self.plan.desc_item] = by_desc
+        polys: List[List[Optional[np.ndarray]]] = [[None] * K for _ in range(S)]
+        for d, item in enumerate(self.plan.desc_item.tolist()):
+            if nv[d]:
+                polys[item // K][item % K] = packed[offsets[d]:offsets[d] + nv[d]].copy()
+        return polys, info.reshape(S, K, N.IPP_CONTOUR_HDR)
+
+    def _simplified(self, verts: torch.Tensor, offsets: np.ndarray, hdr: torch.Tensor, total: int, eps_q: int):
+        """(counts, out_offsets, kept vertices (sum counts, 2)) of the packed device polygons."""
+        p, lib, st = self.plan.pipe, self.lib, _stream(self.device)
+        n = len(self.plan.descs)
+        nb = self._scratch_bytes("ipp_polygons_simplify_scratch_bytes", n, total)
+        if self._simplify_scratch is None or self._simplify_scratch.numel() < nb:
+            self._simplify_scratch = torch.empty(nb, dtype=torch.uint8, device=self.device)
+        scratch = self._simplify_scratch
+        d_off = _to_dev(offsets, self.device)
+        counts = torch.empty(n, dtype=torch.int32, device=self.device)
+        N.check(lib.ipp_polygons_simplify(verts.data_ptr(), d_off.data_ptr(), hdr.data_ptr(), n, total, p.bg_w,
+                                          p.bg_h, eps_q, scratch.data_ptr(), counts.data_ptr(), st),
+                "ipp_polygons_simplify")
+        kept = counts.cpu().numpy().astype(np.int64)                   # synchronises
+        out_offsets = exclusive_offsets(kept)
+        total_kept = int(kept.sum())
+        out = torch.empty(2 * max(total_kept, 1), dtype=torch.int32, device=self.device)
+        N.check(lib.ipp_polygons_simplify_pack(verts.data_ptr(), d_off.data_ptr(), hdr.data_ptr(), scratch.data_ptr(),
+                                               counts.data_ptr(), _to_dev(out_offsets, self.device).data_ptr(), n,
+                                               out.data_ptr(), st), "ipp_polygons_simplify_pack")
+        return kept, out_offsets, out[:2 * total_kept].cpu().numpy().reshape(total_kept, 2)
+
+    def scene_polygons(self, alpha_min: int = 1, cover_min: int = 128, max_edges: Optional[int] = None,
+                       simplify: Optional[float] = None):
+        """The outer contour of every overlay's visible pixels, traced on the
+        device from the visibility map (ipp_pipe_scene_map with boxes, then
+        ipp_scene_contours and ipp_scene_contours_pack; include/ipp.h states
+        the contour's definition).  Returns (polys, info, rows): polys[s][k] is
+        the (V, 2) int32 polygon of scene s, layer k in composite lattice
+        coordinates — the largest 8-connected visible part's outline, holes
+        not cut out — or None when the overlay has no visible pixel or has
+        more boundary edges than ``max_edges`` (default
+        ``scene_contour_capacity(plan)``); info is the (S, K, 8) headers
+        {n_edges, n_outer, n_holes, n_vertices, area2, start_x, start_y,
+        flags}, flags bit 0 = overflowed; rows is ``scene_boxes``' (S, K, 6)
+        from the same alpha pass.  Runs after ``run`` on the current stream;
+        only the headers and the packed vertices are copied back (it
+        synchronises).  Scenes of more than 8 layers are refused.  With
+        ``simplify`` = a tolerance in pixels (``simplify_tolerance``: a
+        multiple of 0.25) the polygons are simplified on the device by the
+        Douglas–Peucker rule of include/ipp.h (ipp_polygons_simplify): polys
+        holds the kept vertices, at least 3 each, info and rows are unchanged
+        (n_vertices stays the traced count), and the unsimplified vertices
+        never leave the device — the counts and the kept vertices do.
+        Backgrounds of more than 16384 pixels on a side are then refused."""
+        alpha_min, cover_min = _check_level("alpha_min", alpha_min), _check_level("cover_min", cover_min)
+        self._check_map("scene_polygons", None)
+        max_edges = self._check_max_edges("scene_polygons", max_edges)
+        eps_q = self._check_simplify("scene_polygons", simplify)
+        buf, rows = self._launch_map("scene_polygons", alpha_min, cover_min, True, None)
+        polys, info = self._polygons(buf, rows, max_edges, eps_q)
+        return polys, info, self._rows_by_scene(rows)
+
+    def run_labelled(self, src: torch.Tensor, bgs: torch.Tensor, out: torch.Tensor, class_ids=0,
+                     alpha_min: int = 1, cover_min: int = 128, min_visible: float = 0.0, masks: bool = False,
+                     polygons: bool = False, max_edges: Optional[int] = None, simplify: Optional[float] = None):
+        """``run`` plus the YOLO lines of every scene (``scene_labels``):
+        labels[s] lists scene s's lines in layer order, one per overlay with
+        visible > 0 and visible / area >= min_visible.  Returns (out, labels);
+        with ``masks`` (out, labels, map), the map of ``scene_masks`` from the
+        same launch as the boxes.  With ``polygons`` the tuple gains, as its
+        last element, the segmentation lines of ``scene_seg_labels`` (polygons
+        of ``scene_polygons`` with ``max_edges`` and ``simplify``), traced from
+        that same map launch.  ``simplify`` without ``polygons`` is refused."""
+        alpha_min, cover_min = _check_level("alpha_min", alpha_min), _check_level("cover_min", cover_min)
+        if simplify is not None and not polygons:
+            raise ValueError("SceneRunner.run_labelled: simplify needs polygons=True")
+        if masks or polygons:
+            self._check_map("run_labelled", None)
+        if polygons:
+            max_edges = self._check_max_edges("run_labelled", max_edges)
+            eps_q = self._check_simplify("run_labelled", simplify)
+        self.run(src, bgs, out)
+        if masks or polygons:
+            buf, rows = self._launch_map("run_labelled", alpha_min, cover_min, True, None)
+        else:
+            rows = self._launch_boxes(alpha_min, cover_min)
+        bg_w, bg_h = self.plan.bg_w, self.plan.bg_h
+        boxes = self._rows_by_scene(rows)
+        res = (out, scene_labels(boxes, bg_w, bg_h, class_ids, min_visible))
+        if masks:
+            res += (buf[:, :, :bg_w],)
+        if polygons:
+            polys, info = self._polygons(buf, rows, max_edges, eps_q)
+            res += (scene_seg_labels(polys, info, boxes, bg_w, bg_h, class_ids, min_visible),)
+        return res

@@ -177,7 +177,7 @@ def _rotations_batch(arg_tuples, output_dirs: List[Path], threads: int = 1, num_
         arrays = [np.asarray(decoded[i][0])[..., :3] for i in opaque]
         sizes = [a.size for a in arrays]
         flat = np.concatenate([a.reshape(-1) for a in arrays])
-        offs = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
+        offs = D.exclusive_offsets(sizes)
         dims, angs, src_offs, keys = [], [], [], []
         for j, i in enumerate(opaque):
             for r, a in enumerate(angles[i]):

@@ -9,22 +9,19 @@ import pytest
 torch = pytest.importorskip("torch")
 
 from tests import contour_refs as C
+from tests import gpu_scene_support as S
 from tests import scene_mask_refs as MR
-from tests import scene_refs as SR
+from tests.gpu_scene_support import DEV, current_stream as _stream, same_polys as _same_polys, to_dev_copy as _t
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 POISON = -0x5A5A5A5B            # 0xA5A5A5A5 as int32
 HANDMADE = C.handmade()
 
 
 @pytest.fixture(scope="module")
 def fused():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from image_processor_pipeline_amd import fused as F
-    return F
+    return S.require_fused()
 
 
 @pytest.fixture(scope="module")
@@ -33,35 +30,11 @@ def lib(fused):
     return N.load()
 
 
-def _t(a):
-    return torch.from_numpy(np.array(a)).to(DEV)          # (a copy: the shared cases are read-only)
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
 def _trace(lib, case, max_edges, slack=3):
     """Both C entries on a handmade case: (hdr (n, 8), verts buffer, offsets, total).
     The vertex buffer has `slack` poisoned pairs after the polygons."""
-    from image_processor_pipeline_amd import _native as N
-    n = len(case.rows)
-    nb = lib.ipp_scene_contours_scratch_bytes(n, max_edges)
-    assert nb == (32 * n + 255) // 256 * 256 + 2 * n * max_edges * 32          # the documented formula
-    scratch = torch.full((nb,), 0xA5, dtype=torch.uint8, device=DEV)
-    vis, rows, sl = _t(case.vis), _t(case.rows), _t(case.scene_layer)
-    hdr = torch.full((n * 8,), POISON, dtype=torch.int32, device=DEV)
-    N.check(lib.ipp_scene_contours(vis.data_ptr(), case.pitch, case.bg_w, case.bg_h, rows.data_ptr(), sl.data_ptr(),
-                                   n, case.n_scenes, case.per_scene, max_edges, scratch.data_ptr(), hdr.data_ptr(),
-                                   _stream()), "ipp_scene_contours")
-    h = hdr.cpu().numpy().reshape(n, 8)
-    nv = h[:, 3].astype(np.int64)
-    offsets = np.concatenate([[0], np.cumsum(nv)[:-1]]).astype(np.int64)
-    total = int(nv.sum())
-    verts = torch.full((2 * (total + slack),), POISON, dtype=torch.int32, device=DEV)
-    N.check(lib.ipp_scene_contours_pack(scratch.data_ptr(), hdr.data_ptr(), _t(offsets).data_ptr(), n, max_edges,
-                                        verts.data_ptr(), _stream()), "ipp_scene_contours_pack")
-    return h, verts.cpu().numpy().reshape(-1, 2), offsets, total
+    t = S.trace_contours(lib, case, max_edges, POISON, slack)
+    return t.hdr, t.verts, t.offsets, t.total
 
 
 def _expect_verts(hdrs, polys, slack=3):
@@ -100,15 +73,9 @@ def test_overflow_is_refused_not_truncated(fused, lib, name, victim):
 
 
 # --- 3: scene batches ------------------------------------------------------------------------------------------
-class Scenes:
+class Scenes(S.SceneBatch):
     def __init__(self, fused, batch):
-        self.fused = fused
-        self.src, self.bgs, self.plan, self.cfg = batch
-        self.runner = fused.SceneRunner(self.plan, DEV)
-        self.dsrc, self.dbgs = _t(self.src), _t(self.bgs)
-        self.out = torch.full((self.plan.n_scenes,) + self.bgs.shape[1:], 77, dtype=torch.uint8, device=DEV)
-        self.runner.run(self.dsrc, self.dbgs, self.out)
-        self.overlays = SR.scene_overlays(self.src, self.plan, self.cfg)
+        super().__init__(fused, batch)
         self._refs = {}
 
     def ref(self, a, c):
@@ -120,16 +87,6 @@ class Scenes:
 @pytest.fixture(scope="module")
 def batches(fused):
     return {name: Scenes(fused, b) for name, b in C.scene_batches(fused).items()}
-
-
-def _same_polys(got, exp):
-    assert len(got) == len(exp)
-    for gs, es in zip(got, exp):
-        assert len(gs) == len(es)
-        for g, e in zip(gs, es):
-            assert (g is None) == (e is None)
-            if g is not None:
-                assert g.dtype == np.int32 and g.shape == e.shape and np.array_equal(g, e)
 
 
 @pytest.mark.parametrize("name", ["noise", "odd", "edge", "eight"])

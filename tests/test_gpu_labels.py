@@ -10,23 +10,16 @@ from PIL import Image
 
 torch = pytest.importorskip("torch")
 
+from tests import gpu_scene_support as S
 from tests import label_refs as R
+from tests.gpu_scene_support import DEV, to_dev as _t
 
 pytestmark = pytest.mark.gpu
-
-DEV = "cuda:0"
 
 
 @pytest.fixture(scope="module")
 def fused():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from image_processor_pipeline_amd import fused as F
-    return F
-
-
-def _t(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+    return S.require_fused()
 
 
 class Batch:

@@ -10,39 +10,27 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
+from tests import gpu_scene_support as S
 from tests import label_refs as R
 from tests import scene_mask_refs as MR
 from tests import scene_refs as SR
+from tests.gpu_scene_support import DEV, to_dev as _t
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 POISON = 0xA5
 
 
 @pytest.fixture(scope="module")
 def fused():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from image_processor_pipeline_amd import fused as F
-    return F
+    return S.require_fused()
 
 
-def _t(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-class Scenes:
+class Scenes(S.SceneBatch):
     """One scene batch after its run, with the oracle's overlays and the reference maps."""
 
     def __init__(self, fused, batch):
-        self.fused = fused
-        self.src, self.bgs, self.plan, self.cfg = batch
-        self.runner = fused.SceneRunner(self.plan, DEV)
-        self.dsrc, self.dbgs = _t(self.src), _t(self.bgs)
-        self.out = torch.full((self.plan.n_scenes,) + self.bgs.shape[1:], 77, dtype=torch.uint8, device=DEV)
-        self.runner.run(self.dsrc, self.dbgs, self.out)
-        self.overlays = SR.scene_overlays(self.src, self.plan, self.cfg)
+        super().__init__(fused, batch)
         self.shape = (self.plan.n_scenes, self.plan.bg_h, MR.pitch_of(self.plan.bg_w))
         self._refs = {}
 

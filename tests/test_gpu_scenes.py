@@ -7,37 +7,26 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
+from tests import gpu_scene_support as S
 from tests import label_refs as R
 from tests import scene_refs as SR
+from tests.gpu_scene_support import DEV, to_dev as _t
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 LEVELS = [(1, 128), (128, 255), (255, 1)]     # (alpha_min, cover_min)
 
 
 @pytest.fixture(scope="module")
 def fused():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from image_processor_pipeline_amd import fused as F
-    return F
+    return S.require_fused()
 
 
-def _t(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-class Scenes:
+class Scenes(S.SceneBatch):
     """One planned scene batch after its run, with the oracle's overlays and composites."""
 
     def __init__(self, fused, src, bgs, plan, cfg):
-        self.fused, self.src, self.bgs, self.plan, self.cfg = fused, src, bgs, plan, cfg
-        self.runner = fused.SceneRunner(plan, DEV)
-        self.dsrc, self.dbgs = _t(src), _t(bgs)
-        self.out = torch.full((plan.n_scenes,) + bgs.shape[1:], 77, dtype=torch.uint8, device=DEV)
-        self.runner.run(self.dsrc, self.dbgs, self.out)
-        self.overlays = SR.scene_overlays(src, plan, cfg)
+        super().__init__(fused, (src, bgs, plan, cfg))
         self.composites = SR.scene_composites(bgs, plan, self.overlays)
 
     def check_composites(self):

@@ -13,12 +13,12 @@ import pytest
 torch = pytest.importorskip("torch")
 
 from tests import contour_refs as C
-from tests import scene_refs as SR
+from tests import gpu_scene_support as S
 from tests import simplify_refs as R
+from tests.gpu_scene_support import DEV, current_stream as _stream, same_polys as _same_polys, to_dev_copy as _t
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 POISON = -0x5A5A5A5B            # 0xA5A5A5A5 as int32
 HANDMADE = C.handmade()
 EPS_QS = (1, 4, 6, 4096)
@@ -33,10 +33,7 @@ CHUNK = int(re.search(r"#define IPP_SIMPLIFY_THREADS (\d+)", _HEADER).group(1))
 
 @pytest.fixture(scope="module")
 def fused():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from image_processor_pipeline_amd import fused as F
-    return F
+    return S.require_fused()
 
 
 @pytest.fixture(scope="module")
@@ -45,32 +42,10 @@ def lib(fused):
     return N.load()
 
 
-def _t(a):
-    return torch.from_numpy(np.array(a)).to(DEV)
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
 def _trace(lib, case, max_edges):
     """The tracer and its pack on a handmade case: (hdr numpy (n, 8), offsets numpy, total, device hdr, device verts)."""
-    from image_processor_pipeline_amd import _native as N
-    n = len(case.rows)
-    scratch = torch.empty(lib.ipp_scene_contours_scratch_bytes(n, max_edges), dtype=torch.uint8, device=DEV)
-    vis, rows, sl = _t(case.vis), _t(case.rows), _t(case.scene_layer)
-    hdr = torch.full((n * 8,), POISON, dtype=torch.int32, device=DEV)
-    N.check(lib.ipp_scene_contours(vis.data_ptr(), case.pitch, case.bg_w, case.bg_h, rows.data_ptr(), sl.data_ptr(),
-                                   n, case.n_scenes, case.per_scene, max_edges, scratch.data_ptr(), hdr.data_ptr(),
-                                   _stream()), "ipp_scene_contours")
-    h = hdr.cpu().numpy().reshape(n, 8)
-    nv = h[:, 3].astype(np.int64)
-    offsets = np.concatenate([[0], np.cumsum(nv)[:-1]]).astype(np.int64)
-    total = int(nv.sum())
-    verts = torch.full((2 * max(total, 1),), POISON, dtype=torch.int32, device=DEV)
-    N.check(lib.ipp_scene_contours_pack(scratch.data_ptr(), hdr.data_ptr(), _t(offsets).data_ptr(), n, max_edges,
-                                        verts.data_ptr(), _stream()), "ipp_scene_contours_pack")
-    return h, offsets, total, hdr, verts
+    t = S.trace_contours(lib, case, max_edges, POISON, 0)
+    return t.hdr, t.offsets, t.total, t.d_hdr, t.d_verts
 
 
 def _simplify(lib, verts, offsets, hdr, total, eps_q, bg=(16384, 16384)):
@@ -225,31 +200,15 @@ def test_large_synthetic_rings_at_the_thresholds(lib):
 
 
 # --- 5: scene batches ------------------------------------------------------------------------------------------
-class Scenes:
+class Scenes(S.SceneBatch):
     def __init__(self, fused, batch):
-        self.fused = fused
-        self.src, self.bgs, self.plan, self.cfg = batch
-        self.runner = fused.SceneRunner(self.plan, DEV)
-        self.dsrc, self.dbgs = _t(self.src), _t(self.bgs)
-        self.out = torch.full((self.plan.n_scenes,) + self.bgs.shape[1:], 77, dtype=torch.uint8, device=DEV)
-        self.runner.run(self.dsrc, self.dbgs, self.out)
-        self.overlays = SR.scene_overlays(self.src, self.plan, self.cfg)
+        super().__init__(fused, batch)
         self.ref = C.scene_reference(self.plan, self.overlays, 1, 128, C.SCENE_MAX_EDGES)
 
 
 @pytest.fixture(scope="module")
 def batches(fused):
     return {name: Scenes(fused, b) for name, b in C.scene_batches(fused).items()}
-
-
-def _same_polys(got, exp):
-    assert len(got) == len(exp)
-    for gs, es in zip(got, exp):
-        assert len(gs) == len(es)
-        for g, e in zip(gs, es):
-            assert (g is None) == (e is None)
-            if g is not None:
-                assert g.dtype == np.int32 and g.shape == e.shape and np.array_equal(g, e)
 
 
 @pytest.mark.parametrize("name", ["noise", "odd", "edge", "eight"])
