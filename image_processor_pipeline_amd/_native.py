@@ -145,6 +145,9 @@ SIGNATURES = {
     "ipp_alpha_bbox": (_I, [_P, _P, _I, _I, _I, _P, _P]),
     "ipp_alpha_bbox_min": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "ipp_pipe_overlay_bbox": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "ipp_pipe_hpass_bgcopy_trim": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P]),
+    "ipp_pipe_vblend_bands_trim": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
+    "ipp_pipe_overlay_bbox_trim": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _I, _P]),
     "ipp_pipe_hpass": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P]),
     "ipp_pipe_vblend_over": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "ipp_pipe_scene_scratch_bytes": (_L, [_I, _I, _I, _I, _I]),

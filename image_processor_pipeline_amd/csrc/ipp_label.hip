@@ -87,7 +87,7 @@ __device__ __forceinline__ void bbox_commit(int32_t* __restrict__ row, int xmin,
 template <typename Sink>
 __device__ __forceinline__ void overlay_alpha_band(const uint8_t* __restrict__ tmp, const int32_t* __restrict__ coefs,
                                                    const ipp_pipe_desc* __restrict__ descs, int im, int ty,
-                                                   Sink sink) {
+                                                   const uint16_t* __restrict__ trim, Sink sink) {
     const ipp_paste_desc p = descs[im].p;
     int vb0, vb1;
     paste_bands(p, vb0, vb1);
@@ -114,6 +114,7 @@ __device__ __forceinline__ void overlay_alpha_band(const uint8_t* __restrict__ t
 #pragma unroll
     for (int r = 0; r < 4; ++r) rb[r] = tt.bias[kBiasWords * t + 4 * (lane >> 4) + r];
     const int gbase = t_row_group(th.x + 16 * (lane >> 4));
+    const int hbands = trim_bands(descs[im].h.lines);  // H bands of the item with a trim entry
     // The alpha dword of T group (row group gbase, column 0); the loop below
     // walks t_group's address from it by whole groups and group rows.
     const uint8_t* abase = tmp + v.src_off + gbase * gstride * kTGroupBytes + kTAlphaByte;
@@ -128,10 +129,19 @@ __device__ __forceinline__ void overlay_alpha_band(const uint8_t* __restrict__ t
         acc[2] = i32x4{0, 0, 0, 0};
 #pragma unroll 1
         for (int ks = 0; ks < th.y; ++ks) {
-            i32x4 bq;
+            // the lane's four groups are one H band: constant (0x80, not
+            // stored) where the item's trim entries say so (ipp_pipe_layout.h)
+            uint32_t e = kTrimNone;
+            if (trim) {
+                const int hb = trim_v_band(th.x, ks, lane);
+                e = hb < hbands ? (uint32_t)trim[hb] : kTrimAll;
+            }
+            i32x4 bq = i32x4{(int32_t)0x80808080u, (int32_t)0x80808080u, (int32_t)0x80808080u, (int32_t)0x80808080u};
+            if (!trim_const(e, ct)) {
 #pragma unroll
-            for (int j = 0; j < 4; ++j)
-                bq[j] = *reinterpret_cast<const int32_t*>(aq + (kKStepGroups * ks + j) * gstride * kTGroupBytes);
+                for (int j = 0; j < 4; ++j)
+                    bq[j] = *reinterpret_cast<const int32_t*>(aq + (kKStepGroups * ks + j) * gstride * kTGroupBytes);
+            }
 #pragma unroll
             for (int q = 0; q < 3; ++q) {
                 const i32x4 a = __builtin_bit_cast(i32x4, tt.blk[th.z + tap_dense_block(ks, q, lane)]);
@@ -152,12 +162,14 @@ __device__ __forceinline__ void overlay_alpha_band(const uint8_t* __restrict__ t
 __global__ void __launch_bounds__(256)
 k_pipe_overlay_bbox(const uint8_t* __restrict__ tmp, const int32_t* __restrict__ coefs,
                     const ipp_pipe_desc* __restrict__ descs, FastDiv tiles_y, int alpha_min,
-                    int32_t* __restrict__ bbox) {
+                    int32_t* __restrict__ bbox, const uint16_t* __restrict__ trim, int trim_stride) {
     const uint32_t b = xcd_remap(blockIdx.x, gridDim.x);
     const int im = (int)fdiv(b, tiles_y);
     const int ty = (int)(b - (uint32_t)im * tiles_y.d);
     int xmin = INT32_MAX, ymin = INT32_MAX, xmax = -1, ymax = -1;
-    overlay_alpha_band(tmp, coefs, descs, im, ty, [&](int x, int o, int a) {
+    // (trim: the H launch's trim table, trim_stride entries per item, or null)
+    const uint16_t* trow = trim ? trim + (int64_t)im * trim_stride : nullptr;
+    overlay_alpha_band(tmp, coefs, descs, im, ty, trow, [&](int x, int o, int a) {
         if (a >= alpha_min) {
             xmin = min(xmin, x);
             xmax = max(xmax, x);
@@ -250,7 +262,8 @@ k_scene_alpha(const uint8_t* __restrict__ tmp, const int32_t* __restrict__ coefs
     if (descs[im].p.ov_w > max_ov_w || descs[im].p.ov_h > max_ov_h) return;  // no plane (block-uniform)
     const int64_t pitch = scene_pitch(max_ov_w);
     uint8_t* plane = planes + (int64_t)im * max_ov_h * pitch;
-    overlay_alpha_band(tmp, coefs, descs, im, ty,
+    // (no trim table: a scene's T is written in full)
+    overlay_alpha_band(tmp, coefs, descs, im, ty, nullptr,
                        [&](int x, int o, int a) { plane[(int64_t)o * pitch + x] = (uint8_t)a; });
 }
 
@@ -462,11 +475,13 @@ int scene_launches(const uint8_t* tmp, const int32_t* coefs, const ipp_pipe_desc
 
 }  // namespace
 
-extern "C" int ipp_pipe_overlay_bbox(const uint8_t* tmp, const int32_t* coefs, const ipp_pipe_desc* descs,
-                                     int32_t n_images, int32_t max_ov_w, int32_t max_ov_h, int32_t alpha_min,
-                                     int32_t tap_format, int32_t* bbox, void* stream) {
+extern "C" int ipp_pipe_overlay_bbox_trim(const uint8_t* tmp, const int32_t* coefs, const ipp_pipe_desc* descs,
+                                          int32_t n_images, int32_t max_ov_w, int32_t max_ov_h, int32_t alpha_min,
+                                          int32_t tap_format, int32_t* bbox, const uint16_t* trim, int32_t max_rows,
+                                          void* stream) {
     if (alpha_min < 1 || alpha_min > 255 || tap_format != IPP_TAPS_MFMA) return IPP_E_ARG;
     if (!tmp || !coefs || !descs || !bbox || n_images < 0 || max_ov_w <= 0 || max_ov_h <= 0) return IPP_E_ARG;
+    if (trim && max_rows <= 0) return IPP_E_ARG;
     if (n_images == 0) return IPP_OK;
     const int tyb = paste_max_bands(max_ov_h);
     const int64_t nb = (int64_t)tyb * n_images;
@@ -475,10 +490,17 @@ extern "C" int ipp_pipe_overlay_bbox(const uint8_t* tmp, const int32_t* coefs, c
     const int ib = (n_images + 255) / 256;
     hipLaunchKernelGGL(k_label_bbox_init, dim3(ib), dim3(256), 0, s, bbox, n_images);
     hipLaunchKernelGGL(k_pipe_overlay_bbox, dim3((uint32_t)nb), dim3(256), 0, s, tmp, coefs, descs,
-                       fast_div((uint32_t)tyb), alpha_min, bbox);
+                       fast_div((uint32_t)tyb), alpha_min, bbox, trim, trim ? trim_bands(max_rows) : 0);
     hipLaunchKernelGGL(k_label_bbox_finish, dim3(ib), dim3(256), 0, s, bbox, n_images);
     IPP_CHECK_LAUNCH();
     return IPP_OK;
+}
+
+extern "C" int ipp_pipe_overlay_bbox(const uint8_t* tmp, const int32_t* coefs, const ipp_pipe_desc* descs,
+                                     int32_t n_images, int32_t max_ov_w, int32_t max_ov_h, int32_t alpha_min,
+                                     int32_t tap_format, int32_t* bbox, void* stream) {
+    return ipp_pipe_overlay_bbox_trim(tmp, coefs, descs, n_images, max_ov_w, max_ov_h, alpha_min, tap_format, bbox,
+                                      nullptr, 0, stream);
 }
 
 extern "C" int ipp_alpha_bbox_min(const uint8_t* img, const ipp_image_desc* descs, int32_t n_images,

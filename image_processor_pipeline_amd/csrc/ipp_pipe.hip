@@ -261,7 +261,8 @@ __device__ __forceinline__ Hp2Chunk hp2_chunk(const int4* hdr, int s0, int ntile
 //
 // The body sweeps the output tiles [s_lo, s_hi) (wave-uniform, s_lo < s_hi):
 // hpass_block trims the band's leading and trailing tiles whose whole input
-// window is fill and writes their constant T groups itself (fill_trim).
+// window is fill and writes their constant T groups itself (fill_trim), or,
+// given a trim table, records the bounds there and leaves the groups unstored.
 //
 // (hpass2_body and the fill trim take the layout's numbers from
 // ipp_pipe_layout.h as named constants inside expressions of the shape they
@@ -766,7 +767,7 @@ template <int NR, bool ZONES, int CN>
 __device__ __forceinline__ void hpass_block(Hpass2Lds<NR>& L, const uint8_t* __restrict__ src,
                                             uint8_t* __restrict__ tmp, const int32_t* __restrict__ coefs,
                                             const ipp_pipe_desc* __restrict__ descs, int im, int tb,
-                                            const ipp_hsv_params& hp) {
+                                            const ipp_hsv_params& hp, uint16_t* __restrict__ trim) {
     const ipp_gather_desc g = descs[im].g;
     const ipp_resample_desc h = descs[im].h;
     const int row0 = tb * HR;
@@ -865,6 +866,10 @@ __device__ __forceinline__ void hpass_block(Hpass2Lds<NR>& L, const uint8_t* __r
     // [xlo, xhi], and the others' constant T groups are stored here, before
     // any gather is in flight.  One header per lane and a ballot give both
     // bounds, wave-uniform; items of more than 64 tiles are not trimmed.
+    // With a trim table (trim = the item's entries) the block records
+    // [s_lo, s_hi) there instead, (0, ntiles) where it does not trim, and
+    // stores no constant group: the table's readers do not load them
+    // (ipp_pipe_layout.h).
     const int ntiles = (h.out_len + kTileOut - 1) >> kTileOutLog2;  // tap_ntiles, phase 0
     int s_lo = 0, s_hi = ntiles;
     if constexpr (!ZONES) {
@@ -884,7 +889,7 @@ __device__ __forceinline__ void hpass_block(Hpass2Lds<NR>& L, const uint8_t* __r
             s_hi = km ? 64 - __builtin_clzll(km) : 0;
             // The trimmed tiles' T groups (addressed as in the body's epilogue:
             // group grp of the item's T, column xo), one tile per wave and turn.
-            const int ntrim = s_lo + ntiles - s_hi;
+            const int ntrim = trim ? 0 : s_lo + ntiles - s_hi;
             for (int i = wave; i < ntrim; i += HP_NW) {
                 const int t = i < s_lo ? i : i - s_lo + s_hi;
                 const int xo = 16 * t + (lane & 15);
@@ -895,9 +900,10 @@ __device__ __forceinline__ void hpass_block(Hpass2Lds<NR>& L, const uint8_t* __r
                     store16<2>(reinterpret_cast<uint8_t*>(dst), kTGroupBytes, true, w);
                 }
             }
-            if (s_lo >= s_hi) return;  // nothing to sweep (block-uniform: no barrier was met)
         }
     }
+    if (trim && threadIdx.x == 0) trim[tb] = (uint16_t)trim_entry(s_lo, s_hi);
+    if (s_lo >= s_hi) return;  // nothing to sweep (block-uniform: no barrier was met)
 
     // (the table barrier is in the body, after the first gathers)
     const int nrows = min(HR, h.lines - row0);
@@ -914,7 +920,7 @@ template <int NR, bool ZONES, int CN>
 __global__ void __launch_bounds__(64 * HP_NW) __attribute__((amdgpu_waves_per_eu(ZONES ? 3 : 4)))
 k_pipe_hpass2(const uint8_t* __restrict__ src, uint8_t* __restrict__ tmp, const int32_t* __restrict__ coefs,
               const ipp_pipe_desc* __restrict__ descs, int n, FastDiv tiles_y, FastDiv per_grp, ipp_hsv_params hp,
-              const uint8_t* __restrict__ bg, uint8_t* __restrict__ dst) {
+              const uint8_t* __restrict__ bg, uint8_t* __restrict__ dst, uint16_t* __restrict__ trim) {
     __shared__ Hpass2Lds<NR> L;
     const uint32_t b = xcd_remap(blockIdx.x, gridDim.x);
     // tiles_y = H-pass blocks per item (one per band).  Each group of
@@ -931,7 +937,8 @@ k_pipe_hpass2(const uint8_t* __restrict__ src, uint8_t* __restrict__ tmp, const 
     const int j = (int)fdiv((uint32_t)t, tiles_y);
     const int im = grp * kCopyGroup + j;
     if (im >= n) return;
-    hpass_block<NR, ZONES, CN>(L, src, tmp, coefs, descs, im, t - j * ty, hp);
+    // (the trim table's row of the item: ty entries, one per H band)
+    hpass_block<NR, ZONES, CN>(L, src, tmp, coefs, descs, im, t - j * ty, hp, trim ? trim + (int64_t)im * ty : nullptr);
 }
 
 // V pass on MFMA (tap tiles aligned with 16-row background bands: the plan's
@@ -1103,7 +1110,8 @@ template <bool MAGIC, bool INPLACE = false>
 __device__ __forceinline__ void vblend_block(uint32_t* __restrict__ orow, const uint8_t* __restrict__ tmp,
                                              typename VbPtr<INPLACE>::bg_t bg, typename VbPtr<INPLACE>::dst_t dst,
                                              const int32_t* __restrict__ coefs,
-                                             const ipp_pipe_desc* __restrict__ descs, int im, int ty, int ov_w_max) {
+                                             const ipp_pipe_desc* __restrict__ descs, int im, int ty, int ov_w_max,
+                                             const uint16_t* __restrict__ trim) {
     const ipp_paste_desc p = vb_paste_desc(descs[im].p, INPLACE);
     int y0 = ty * kBandRows;
     {
@@ -1166,12 +1174,28 @@ __device__ __forceinline__ void vblend_block(uint32_t* __restrict__ orow, const 
         for (int r = 0; r < 4; ++r) rb[r] = tt.bias[kBiasWords * t + 4 * (lane >> 4) + r];
         const u32x4_t* tbase = reinterpret_cast<const u32x4_t*>(tmp + v.src_off);
         const int gbase = t_row_group(th.x + 16 * (lane >> 4));
-        // T groups of K step ks of column tile ct: rows th.x + 64 ks + 16 (lane >> 4) .. + 15
-        auto tload = [&](int ct, int ks, u32x4_t (&g)[4]) {
-            const int xs = min(16 * ct + x_l, p.ov_w - 1);
-            const u32x4_t* tq = t_group(tbase, gstride, gbase + kKStepGroups * ks, xs);
+        // The trim entry of the lane's H band of K step ks (trim = the item's
+        // row of the H launch's trim table, ipp_pipe_layout.h): the band does
+        // not depend on the column tile, so a block reads its entries once.
+        // No table: nothing is constant.
+        const int hbands = trim_bands(descs[im].h.lines);
+        auto tentry = [&](int ks) -> uint32_t {
+            if (!trim) return kTrimNone;
+            const int hb = trim_v_band(th.x, ks, lane);
+            return hb < hbands ? (uint32_t)trim[hb] : kTrimAll;
+        };
+        // T groups of K step ks of column tile ct: rows th.x + 64 ks + 16 (lane >> 4) .. + 15,
+        // one H band (entry e): loaded, or 0x80 in every byte where the H launch left them unstored
+        auto tload = [&](int ct, int ks, uint32_t e, u32x4_t (&g)[4]) {
+            if (trim_const(e, ct)) {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) g[j] = tq[j * gstride];
+                for (int j = 0; j < 4; ++j) g[j] = u32x4_t{0x80808080u, 0x80808080u, 0x80808080u, 0x80808080u};
+            } else {
+                const int xs = min(16 * ct + x_l, p.ov_w - 1);
+                const u32x4_t* tq = t_group(tbase, gstride, gbase + kKStepGroups * ks, xs);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) g[j] = tq[j * gstride];
+            }
         };
         // the tile's unpremultiplied overlay pixels into the band's LDS rows
         // (s(c, r) = the sum of channel c, tile row r)
@@ -1202,6 +1226,12 @@ __device__ __forceinline__ void vblend_block(uint32_t* __restrict__ orow, const 
 #pragma unroll
                     for (int q = 0; q < 3; ++q)
                         ta[ks][q] = __builtin_bit_cast(i32x4, tt.blk[th.z + tap_dense_block(ks, q, lane)]);
+                // the lane's trim entries, K step ks in bits 16 ks .. 16 ks + 15
+                static_assert(NK <= 4, "four 16-bit trim entries in 64 bits");
+                uint64_t tpk = 0;
+#pragma unroll
+                for (int ks = 0; ks < NK; ++ks) tpk |= (uint64_t)tentry(ks) << (16 * ks);
+                auto te = [&](int ks) { return (uint32_t)(tpk >> (16 * ks)) & 0xFFFFu; };
                 // the loaded T groups of a tile, turned channel-major
                 auto transpose = [&](const u32x4_t (&g)[NK][4], i32x4 (&bq)[NK][4]) {
 #pragma unroll
@@ -1220,14 +1250,14 @@ __device__ __forceinline__ void vblend_block(uint32_t* __restrict__ orow, const 
                     int ct = wave;
                     if (ct < ctiles) {
 #pragma unroll
-                        for (int ks = 0; ks < NK; ++ks) tload(ct, ks, gn[ks]);
+                        for (int ks = 0; ks < NK; ++ks) tload(ct, ks, te(ks), gn[ks]);
                         transpose(gn, bc);
                     }
                     for (; ct < ctiles; ct += 4) {
                         const bool more = ct + 4 < ctiles;
                         if (more) {
 #pragma unroll
-                            for (int ks = 0; ks < NK; ++ks) tload(ct + 4, ks, gn[ks]);
+                            for (int ks = 0; ks < NK; ++ks) tload(ct + 4, ks, te(ks), gn[ks]);
                         }
                         i32x4 acc[4];
                         vb_mfma_tile<NK>(ta, bc, rb, acc);
@@ -1238,7 +1268,7 @@ __device__ __forceinline__ void vblend_block(uint32_t* __restrict__ orow, const 
                     for (int ct = wave; ct < ctiles; ct += 4) {
                         u32x4_t g[NK][4];
 #pragma unroll
-                        for (int ks = 0; ks < NK; ++ks) tload(ct, ks, g[ks]);
+                        for (int ks = 0; ks < NK; ++ks) tload(ct, ks, te(ks), g[ks]);
                         i32x4 bq[NK][4];
                         transpose(g, bq);
                         i32x4 acc[4];
@@ -1248,7 +1278,8 @@ __device__ __forceinline__ void vblend_block(uint32_t* __restrict__ orow, const 
                 }
             } else {
                 // nK beyond the hoisted forms: each K step's taps and T groups
-                // loaded in turn, one accumulator per (channel, plane)
+                // loaded in turn, one accumulator per (channel, plane) (and the
+                // K step's trim entry: nK has no bound here to keep them all)
                 for (int ct = wave; ct < ctiles; ct += 4) {
                     i32x4 acc[4][3];
 #pragma unroll
@@ -1263,7 +1294,7 @@ __device__ __forceinline__ void vblend_block(uint32_t* __restrict__ orow, const 
 #pragma unroll
                         for (int q = 0; q < 3; ++q) a[q] = __builtin_bit_cast(i32x4, tt.blk[th.z + tap_dense_block(ks, q, lane)]);
                         u32x4_t g[4];
-                        tload(ct, ks, g);
+                        tload(ct, ks, tentry(ks), g);
 #pragma unroll
                         for (int c = 0; c < 4; ++c) {
                             const i32x4 bq = vb_bop(g, c);
@@ -1379,12 +1410,14 @@ template <bool MAGIC>
 __global__ void __launch_bounds__(256) IPP_VB_ATTR
 k_pipe_vblend_mfma(const uint8_t* __restrict__ tmp, const uint8_t* __restrict__ bg, uint8_t* __restrict__ dst,
                    const int32_t* __restrict__ coefs, const ipp_pipe_desc* __restrict__ descs, FastDiv tiles_y,
-                   int ov_w_max) {
+                   int ov_w_max, const uint16_t* __restrict__ trim, int trim_stride) {
     extern __shared__ __attribute__((aligned(16))) uint32_t orow[];  // [kBandRows][orow_stride(ov_w_max)] (+ 256 divisors)
     const uint32_t b = xcd_remap(blockIdx.x, gridDim.x);
     const int im = (int)fdiv(b, tiles_y);
     const int ty = (int)(b - (uint32_t)im * tiles_y.d);
-    vblend_block<MAGIC>(orow, tmp, bg, dst, coefs, descs, im, ty, ov_w_max);
+    // (trim: the H launch's trim table, trim_stride entries per item, or null)
+    vblend_block<MAGIC>(orow, tmp, bg, dst, coefs, descs, im, ty, ov_w_max,
+                        trim ? trim + (int64_t)im * trim_stride : nullptr);
 }
 
 // The same block over one image pointer (a scene's layers >= 1): reads the
@@ -1397,12 +1430,14 @@ k_pipe_vblend_over(const uint8_t* __restrict__ tmp, uint8_t* img, const int32_t*
     const uint32_t b = xcd_remap(blockIdx.x, gridDim.x);
     const int im = (int)fdiv(b, tiles_y);
     const int ty = (int)(b - (uint32_t)im * tiles_y.d);
-    vblend_block<MAGIC, true>(orow, tmp, img, img, coefs, descs, im, ty, ov_w_max);
+    // (no trim table: the later layers' T comes from ipp_pipe_hpass, written in full)
+    vblend_block<MAGIC, true>(orow, tmp, img, img, coefs, descs, im, ty, ov_w_max, nullptr);
 }
 
 template <int NR, bool ZONES, int CN>
 void launch_hpass(int n, int ty, hipStream_t s, const uint8_t* src, uint8_t* tmp, const int32_t* coefs,
-                  const ipp_pipe_desc* descs, const ipp_hsv_params& hp, const uint8_t* bg, uint8_t* dst) {
+                  const ipp_pipe_desc* descs, const ipp_hsv_params& hp, const uint8_t* bg, uint8_t* dst,
+                  uint16_t* trim) {
     // H pass + the background outside the overlays, per group of kCopyGroup
     // items.  bg == nullptr (ipp_pipe_hpass): no copy slabs — every block
     // index within a group is < kCopyGroup·ty, so the kernel's copy branch is
@@ -1410,33 +1445,36 @@ void launch_hpass(int n, int ty, hipStream_t s, const uint8_t* src, uint8_t* tmp
     const int64_t groups = (n + kCopyGroup - 1) / kCopyGroup;
     const uint32_t per_grp = (uint32_t)(kCopyGroup * ty + (bg ? kCopySlabs : 0));
     hipLaunchKernelGGL((k_pipe_hpass2<NR, ZONES, CN>), dim3((uint32_t)(groups * per_grp)), dim3(64 * HP_NW), 0, s,
-                       src, tmp, coefs, descs, n, fast_div((uint32_t)ty), fast_div(per_grp), hp, bg, dst);
+                       src, tmp, coefs, descs, n, fast_div((uint32_t)ty), fast_div(per_grp), hp, bg, dst, trim);
 }
 
 template <int NR>
 void launch_hpass_nr(bool zones, int cn, int n, int ty, hipStream_t s, const uint8_t* src, uint8_t* tmp,
                      const int32_t* coefs, const ipp_pipe_desc* descs, const ipp_hsv_params& hp, const uint8_t* bg,
-                     uint8_t* dst) {
+                     uint8_t* dst, uint16_t* trim) {
     if (zones) {
-        if (cn == 4) launch_hpass<NR, true, 4>(n, ty, s, src, tmp, coefs, descs, hp, bg, dst);
-        else launch_hpass<NR, true, 3>(n, ty, s, src, tmp, coefs, descs, hp, bg, dst);
+        if (cn == 4) launch_hpass<NR, true, 4>(n, ty, s, src, tmp, coefs, descs, hp, bg, dst, trim);
+        else launch_hpass<NR, true, 3>(n, ty, s, src, tmp, coefs, descs, hp, bg, dst, trim);
     } else {
-        if (cn == 4) launch_hpass<NR, false, 4>(n, ty, s, src, tmp, coefs, descs, hp, bg, dst);
-        else launch_hpass<NR, false, 3>(n, ty, s, src, tmp, coefs, descs, hp, bg, dst);
+        if (cn == 4) launch_hpass<NR, false, 4>(n, ty, s, src, tmp, coefs, descs, hp, bg, dst, trim);
+        else launch_hpass<NR, false, 3>(n, ty, s, src, tmp, coefs, descs, hp, bg, dst, trim);
     }
 }
 
 // The H launch of ipp_pipe_hpass_bgcopy (bg and dst given) and of
-// ipp_pipe_hpass (both null: no copy blocks).
+// ipp_pipe_hpass (both null: no copy blocks).  trim: the trim table of
+// ipp_pipe_hpass_bgcopy_trim (n_images rows of trim_bands(max_rows) entries),
+// or null: every T group is stored.
 int hpass_entry(const uint8_t* src, uint8_t* tmp, const int32_t* coefs, const ipp_pipe_desc* descs, int32_t n_images,
                 int32_t max_out_w, int32_t max_rows, int32_t src_cn, const ipp_hsv_params* hsv, int32_t tap_format,
-                const uint8_t* bg, uint8_t* dst, void* stream) {
+                const uint8_t* bg, uint8_t* dst, uint16_t* trim, void* stream) {
     if (n_images == 0) return IPP_OK;
     if (!src || !tmp || !coefs || !descs || !hsv || n_images < 0 || max_out_w <= 0 || max_rows <= 0)
         return IPP_E_ARG;
     if (src_cn != 3 && src_cn != 4) return IPP_E_ARG;
     if (tap_format != IPP_TAPS_MFMA) return IPP_E_ARG;
     const int ty = (max_rows + HR - 1) / HR;  // one block per 16-row band
+    static_assert(HR == kBandRows, "an H band is a trim table entry (trim_bands)");
     if ((int64_t)(kCopyGroup * ty + kCopySlabs) * ((n_images + kCopyGroup - 1) / kCopyGroup) >= INT32_MAX)
         return IPP_E_ARG;
     hipStream_t s = (hipStream_t)stream;
@@ -1449,21 +1487,21 @@ int hpass_entry(const uint8_t* src, uint8_t* tmp, const int32_t* coefs, const ip
     // A range that never matches: lo_v = 1 > hi_v = 0 (cv::inRange's empty range).
     const ipp_hsv_range never = ipp_hsv_range{{0, 0, 1}, {180, 255, 0}, {0, 0, 0, 0}};
     switch (hsv->n_ranges) {
-        case 1: launch_hpass_nr<1>(zones, cn, n, ty, s, src, tmp, coefs, descs, *hsv, bg, dst); break;
-        case 2: launch_hpass_nr<2>(zones, cn, n, ty, s, src, tmp, coefs, descs, *hsv, bg, dst); break;
-        case 3: launch_hpass_nr<3>(zones, cn, n, ty, s, src, tmp, coefs, descs, *hsv, bg, dst); break;
-        case 4: launch_hpass_nr<4>(zones, cn, n, ty, s, src, tmp, coefs, descs, *hsv, bg, dst); break;
+        case 1: launch_hpass_nr<1>(zones, cn, n, ty, s, src, tmp, coefs, descs, *hsv, bg, dst, trim); break;
+        case 2: launch_hpass_nr<2>(zones, cn, n, ty, s, src, tmp, coefs, descs, *hsv, bg, dst, trim); break;
+        case 3: launch_hpass_nr<3>(zones, cn, n, ty, s, src, tmp, coefs, descs, *hsv, bg, dst, trim); break;
+        case 4: launch_hpass_nr<4>(zones, cn, n, ty, s, src, tmp, coefs, descs, *hsv, bg, dst, trim); break;
         case 5: case 6: {
             ipp_hsv_params q = *hsv;  // pad with never-matching ranges (lo > hi in v)
             for (int k = q.n_ranges; k < 6; ++k) q.r[k] = never;
-            launch_hpass_nr<6>(zones, cn, n, ty, s, src, tmp, coefs, descs, q, bg, dst);
+            launch_hpass_nr<6>(zones, cn, n, ty, s, src, tmp, coefs, descs, q, bg, dst, trim);
             break;
         }
         default: {
             if (hsv->n_ranges > IPP_MAX_HSV_RANGES) return IPP_E_ARG;
             ipp_hsv_params q = *hsv;
             for (int k = q.n_ranges; k < IPP_MAX_HSV_RANGES; ++k) q.r[k] = never;
-            launch_hpass_nr<IPP_MAX_HSV_RANGES>(zones, cn, n, ty, s, src, tmp, coefs, descs, q, bg, dst);
+            launch_hpass_nr<IPP_MAX_HSV_RANGES>(zones, cn, n, ty, s, src, tmp, coefs, descs, q, bg, dst, trim);
             break;
         }
     }
@@ -1479,14 +1517,26 @@ extern "C" int ipp_pipe_hpass_bgcopy(const uint8_t* src, uint8_t* tmp, const int
                                      int32_t tap_format, const uint8_t* bg, uint8_t* dst, void* stream) {
     if (n_images == 0) return IPP_OK;
     if (!bg || !dst) return IPP_E_ARG;
-    return hpass_entry(src, tmp, coefs, descs, n_images, max_out_w, max_rows, src_cn, hsv, tap_format, bg, dst, stream);
+    return hpass_entry(src, tmp, coefs, descs, n_images, max_out_w, max_rows, src_cn, hsv, tap_format, bg, dst, nullptr,
+                       stream);
+}
+
+extern "C" int ipp_pipe_hpass_bgcopy_trim(const uint8_t* src, uint8_t* tmp, const int32_t* coefs,
+                                          const ipp_pipe_desc* descs, int32_t n_images, int32_t max_out_w,
+                                          int32_t max_rows, int32_t src_cn, const ipp_hsv_params* hsv,
+                                          int32_t tap_format, const uint8_t* bg, uint8_t* dst, uint16_t* trim,
+                                          void* stream) {
+    if (n_images == 0) return IPP_OK;
+    if (!bg || !dst) return IPP_E_ARG;
+    return hpass_entry(src, tmp, coefs, descs, n_images, max_out_w, max_rows, src_cn, hsv, tap_format, bg, dst, trim,
+                       stream);
 }
 
 extern "C" int ipp_pipe_hpass(const uint8_t* src, uint8_t* tmp, const int32_t* coefs, const ipp_pipe_desc* descs,
                               int32_t n_images, int32_t max_out_w, int32_t max_rows, int32_t src_cn,
                               const ipp_hsv_params* hsv, int32_t tap_format, void* stream) {
     return hpass_entry(src, tmp, coefs, descs, n_images, max_out_w, max_rows, src_cn, hsv, tap_format, nullptr,
-                       nullptr, stream);
+                       nullptr, nullptr, stream);
 }
 
 extern "C" int ipp_pipe_status(int32_t* status, void* stream) {
@@ -1502,12 +1552,14 @@ extern "C" int ipp_pipe_status(int32_t* status, void* stream) {
     return IPP_OK;
 }
 
-// bg == nullptr: the in-place form (ipp_pipe_vblend_over) on dst.
+// bg == nullptr: the in-place form (ipp_pipe_vblend_over) on dst.  trim: the
+// H launch's trim table (trim_bands(max_rows) entries per item) or null.
 static int vblend_entry(const uint8_t* tmp, const uint8_t* bg, uint8_t* dst, const int32_t* coefs,
                         const ipp_pipe_desc* descs, int32_t n_images, int32_t bg_w, int32_t bg_h, int32_t max_ov_w,
-                        int32_t max_ov_h, int32_t tap_format, void* stream) {
+                        int32_t max_ov_h, int32_t tap_format, const uint16_t* trim, int32_t max_rows, void* stream) {
     if (n_images == 0) return IPP_OK;
     if (!tmp || !dst || !coefs || !descs || n_images < 0 || bg_w <= 0 || bg_h <= 0) return IPP_E_ARG;
+    if (trim && (max_rows <= 0 || !bg)) return IPP_E_ARG;
     if (tap_format != IPP_TAPS_MFMA || max_ov_w <= 0 || max_ov_w > bg_w || max_ov_h <= 0 || max_ov_h > bg_h ||
         max_ov_w > IPP_PIPE_MAX_OV_W)
         return IPP_E_ARG;
@@ -1529,12 +1581,13 @@ static int vblend_entry(const uint8_t* tmp, const uint8_t* bg, uint8_t* dst, con
         IPP_CHECK_LAUNCH();
         return IPP_OK;
     }
+    const int tstride = trim ? trim_bands(max_rows) : 0;
     if (use_magic)
         hipLaunchKernelGGL(k_pipe_vblend_mfma<true>, dim3((uint32_t)nb), dim3(256), rows + magic, st, tmp, bg, dst,
-                           coefs, descs, ftyb, max_ov_w);
+                           coefs, descs, ftyb, max_ov_w, trim, tstride);
     else
         hipLaunchKernelGGL(k_pipe_vblend_mfma<false>, dim3((uint32_t)nb), dim3(256), rows, st, tmp, bg, dst, coefs,
-                           descs, ftyb, max_ov_w);
+                           descs, ftyb, max_ov_w, trim, tstride);
     IPP_CHECK_LAUNCH();
     return IPP_OK;
 }
@@ -1544,11 +1597,23 @@ extern "C" int ipp_pipe_vblend_bands(const uint8_t* tmp, const uint8_t* bg, uint
                                      int32_t max_ov_w, int32_t max_ov_h, int32_t tap_format, void* stream) {
     if (n_images == 0) return IPP_OK;
     if (!bg) return IPP_E_ARG;
-    return vblend_entry(tmp, bg, dst, coefs, descs, n_images, bg_w, bg_h, max_ov_w, max_ov_h, tap_format, stream);
+    return vblend_entry(tmp, bg, dst, coefs, descs, n_images, bg_w, bg_h, max_ov_w, max_ov_h, tap_format, nullptr, 0,
+                        stream);
+}
+
+extern "C" int ipp_pipe_vblend_bands_trim(const uint8_t* tmp, const uint8_t* bg, uint8_t* dst, const int32_t* coefs,
+                                          const ipp_pipe_desc* descs, int32_t n_images, int32_t bg_w, int32_t bg_h,
+                                          int32_t max_ov_w, int32_t max_ov_h, int32_t tap_format,
+                                          const uint16_t* trim, int32_t max_rows, void* stream) {
+    if (n_images == 0) return IPP_OK;
+    if (!bg) return IPP_E_ARG;
+    return vblend_entry(tmp, bg, dst, coefs, descs, n_images, bg_w, bg_h, max_ov_w, max_ov_h, tap_format, trim,
+                        max_rows, stream);
 }
 
 extern "C" int ipp_pipe_vblend_over(const uint8_t* tmp, uint8_t* dst, const int32_t* coefs,
                                     const ipp_pipe_desc* descs, int32_t n_images, int32_t bg_w, int32_t bg_h,
                                     int32_t max_ov_w, int32_t max_ov_h, int32_t tap_format, void* stream) {
-    return vblend_entry(tmp, nullptr, dst, coefs, descs, n_images, bg_w, bg_h, max_ov_w, max_ov_h, tap_format, stream);
+    return vblend_entry(tmp, nullptr, dst, coefs, descs, n_images, bg_w, bg_h, max_ov_w, max_ov_h, tap_format, nullptr,
+                        0, stream);
 }

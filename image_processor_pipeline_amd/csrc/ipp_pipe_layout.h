@@ -56,6 +56,9 @@
 // at base + g·pitch + 16·x', channel c = dword c (alpha = dword 3).  An H-pass
 // MFMA lane writes exactly one group; a V-pass lane reads four (16 T rows of
 // all four channels); a K step = 64 T rows = 16 row groups.
+// T is sparse after ipp_pipe_hpass_bgcopy_trim with a trim table: the groups
+// the table marks constant (trim_const below; every byte of them is 0x80) are
+// not stored, and the readers that take the table do not load them.
 //
 // Bands: composite rows outside the overlay's 16-row bands [vb0, vb1) are
 // plain copies of the background (Paste.c leaves them untouched).  The H
@@ -147,6 +150,42 @@ IPP_HD constexpr int t_pitch_vecs(int pitch_bytes) { return pitch_bytes >> 4; } 
 IPP_HD constexpr int64_t t_groups(int rows, int nkb_v) {
     return (((int64_t)(rows + 15) / 16) * 16 + kKStepCols * nkb_v + 16) / kTGroupRows;
 }
+
+// ---- trim table -----------------------------------------------------------------
+// The H launch's record of its fill trim (ipp_pipe.hip hpass_block), one
+// 16-bit entry per (item, H band): trim[item·trim_bands(max_rows) + band] =
+// lo | hi << 8, the band's swept column tiles [lo, hi).  The T groups of the
+// band's other column tiles hold 0x80 in every byte and, with a table, are
+// neither stored nor loaded.  A block that does not trim writes (0, its tile
+// count); a tile count of 255 or more is stored as 255 = no upper bound (only
+// items of at most 64 tiles trim).  Bands at or past the item's lines have no
+// entry: their T rows lie past every tap's support and are constant to a
+// reader.  The table is the one source of the bounds: they come out of
+// float32 arithmetic in hpass_block, which no reader repeats.
+//
+// H band hb = T rows 16·hb .. 16·hb + 15 of the item.  A V tile's window
+// starts at T row K0, a multiple of 16 (above: K0 is rounded down to 16), and
+// the V axis's input index 0 is T row 0: the planner gives the axis shift =
+// the H desc's line0 (ipp_plan.cpp; both 0 when an axis is the identity), and
+// T row r is M row line0 + r.  So the four groups a V lane reads in K step ks
+// (rows K0 + 64·ks + 16·(lane >> 4) .. + 15) are exactly H band
+// trim_v_band(K0, ks, lane).
+constexpr int kTrimOpen = 255;                       // hi: no upper bound
+constexpr uint32_t kTrimNone = kTrimOpen << 8;       // no group is constant (no table given)
+constexpr uint32_t kTrimAll = 0;                     // every group is constant (a band past the item's lines)
+IPP_HD constexpr int trim_bands(int max_rows) { return (max_rows + kBandRows - 1) / kBandRows; }
+IPP_HD constexpr uint32_t trim_entry(int lo, int hi) { return (uint32_t)lo | (uint32_t)imin(hi, kTrimOpen) << 8; }
+// are the T groups of column tile ct constant in the band of entry e?
+IPP_HD constexpr bool trim_const(uint32_t e, int ct) {
+    return ct < (int)(e & 255u) || (ct >= (int)(e >> 8 & 255u) && (e >> 8 & 255u) != (uint32_t)kTrimOpen);
+}
+IPP_HD constexpr int trim_v_band(int k0, int ks, int lane) { return (k0 >> 4) + (kKStepCols / kBandRows) * ks + (lane >> 4); }
+static_assert(kKStepCols == 4 * kBandRows && kBandRows == 4 * kTGroupRows,
+              "a V lane's four groups of a K step are one H band, a K step is four");
+static_assert(trim_const(trim_entry(2, 5), 1) && !trim_const(trim_entry(2, 5), 2) && !trim_const(trim_entry(2, 5), 4) &&
+                  trim_const(trim_entry(2, 5), 5) && trim_const(kTrimAll, 0) && !trim_const(kTrimNone, 300) &&
+                  !trim_const(trim_entry(0, 300), 299),
+              "trim_const");
 
 static_assert(tap_block_word(1) == 20 && tap_bias_word(1) == 4, "blocks begin at word 20·T, bias at 4·T (ipp.h)");
 static_assert((1 << kTileOutLog2) == kTileOut && (1 << kTGroupRowsLog2) == kTGroupRows, "the shifts");

@@ -332,24 +332,36 @@ def overlap_bounds(n: int, parts: int, ratio: float = 1.0, group: int = N.IPP_PI
     return b
 
 
+def trim_bands(plan: PipePlan) -> int:
+    """Entries per descriptor of the H launch's trim table (ipp.h): one per 16-row band of max_rows."""
+    return (plan.max_rows + 15) // 16
+
+
 def _launch_hpass_bgcopy(lib, plan: PipePlan, src: int, tmp: int, coefs: int, descs: int, n: int, bgs: int, out: int,
-                         stream: int) -> None:
-    """The H launch (ipp_pipe_hpass_bgcopy) of `n` descriptors at device
-    address `descs`; the other buffers are device addresses too."""
-    N.check(lib.ipp_pipe_hpass_bgcopy(src, tmp, coefs, descs, n, plan.max_out_w, plan.max_rows, 3, N.np_ptr(plan.hsv),
-                                      plan.tap_format, bgs, out, stream), "ipp_pipe_hpass_bgcopy")
+                         stream: int, trim: Optional[int] = None) -> None:
+    """The H launch (ipp_pipe_hpass_bgcopy_trim) of `n` descriptors at device
+    address `descs`; the other buffers are device addresses too.  `trim`: the
+    address of the range's rows of the trim table; the launch then leaves the
+    constant T groups unstored, and only the V and box launches given the
+    same rows may read tmp.  None: T is written in full."""
+    N.check(lib.ipp_pipe_hpass_bgcopy_trim(src, tmp, coefs, descs, n, plan.max_out_w, plan.max_rows, 3,
+                                           N.np_ptr(plan.hsv), plan.tap_format, bgs, out, trim, stream),
+            "ipp_pipe_hpass_bgcopy_trim")
 
 
 def _launch_vblend_bands(lib, plan: PipePlan, tmp: int, bgs: int, out: int, coefs: int, descs: int, n: int,
-                         stream: int) -> None:
-    """The V launch (ipp_pipe_vblend_bands) of the same descriptor range."""
-    N.check(lib.ipp_pipe_vblend_bands(tmp, bgs, out, coefs, descs, n, plan.bg_w, plan.bg_h, plan.max_ov_w,
-                                      plan.max_ov_h, plan.tap_format, stream), "ipp_pipe_vblend_bands")
+                         stream: int, trim: Optional[int] = None) -> None:
+    """The V launch (ipp_pipe_vblend_bands_trim) of the same descriptor range
+    (`trim` as the H launch had it)."""
+    N.check(lib.ipp_pipe_vblend_bands_trim(tmp, bgs, out, coefs, descs, n, plan.bg_w, plan.bg_h, plan.max_ov_w,
+                                           plan.max_ov_h, plan.tap_format, trim, plan.max_rows, stream),
+            "ipp_pipe_vblend_bands_trim")
 
 
 class _Runner:
-    """What PipeRunner and SceneRunner (scenes.py) keep on the device: the plan's descriptors, its taps and
-    the H pass's scratch.  `plan` is a PipePlan, or a ScenePlan with one in ``pipe``."""
+    """What PipeRunner and SceneRunner (scenes.py) keep on the device: the plan's descriptors, its taps, the
+    H pass's scratch and the trim table beside it (one row per descriptor; PipeRunner's launches use it, a
+    scene's T is written in full).  `plan` is a PipePlan, or a ScenePlan with one in ``pipe``."""
 
     def __init__(self, plan, device):
         pipe = getattr(plan, "pipe", plan)
@@ -358,12 +370,17 @@ class _Runner:
         self.descs = _to_dev(plan.descs, self.device)
         self.coefs, self.host_tiles = plan_taps(pipe, self.device)
         self.tmp = torch.empty(pipe.tmp_bytes, dtype=torch.uint8, device=self.device)
+        self.trim = torch.empty((len(plan.descs), trim_bands(pipe)), dtype=torch.int16, device=self.device)
         self.lib = N.load()
         self._hpass_done = False   # an H launch has filled tmp (the box and map launches need it)
 
     def _dptr(self, d0: int) -> int:
         """Device address of descriptor d0."""
         return self.descs.data_ptr() + d0 * self.plan.descs.itemsize
+
+    def _tptr(self, d0: int) -> int:
+        """Device address of descriptor d0's row of the trim table."""
+        return self.trim.data_ptr() + d0 * self.trim.stride(0) * self.trim.element_size()
 
     def _check_tensors(self, caller: str, src: torch.Tensor, bgs: torch.Tensor, out: torch.Tensor) -> None:
         """The entry points that take tensors hand their raw pointers to the
@@ -390,7 +407,8 @@ class PipeRunner(_Runner):
         p = self.plan
         i0, n = items if items is not None else (0, len(p.descs))
         _launch_hpass_bgcopy(self.lib, p, src.data_ptr(), self.tmp.data_ptr(), self.coefs.data_ptr(),
-                             self._dptr(i0), n, bgs.data_ptr(), out.data_ptr(), _stream(self.device))
+                             self._dptr(i0), n, bgs.data_ptr(), out.data_ptr(), _stream(self.device),
+                             trim=self._tptr(i0))
         self._hpass_done = True
 
     def overlay_bboxes(self, alpha_min: int = 1, items=None) -> np.ndarray:
@@ -417,9 +435,10 @@ class PipeRunner(_Runner):
             raise N.NativeError("PipeRunner.overlay_bboxes: no H launch (hpass_bgcopy) has run on this runner")
         p = self.plan
         bbox = torch.empty(4 * max(n, 0), dtype=torch.int32, device=self.device)
-        N.check(self.lib.ipp_pipe_overlay_bbox(self.tmp.data_ptr(), self.coefs.data_ptr(), self._dptr(i0), n,
-                                               p.max_ov_w, p.max_ov_h, alpha_min, p.tap_format, bbox.data_ptr(),
-                                               _stream(self.device)), "ipp_pipe_overlay_bbox")
+        N.check(self.lib.ipp_pipe_overlay_bbox_trim(self.tmp.data_ptr(), self.coefs.data_ptr(), self._dptr(i0), n,
+                                                    p.max_ov_w, p.max_ov_h, alpha_min, p.tap_format, bbox.data_ptr(),
+                                                    self._tptr(i0), p.max_rows, _stream(self.device)),
+                "ipp_pipe_overlay_bbox_trim")
         return bbox
 
     def _bboxes_by_item(self, bbox: torch.Tensor, i0: int, n: int) -> np.ndarray:
@@ -436,7 +455,7 @@ class PipeRunner(_Runner):
         p = self.plan
         i0, n = items if items is not None else (0, len(p.descs))
         _launch_vblend_bands(self.lib, p, self.tmp.data_ptr(), bgs.data_ptr(), out.data_ptr(), self.coefs.data_ptr(),
-                             self._dptr(i0), n, _stream(self.device))
+                             self._dptr(i0), n, _stream(self.device), trim=self._tptr(i0))
 
     def run_overlapped(self, src: torch.Tensor, bgs: torch.Tensor, out: torch.Tensor, parts: int,
                        ratio: float = 1.0) -> None:
@@ -548,6 +567,7 @@ class PipeStream:
         bufs = {"descs": self._buf(slot, "descs", plan.descs.nbytes),
                 "coefs": self._buf(slot, "coefs", 4 * (plan.coef_words + 4096)),
                 "tmp": self._buf(slot, "tmp", plan.tmp_bytes),
+                "trim": self._buf(slot, "trim", 2 * len(plan.descs) * trim_bands(plan)),
                 "scratch": self._buf(slot, "scratch", self.lib.ipp_pipe_taps_scratch_bytes(len(plan.axes)))}
         stats = np.zeros(2, np.int64)
         side = slot["side"]
@@ -588,9 +608,10 @@ class PipeStream:
                     ev[0].record(main)
                 _launch_hpass_bgcopy(self.lib, plan, src.data_ptr(), b["tmp"].data_ptr(), b["coefs"].data_ptr(),
                                      b["descs"].data_ptr(), len(plan.descs), bgs.data_ptr(), out.data_ptr(),
-                                     main.cuda_stream)
+                                     main.cuda_stream, trim=b["trim"].data_ptr())
                 _launch_vblend_bands(self.lib, plan, b["tmp"].data_ptr(), bgs.data_ptr(), out.data_ptr(),
-                                     b["coefs"].data_ptr(), b["descs"].data_ptr(), len(plan.descs), main.cuda_stream)
+                                     b["coefs"].data_ptr(), b["descs"].data_ptr(), len(plan.descs), main.cuda_stream,
+                                     trim=b["trim"].data_ptr())
                 if ev:
                     ev[1].record(main)
                     self.events.append(ev)

@@ -280,6 +280,36 @@ int ipp_pipe_overlay_bbox(const uint8_t* tmp, const int32_t* coefs, const ipp_pi
                           int32_t n_images, int32_t max_ov_w, int32_t max_ov_h,
                           int32_t alpha_min, int32_t tap_format, int32_t* bbox, void* stream);
 
+/* The same three launches with the H launch's trim table.  Where the HSV
+ * ranges exclude black and there are no zones, a 16-row band of an item's T
+ * is the constant 0x80 in its leading and trailing 16-column tiles whose
+ * input window holds only the rotation's fill (items of at most 64 tiles).
+ * trim: device uint16[n_images][(max_rows + 15) / 16], written by the H
+ * launch, one entry lo | hi << 8 per (descriptor, band): the band's other
+ * tiles [lo, hi) (hi 255: no upper bound; a band that does not trim has lo 0
+ * and hi = its tile count; bands past the item's rows have no entry).  With
+ * a table the H launch does not store the constant 16-B groups and the V
+ * launch and the box launch do not load them: tmp is then SPARSE, and only
+ * these two entry points, given the same table and the same max_rows, may
+ * read it (every other reader of tmp takes the T of ipp_pipe_hpass_bgcopy or
+ * ipp_pipe_hpass, written in full).  A launch over a sub-range of the
+ * descriptors takes trim advanced by the same number of rows as descs.
+ * trim == NULL: exactly the entry points above (max_rows is ignored). */
+int ipp_pipe_hpass_bgcopy_trim(const uint8_t* src, uint8_t* tmp, const int32_t* coefs,
+                               const ipp_pipe_desc* descs, int32_t n_images,
+                               int32_t max_out_w, int32_t max_rows, int32_t src_cn,
+                               const ipp_hsv_params* hsv, int32_t tap_format,
+                               const uint8_t* bg, uint8_t* dst, uint16_t* trim, void* stream);
+int ipp_pipe_vblend_bands_trim(const uint8_t* tmp, const uint8_t* bg, uint8_t* dst,
+                               const int32_t* coefs, const ipp_pipe_desc* descs, int32_t n_images,
+                               int32_t bg_w, int32_t bg_h, int32_t max_ov_w, int32_t max_ov_h,
+                               int32_t tap_format, const uint16_t* trim, int32_t max_rows,
+                               void* stream);
+int ipp_pipe_overlay_bbox_trim(const uint8_t* tmp, const int32_t* coefs, const ipp_pipe_desc* descs,
+                               int32_t n_images, int32_t max_ov_w, int32_t max_ov_h,
+                               int32_t alpha_min, int32_t tap_format, int32_t* bbox,
+                               const uint16_t* trim, int32_t max_rows, void* stream);
+
 /* ------------------------------------------------------------------------ */
 /* Scenes: K overlays (layers 0 .. K-1, layer K-1 on top) pasted in layer     */
 /* order onto one composite, each by paste(ov, (x, y), ov) onto the result of */
