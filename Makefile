@@ -5,7 +5,7 @@ ARCH ?= gfx950
 PKG := image_processor_pipeline_amd
 CSRC := $(PKG)/csrc
 SRCS := $(CSRC)/ipp_gather.hip $(CSRC)/ipp_hsv.hip $(CSRC)/ipp_resample.hip $(CSRC)/ipp_pipe.hip \
-        $(CSRC)/ipp_ccl.hip $(CSRC)/ipp_util.hip $(CSRC)/ipp_bilinear.hip \
+        $(CSRC)/ipp_pipe_vblend.hip $(CSRC)/ipp_ccl.hip $(CSRC)/ipp_util.hip $(CSRC)/ipp_bilinear.hip \
         $(CSRC)/ipp_enhance.hip $(CSRC)/ipp_taps.hip $(CSRC)/ipp_label.hip $(CSRC)/ipp_contour.hip \
         $(CSRC)/ipp_simplify.hip
 HOST_SRCS := $(CSRC)/ipp_host.cpp $(CSRC)/ipp_plan.cpp
@@ -19,8 +19,9 @@ HOSTFLAGS := -O2 -std=c++17 -fPIC -Iinclude
 all: $(LIB) $(OBJDIR)/ipp_pipe.s
 
 # The H pass's ISA, for the static check of its hand-waited gathers
-# (tools/asm_hazard.py, tests/test_asm_gather_hazard.py).
-$(OBJDIR)/ipp_pipe.s: $(CSRC)/ipp_pipe.hip $(HDRS) | $(OBJDIR)
+# (tools/asm_hazard.py, tests/test_asm_gather_hazard.py).  Any kernel file's
+# ISA: make build/obj/<file>.s (the resource tests use it when it is fresh).
+$(OBJDIR)/%.s: $(CSRC)/%.hip $(HDRS) | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -S --cuda-device-only $< -o $@
 
 # Pillow's BILINEAR (double), Blend (float) and LANCZOS tap (double)
@@ -53,9 +54,11 @@ variant:
 	for f in $(HOST_SRCS); do g++ $(HOSTFLAGS) -c $$f -o variants/$(NAME)/obj/$$(basename $$f .cpp).o || exit 1; done
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o variants/$(NAME)/libipp.so variants/$(NAME)/obj/*.o -lpthread
 
-# A variant that differs only in one kernel file (F, default ipp_pipe): that
-# file rebuilt with VFLAGS, linked with the in-tree objects of the others.
-#   make kvariant NAME=kb2 VFLAGS=-DIPP_HP_BANDS=2 [F=ipp_ccl]
+# A variant that differs only in one kernel file (F, default ipp_pipe, the H
+# launch): that file rebuilt with VFLAGS, linked with the in-tree objects of
+# the others.
+#   make kvariant NAME=slabs6 VFLAGS=-DIPP_COPY_SLABS=6
+#   make kvariant NAME=wpe2 VFLAGS=-DIPP_VB_WPE=2 F=ipp_pipe_vblend   (the V launch; or F=ipp_ccl, ...)
 F ?= ipp_pipe
 kvariant: $(OBJS)
 	mkdir -p variants/$(NAME)/obj

@@ -4,7 +4,7 @@
 //   ipp_pipe_overlay_bbox: the tight box of each item's resized overlay in the
 //   fused pipe.  The resized overlay is never materialised there: its alpha
 //   exists only as T (the H pass's scratch) combined with the V-axis tap
-//   tiles.  The kernel is the V pass of ipp_pipe.hip's k_pipe_vblend_mfma
+//   tiles.  The kernel is the V pass of ipp_pipe_vblend.hip's k_pipe_vblend_mfma
 //   restricted to channel 3: it reads dword 3 of each 16-B T group and the
 //   band's tap tile, and writes nothing but the boxes.
 //
@@ -68,7 +68,7 @@ __device__ __forceinline__ void bbox_commit(int32_t* __restrict__ row, int xmin,
 // one item; its four waves stride over the 16-column tiles.
 //
 // The band, tap tile and T group addressing is ipp_pipe_layout.h's, as in
-// ipp_pipe.hip's vblend_block (tests/test_gpu_labels.py compares the boxes
+// ipp_pipe_vblend.hip's vblend_block (tests/test_gpu_labels.py compares the boxes
 // with the resized overlay's alpha).
 //   A = the tile's taps, one byte plane per MFMA (lane l: row l&15, T rows
 //       16(l>>4)..+15 of the K step);

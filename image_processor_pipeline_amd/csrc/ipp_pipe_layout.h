@@ -1,9 +1,9 @@
 // ipp_pipe_layout.h — the one statement of the fused pipe's shared layouts:
 // the MFMA tap tiles of an axis, the H pass's scratch T, and the 16-row bands
 // and 16-pixel column groups of a composite.  Its writers (ipp_host.cpp,
-// ipp_taps.hip), its readers (ipp_pipe.hip, ipp_label.hip) and the planner
-// that sizes the buffers (ipp_plan.cpp) take every number of the format from
-// here.  Plain C++ for the host files, __host__ __device__ under hipcc.
+// ipp_taps.hip), its readers (ipp_pipe.hip, ipp_pipe_vblend.hip,
+// ipp_label.hip) and the planner that sizes the buffers (ipp_plan.cpp) take
+// every number of the format from here. Plain C++ for the host files, __host__ __device__ under hipcc.
 //
 // A change of a number (a count, a size, an offset) is made in this file
 // alone.  A change of a formula's shape is made in the functions below and,
@@ -223,6 +223,19 @@ template <typename V>
 __device__ __forceinline__ const V* t_group(const V* base, int pitch, int group, int x) {
     static_assert(sizeof(V) == kTGroupBytes, "a pointer to whole groups");
     return base + x + (int64_t)group * pitch;
+}
+
+// Column split of the band rows [vb0, vb1): on dense, 16-B aligned images
+// whose width is a multiple of 16, the H pass's copy blocks also write the
+// band rows' 16-pixel groups outside [gx0, gx1) (the groups the overlay
+// touches) and the V pass visits only [gx0, gx1).  Both kernels decide it
+// with this one predicate: the one above (ipp_plan.cpp counts the bytes by
+// it) with the two images' alignment.
+__device__ __forceinline__ bool band_cols_split(const ipp_paste_desc& p, const uint8_t* bg, const uint8_t* dst,
+                                                int& gx0, int& gx1) {
+    return pipe_layout::band_cols_split(p, gx0, gx1, [&] {
+        return ((reinterpret_cast<uintptr_t>(bg + p.bg_off) | reinterpret_cast<uintptr_t>(dst + p.dst_off)) & 15u) == 0;
+    });
 }
 #endif
 

@@ -6,43 +6,16 @@ emitted ISA of every instantiation (control-flow-aware); this test runs it on
 the build's ipp_pipe.s and on a mutation of the source that drops the
 end-of-phase-2 waits (the round-2 structure: the next chunk's sets stayed in
 flight across the loop's back edge, where the compiler copies them)."""
-import os
 import re
 import shutil
-import subprocess
-import sys
-from pathlib import Path
 
-import pytest
-
-ROOT = Path(__file__).resolve().parents[1]
-CSRC = ROOT / "image_processor_pipeline_amd" / "csrc"
-HIPCC = "/opt/rocm/bin/hipcc"
-sys.path.insert(0, str(ROOT))
-from tools import asm_hazard  # noqa: E402
-
-needs_hipcc = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
-
-
-def _compile(src: Path, out: Path, inc: Path):
-    subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", f"-I{ROOT / 'include'}",
-                    f"-I{inc}", "-S", "--cuda-device-only", str(src), "-o", str(out)],
-                   check=True, capture_output=True)
-
-
-def _asm_of_build(tmp_path) -> Path:
-    s = ROOT / "build" / "obj" / "ipp_pipe.s"
-    deps = [CSRC / "ipp_pipe.hip"] + list(CSRC.glob("*.h")) + [ROOT / "include" / "ipp.h"]
-    if s.exists() and s.stat().st_mtime >= max(d.stat().st_mtime for d in deps):
-        return s
-    out = tmp_path / "ipp_pipe.s"
-    _compile(CSRC / "ipp_pipe.hip", out, CSRC)
-    return out
+from tests.kernel_isa import CSRC, compile_isa, isa, needs_hipcc
+from tools import asm_hazard
 
 
 @needs_hipcc
-def test_hpass_gathers_never_touched_in_flight(tmp_path, capsys):
-    path = _asm_of_build(tmp_path)
+def test_hpass_gathers_never_touched_in_flight(capsys):
+    path = isa("ipp_pipe")[0]
     for pattern, least in (("k_pipe_hpass2", 24),):
         rc = asm_hazard.main(str(path), pattern)
         out = capsys.readouterr().out
@@ -63,7 +36,7 @@ def test_checker_flags_waits_left_to_the_back_edge(tmp_path, capsys):
     for h in CSRC.glob("*.h"):
         shutil.copy(h, d)
     (d / "ipp_pipe.hip").write_text(mutated)
-    _compile(d / "ipp_pipe.hip", d / "ipp_pipe.s", d)
+    compile_isa(d / "ipp_pipe.hip", d / "ipp_pipe.s", d)
     rc = asm_hazard.main(str(d / "ipp_pipe.s"))
     out = capsys.readouterr().out
     assert rc == 1 and "in-flight gather register" in out, out

@@ -1,20 +1,16 @@
 """Register/scratch/LDS budget of the contour kernels (ipp_contour.hip
-k_contour_*): compiled to ISA (CPU only) and read from the amdhsa metadata
-alone through tools/kernel_res; a resource check only."""
-import os
+k_contour_*): read from the amdhsa metadata of their ISA alone
+(tests/kernel_isa.py, CPU only); a resource check only."""
+from tests.kernel_isa import LDS_MAX, isa, needs_hipcc
 
-import pytest
-
-from tests.test_scene_kernel_resources import HIPCC, LDS_MAX, _kernels
-
-pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
+pytestmark = needs_hipcc
 
 WANT = ("k_contour_emit", "k_contour_link", "k_contour_jump", "k_contour_select", "k_contour_header",
         "k_contour_pack")
 
 
-def test_contour_kernels_no_spills_no_private_segment(tmp_path):
-    ks, _ = _kernels("ipp_contour", tmp_path)
+def test_contour_kernels_no_spills_no_private_segment():
+    _, _, ks = isa("ipp_contour")
     seen = {}
     for k in ks:
         name = k.get("name") or ""

@@ -2,44 +2,23 @@
 spills and no scratch in the pipe, CCL and gather kernels, and the H pass
 within the 128 VGPRs that give four blocks per CU (the measured occupancy
 lever: 3 blocks per CU made it 14 % slower).  Reads the amdhsa metadata of
-the device code hipcc emits (`make` writes build/obj/ipp_pipe.s; the others
-are compiled here, CPU only)."""
-import os
-import subprocess
-import sys
-from pathlib import Path
-
+the device code hipcc emits (tests/kernel_isa.py: `make` writes
+build/obj/ipp_pipe.s; the others are compiled there, CPU only)."""
 import pytest
 
-ROOT = Path(__file__).resolve().parents[1]
-CSRC = ROOT / "image_processor_pipeline_amd" / "csrc"
-HIPCC = "/opt/rocm/bin/hipcc"
-sys.path.insert(0, str(ROOT))
-from tools import kernel_res  # noqa: E402
+from tests.kernel_isa import isa, kernel_res, needs_hipcc
 
-needs_hipcc = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
-
-
-def _asm(name: str, tmp_path: Path) -> Path:
-    built = ROOT / "build" / "obj" / f"{name}.s"
-    src = CSRC / f"{name}.hip"
-    deps = [src] + list(CSRC.glob("*.h")) + [ROOT / "include" / "ipp.h"]
-    if built.exists() and built.stat().st_mtime >= max(d.stat().st_mtime for d in deps):
-        return built
-    out = tmp_path / f"{name}.s"
-    subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", f"-I{ROOT / 'include'}",
-                    f"-I{CSRC}", "-S", "--cuda-device-only", str(src), "-o", str(out)], check=True,
-                   capture_output=True)
-    return out
+# every instantiation of the two pipe files: 24 k_pipe_hpass2 (6 range counts,
+# zones, 3 or 4 channels), 4 k_pipe_vblend_* (two kernels, MAGIC or not)
+PIPE_KERNELS = {"ipp_pipe": 24, "ipp_pipe_vblend": 4}
 
 
 @needs_hipcc
 @pytest.mark.parametrize("name,hot", [("ipp_pipe", ("k_pipe_",)), ("ipp_ccl", ("k_ccl_",)),
-                                      ("ipp_gather", ("k_rotate_flip_nearest", "k_copy_rows"))])
-def test_no_spills_no_scratch(name, hot, tmp_path):
-    path = _asm(name, tmp_path)
-    ks = list(kernel_res.kernels(str(path)))
-    text = path.read_text()
+                                      ("ipp_gather", ("k_rotate_flip_nearest", "k_copy_rows")),
+                                      ("ipp_pipe_vblend", ("k_pipe_",))])
+def test_no_spills_no_scratch(name, hot):
+    _, text, ks = isa(name)
     checked = 0
     for k in ks:
         if not any(h in k.get("name", "") for h in hot):
@@ -50,12 +29,15 @@ def test_no_spills_no_scratch(name, hot, tmp_path):
         # spill slots that all went to VGPR lanes) none ever accessed
         if int(k.get("private_segment_fixed_size", 0)):
             assert "scratch_" not in kernel_res.body(text, k["name"]), k["name"]
-    assert checked > 0
+    if name in PIPE_KERNELS:
+        assert checked == PIPE_KERNELS[name]
+    else:
+        assert checked > 0
 
 
 @needs_hipcc
-def test_hpass_fits_four_blocks_per_cu(tmp_path):
-    for k in kernel_res.kernels(str(_asm("ipp_pipe", tmp_path))):
+def test_hpass_fits_four_blocks_per_cu():
+    for k in isa("ipp_pipe")[2]:
         n = k.get("name", "")
         if "k_pipe_hpass2" in n:
             regs = int(k["vgpr_count"]) + int(k.get("agpr_count", 0))

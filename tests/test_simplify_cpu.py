@@ -172,12 +172,12 @@ def test_library_exports_and_binds_the_entries():
 
 
 # --- 5: the kernels' resources ---------------------------------------------------------------------------------
-def test_simplify_kernels_no_spills_no_private_segment(tmp_path):
-    from tests.test_scene_kernel_resources import HIPCC, LDS_MAX, _kernels
+def test_simplify_kernels_no_spills_no_private_segment():
+    from tests.kernel_isa import HIPCC, LDS_MAX, isa
     if not os.path.exists(HIPCC):
         pytest.skip("hipcc not available")
     want = ("k_simplify_pack", "k_simplify")
-    ks, _ = _kernels("ipp_simplify", tmp_path)
+    _, _, ks = isa("ipp_simplify")
     seen = {}
     for k in ks:
         name = k.get("name") or ""
