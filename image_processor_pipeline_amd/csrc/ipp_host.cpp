@@ -195,7 +195,7 @@ extern "C" int ipp_gather_prepare(ipp_gather_desc* descs, int32_t n) {
         ipp_gather_desc& g = descs[i];
         g.base_off = g.src_off + (int64_t)g.in_y0 * g.src_pitch + (int64_t)g.in_x0 * g.src_cn;
         const int64_t avail = (int64_t)(g.src_h - g.in_y0) * g.src_pitch - (int64_t)g.in_x0 * g.src_cn;
-        g.lim = (uint32_t)(avail - 4);
+        g.lim = avail < 4 ? 0u : (uint32_t)(avail - 4);  // (avail = 3: a 1×1 window on the source's last pixel)
         const uint32_t sgx = (g.flip & 1) ? 0xFFFFFFFFu : 1u, sgy = (g.flip & 2) ? 0xFFFFFFFFu : 1u;
         const uint32_t sx0 = (uint32_t)(g.off_x + ((g.flip & 1) ? g.out_w - 1 : 0));
         const uint32_t sy0 = (uint32_t)(g.off_y + ((g.flip & 2) ? g.out_h - 1 : 0));

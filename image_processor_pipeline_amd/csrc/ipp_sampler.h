@@ -36,7 +36,7 @@ __device__ __forceinline__ Sampler make_sampler(const uint8_t* src, const ipp_ga
     s.base = src + g.src_off + (int64_t)g.in_y0 * g.src_pitch + (int64_t)g.in_x0 * g.src_cn;
     s.pitch = (uint32_t)g.src_pitch;
     const int64_t avail = (int64_t)(g.src_h - g.in_y0) * g.src_pitch - (int64_t)g.in_x0 * g.src_cn;
-    s.lim = (uint32_t)(avail - 4);
+    s.lim = avail < 4 ? 0u : (uint32_t)(avail - 4);
     const int sgx = (g.flip & 1) ? -1 : 1, sgy = (g.flip & 2) ? -1 : 1;
     const uint32_t sx0 = (uint32_t)(g.off_x + ((g.flip & 1) ? g.out_w - 1 : 0));
     const uint32_t sy0 = (uint32_t)(g.off_y + ((g.flip & 2) ? g.out_h - 1 : 0));

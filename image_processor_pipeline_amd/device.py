@@ -8,7 +8,7 @@ CPU fallback in the product path.
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import List, Optional, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -59,19 +59,34 @@ class GatherPlan:
     total_bytes: int
     max_w: int
     max_h: int
+    min_src_bytes: int = 0         # the source buffer must be at least this long (ipp.h: 3-channel windows)
+
+
+def gather_min_src_bytes(descs: np.ndarray) -> int:
+    """ipp.h's contract of ipp_rotate_flip_nearest: a 3-channel source is read
+    with 4-byte loads, so the buffer must reach 4 bytes from the origin of
+    every 3-channel window (from the source fields, so that it also holds for
+    descriptors with prepared = 0)."""
+    d = descs[descs["src_cn"] == 3]
+    if d.size == 0:
+        return 0
+    base = d["src_off"] + d["in_y0"].astype(np.int64) * d["src_pitch"] + d["in_x0"].astype(np.int64) * 3
+    return int(base.max()) + 4
 
 
 def plan_rotate_flip(src_dims: Sequence[Tuple[int, int, int]], angles: Sequence[float],
                      flips: Sequence[int], windows: Optional[Sequence[Tuple[int, int, int, int]]] = None,
                      src_offsets: Optional[Sequence[int]] = None, src_pitches: Optional[Sequence[int]] = None,
-                     crop_to_bbox: bool = True, row_align: int = 128) -> GatherPlan:
+                     crop_to_bbox: Union[bool, Sequence[bool]] = True, row_align: int = 128) -> GatherPlan:
     """Plan the fused gather for opaque (3-channel) or alpha-free sources.
 
     src_dims: (h, w, cn) per source; windows: (x0, y0, w, h) crop window per
     source (default: whole image).  The rotated canvas is cropped to its
-    alpha bbox analytically (opaque input ⇒ exact; rotations.py:99-109).
+    alpha bbox analytically (opaque input ⇒ exact; rotations.py:99-109);
+    crop_to_bbox is one bool for the call or one per source.
     row_align: output row pitch alignment in bytes (a multiple of 16)."""
     n = len(src_dims)
+    crop = [crop_to_bbox] * n if isinstance(crop_to_bbox, (bool, np.bool_)) else list(crop_to_bbox)
     d = np.zeros(n, N.GATHER_DESC)
     shapes, offs, pitches = [], np.zeros(n, np.int64), np.zeros(n, np.int64)
     off = 0
@@ -80,7 +95,7 @@ def plan_rotate_flip(src_dims: Sequence[Tuple[int, int, int]], angles: Sequence[
         x0, y0, iw, ih = windows[i] if windows is not None else (0, 0, w, h)
         plan = G.rotation_plan(iw, ih, float(angles[i]))
         ox, oy, ow, oh = 0, 0, plan.nw, plan.nh
-        if crop_to_bbox:
+        if crop[i]:
             bb = G.rotated_bbox(iw, ih, plan)
             if bb is not None and bb[2] > bb[0] and bb[3] > bb[1]:
                 ox, oy, ow, oh = bb[0], bb[1], bb[2] - bb[0], bb[3] - bb[1]
@@ -109,7 +124,7 @@ def plan_rotate_flip(src_dims: Sequence[Tuple[int, int, int]], angles: Sequence[
     # the per-image sampler (flip and bbox origin folded into the affine),
     # once here instead of in every block of the kernel
     N.check(N.load().ipp_gather_prepare(N.np_ptr(d), n), "ipp_gather_prepare")
-    return GatherPlan(d, shapes, offs, pitches, off, max_w, max_h)
+    return GatherPlan(d, shapes, offs, pitches, off, max_w, max_h, gather_min_src_bytes(d))
 
 
 def rotate_flip_nearest(src: torch.Tensor, plan: GatherPlan, out: Optional[torch.Tensor] = None,
@@ -117,6 +132,10 @@ def rotate_flip_nearest(src: torch.Tensor, plan: GatherPlan, out: Optional[torch
     """Launch the gather over a flat source buffer; returns the packed output."""
     _require_cuda(src, "rotate_flip_nearest")
     lib = N.load()
+    if src.numel() < plan.min_src_bytes:
+        # a 1×1 window of a 3-channel source on the buffer's last pixel: its
+        # dword load needs one byte more than the tensor has (ipp.h)
+        src = torch.cat([src.reshape(-1), src.new_zeros(plan.min_src_bytes - src.numel())])
     if out is None:
         out = torch.empty(max(plan.total_bytes, 16), dtype=torch.uint8, device=src.device)
     if descs_dev is None:

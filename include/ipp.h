@@ -65,7 +65,8 @@ typedef struct ipp_gather_desc {
      * (prepared = 1) so that every block of the gather kernels reads it
      * instead of recomputing it; with prepared = 0 the kernels compute it. */
     int64_t base_off;                 /* src_off + in_y0*src_pitch + in_x0*src_cn */
-    uint32_t lim;                     /* last byte offset from base where a 4-byte load fits */
+    uint32_t lim;                     /* last byte offset from base where a 4-byte load fits
+                                         (0 when fewer than 4 bytes are left) */
     int32_t b[6];                     /* 16.16 map with the flip and bbox origin folded in:
                                          x_src = b2 + y*b1 + x*b0, y_src = b5 + y*b4 + x*b3 */
     int32_t prepared;
@@ -77,7 +78,13 @@ int ipp_gather_prepare(ipp_gather_desc* descs, int32_t n);
 
 /* rotations.py:55 convert('RGBA') + :96 rotate(angle, expand=True) + :99-101
  * getbbox()/crop(), recadrages.py:46 margin crop, symmetry.py:114-119 flip —
- * fused gather.  Writes RGBA. */
+ * fused gather.  Writes RGBA.
+ * A 3-channel pixel is read with one 4-byte load, clamped to the last dword
+ * of the source (lim), and pixels outside the window read the window's
+ * origin.  So for every 3-channel descriptor src must extend at least 4 bytes
+ * from the window's origin, base_off + 4 <= size of src: a 1×1 window on the
+ * source's last pixel (3 bytes left) needs one byte after the source.
+ * device.rotate_flip_nearest launches from a longer copy in that case. */
 int ipp_rotate_flip_nearest(const uint8_t* src, uint8_t* dst,
                             const ipp_gather_desc* descs, int32_t n_images,
                             int32_t max_out_w, int32_t max_out_h, void* stream);

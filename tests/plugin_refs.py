@@ -3,16 +3,19 @@
 
 The kernels behind the drop-in plugins (ipp_lanczos_h/v, ipp_paste_blend,
 ipp_copy_window, ipp_hsv_mask, ipp_alpha_bbox(_min), ipp_enhance_*,
-ipp_box_pass, ipp_rotate_bilinear) are compared with ``oracle/ops.py``; the CPU
-module compares ``oracle/ops.py`` with live Pillow on the same cases.  This
-module holds
+ipp_box_pass, ipp_rotate_bilinear, ipp_rotate_flip_nearest with the sampler
+that ipp_gather_prepare sets up on the host) are compared with
+``oracle/ops.py``; the CPU module compares ``oracle/ops.py`` with live Pillow
+on the same cases.  This module holds
 
 * the seeded case tables — shapes, sizes, positions, factors, radii and α
   palettes, chosen from the kernels' tilings (64 outputs × 4 lines, 16-byte
   chunks of 1024-byte blocks, 1024- and 256-pixel tiles, 64×16 bbox tiles);
 * the image builders, each a pure function of its arguments;
 * the numpy references that ``oracle/ops.py`` has no routine for (window
-  slices with flips, the box of α ≥ alpha_min).
+  slices with flips, the box of α ≥ alpha_min);
+* ``gather_model``, the prepared gather evaluated on the host from a
+  descriptor, with the bounds of every load asserted.
 
 No GPU work here.  Sizes are (w, h) in the tables and (h, w, cn) in arrays.
 """
@@ -400,3 +403,270 @@ ROTATE_SEED = 8800
 def rotate_image(k: int) -> np.ndarray:
     w, h = ROTATE_SHAPES[k]
     return rgba_image(ROTATE_SEED + k, w, h)
+
+
+# ---------------------------------------------------------------------------
+# 9. The rotate / flip gather (ipp_rotate_flip_nearest, its sampler set up by
+#    ipp_gather_prepare): items (w, h, cn, angle, flip bits, window | None,
+#    src_pad_bytes) of ONE ragged launch.  k_rotate_flip_nearest: a block is a
+#    column of three 64×16 tiles (48 output rows), a thread owns 4 adjacent
+#    pixels; the grid is sized by the largest output, so the other items leave
+#    blocks that must exit.  The angles 0 / 180 give an output of the window's
+#    size and 90 / 270 of its transpose, so the first eleven items place the
+#    output exactly on the tile edges: widths 1 2 3 4 5 63 64 65 127 128 129,
+#    heights 1 15 16 17 47 48 49 95 96 97.
+#
+#    3-channel items are opaque and planned with the analytic box; 4-channel
+#    items carry ALPHA_PALETTE's α and are planned without the box crop.
+#    src_pad_bytes > 0 makes src_pitch = w·cn + pad, the padding filled with
+#    GATHER_SRC_JUNK.  The sources are packed back to back in the table's order
+#    whatever the launch order is, so the LAST item's source ends the buffer:
+#    it is the bottom-right 1×1 window of a 3-channel source, whose dword load
+#    needs one byte past the buffer (ipp.h).  Item 17 is the same window in the
+#    middle of the buffer.
+# ---------------------------------------------------------------------------
+
+GATHER_ITEMS = [
+    # output sizes on the tile edges, through the fast-path angles
+    (1, 1, 3, 0.0, 0, None, 0),              # 0: a 1×1 source, out 1×1
+    (2, 15, 4, 180.0, 1, None, 0),           # out 2×15
+    (16, 3, 3, 90.0, 2, None, 0),            # out 3×16
+    (4, 17, 4, 0.0, 3, None, 1),             # out 4×17 (nt = 2); every row misaligned
+    (47, 5, 3, 270.0, 3, None, 1),           # out 5×47; every row misaligned
+    (63, 48, 3, 180.0, 1, None, 0),
+    (64, 49, 4, 0.0, 2, None, 0),            # one tile row in the second row-block
+    (95, 65, 4, 90.0, 0, None, 0),           # out 65×95
+    (127, 96, 3, 0.0, 0, None, 5),
+    (97, 128, 4, 270.0, 1, None, 0),         # out 128×97
+    (129, 97, 3, 180.0, 2, None, 0),         # three tile columns, three row-blocks
+    # windows
+    (40, 30, 3, 33.3, 3, (5, 4, 29, 20), 0),     # 11: margins
+    (37, 29, 4, 117.0, 1, (3, 2, 30, 21), 7),    # margins, padded rows
+    (9, 7, 3, 0.0, 1, (0, 0, 1, 1), 0),          # 13..16: 1×1 at each corner
+    (9, 7, 4, 90.0, 2, (8, 0, 1, 1), 0),
+    (9, 7, 3, 45.0, 0, (0, 6, 1, 1), 3),
+    (9, 7, 4, 180.0, 3, (8, 6, 1, 1), 0),
+    (9, 7, 3, 270.0, 2, (8, 6, 1, 1), 0),        # 17: bottom right, 3 channels, mid-buffer
+    (21, 6, 4, 0.01, 2, (0, 5, 21, 1), 0),       # last row only
+    (21, 6, 3, 89.99, 1, (20, 0, 1, 6), 0),      # last column only
+    (21, 6, 3, 180.0, 3, (0, 5, 21, 1), 0),
+    (21, 6, 4, 90.0, 0, (20, 0, 1, 6), 2),
+    # general angles
+    (100, 180, 3, 33.3, 1, None, 0),             # 22: the largest output; alone sets max_w / max_h
+    (90, 90, 4, 45.0, 3, None, 0),
+    (13, 2, 3, 117.0, 2, None, 0),
+    (64, 64, 4, 301.7, 0, None, 0),
+    (100, 60, 3, 0.01, 0, None, 0),
+    (60, 100, 4, 89.99, 1, None, 0),
+    (120, 40, 3, -123.4, 2, None, 0),
+    (50, 70, 4, 700.0, 2, None, 0),
+    (33, 20, 4, 45.0, 1, None, 0),
+    (1, 7, 4, 33.3, 3, None, 0),
+    (7, 1, 3, 301.7, 3, None, 2),
+    (70, 33, 3, 700.0, 0, (1, 1, 66, 31), 0),
+    (31, 57, 4, -123.4, 0, (0, 3, 31, 50), 0),
+    (17, 16, 3, 45.0, 1, None, 0),
+    (3, 2, 4, 117.0, 2, None, 0),
+    (5, 4, 3, 89.99, 3, None, 0),
+    (5, 4, 3, 0.0, 0, (4, 3, 1, 1), 0),          # last: bottom right, 3 channels, ends the buffer
+]
+GATHER_SEED = 8900
+GATHER_SRC_JUNK = 0x5A
+GATHER_SENTINEL = 0xA5
+GATHER_TAIL = 256                    # sentinel bytes after the packed output
+GATHER_WIDTHS = (1, 2, 3, 4, 5, 63, 64, 65, 127, 128, 129)
+GATHER_HEIGHTS = (1, 15, 16, 17, 47, 48, 49, 95, 96, 97)
+GATHER_ANGLES = (33.3, 45.0, 117.0, 301.7, 0.01, 89.99, -123.4, 700.0)
+GATHER_ORDERS = ("listed", "reversed", "largest_mid")
+GATHER_LARGEST = 22
+GATHER_SYMS = ("o", "h", "v", "hv")  # flip bits 0..3 as oracle.ops.flip names them
+
+# The kernel's tiling, restated here and nowhere else in the tests: a block of
+# k_rotate_flip_nearest covers GATHER_TILE_W × (GATHER_TILE_H · GATHER_RT)
+# output pixels (TILE_W, TILE_H, IPP_ROT_RT of ipp_gather.hip).
+GATHER_TILE_W, GATHER_TILE_H, GATHER_RT = 64, 16, 3
+
+# Launches for the block-index arithmetic (xcd_remap, FastDiv): n_small copies
+# of a one-tile item — same shape, own pixels, flips and channel counts cycling
+# — with one three-tile-wide item in the middle, or without it.  Block counts
+# 3·(n_small + 1) = 3, 6, .., 24 visit every residue mod 8; the launches
+# without the wide item have 1 and 9 blocks.
+GATHER_SMALL = (5, 3)                        # (w, h) of the one-tile item
+GATHER_WIDE = (130, 10, 3, 180.0, 1, None, 0)
+GATHER_RESIDUE_LAUNCHES = [(n, True) for n in range(8)] + [(1, False), (9, False)]
+
+
+def gather_window(item):
+    w, h, _, _, _, win, _ = item
+    return win if win is not None else (0, 0, w, h)
+
+
+def gather_out_size(item):
+    """(out_w, out_h) of an item: exact for the fast-path angles; for the others
+    the shape of its reference."""
+    _, _, ww, wh = gather_window(item)
+    a = item[3] % 360.0
+    if a in (0.0, 180.0):
+        return ww, wh
+    if a in (90.0, 270.0):
+        return wh, ww
+    ref = gather_ref(item, np.zeros((wh, ww, item[2]), np.uint8))
+    return ref.shape[1], ref.shape[0]
+
+
+def gather_blocks(sizes):
+    """Blocks of one launch over outputs of `sizes` (w, h): ⌈max_w / 64⌉ ·
+    ⌈max_h / 48⌉ · n."""
+    mw, mh = max(s[0] for s in sizes), max(s[1] for s in sizes)
+    rows = GATHER_TILE_H * GATHER_RT
+    return -(-mw // GATHER_TILE_W) * -(-mh // rows) * len(sizes)
+
+
+def gather_last_nt(out_h: int) -> int:
+    """Live tiles (1..3) of the last row-block of an output out_h rows high."""
+    rows = GATHER_TILE_H * GATHER_RT
+    return -(-(out_h - (out_h - 1) // rows * rows) // GATHER_TILE_H)
+
+
+def gather_order(name: str, n: int = len(GATHER_ITEMS)):
+    """Launch order of the table: as listed, reversed, or with the largest
+    item moved to the middle."""
+    idx = list(range(n))
+    if name == "reversed":
+        idx.reverse()
+    elif name == "largest_mid":
+        idx.remove(GATHER_LARGEST)
+        idx.insert(len(idx) // 2, GATHER_LARGEST)
+    elif name != "listed":
+        raise ValueError(name)
+    return idx
+
+
+def gather_residue_items(k: int):
+    """The items of GATHER_RESIDUE_LAUNCHES[k]."""
+    n_small, wide = GATHER_RESIDUE_LAUNCHES[k]
+    w, h = GATHER_SMALL
+    items = [(w, h, 3 + (j + k) % 2, (0.0, 90.0, 180.0, 270.0)[(j + k) % 4], (j + 3 * k) % 4, None, j % 2)
+             for j in range(n_small)]
+    if wide:
+        items.insert(n_small // 2, GATHER_WIDE)
+    return items
+
+
+class GatherLaunch:
+    """One launch: the flat source buffer (sources in the items' own order,
+    back to back) and the arguments of device.plan_rotate_flip in launch
+    order.  wins[j] is the window of launch item j as an array."""
+
+    def __init__(self, items, seed: int, order=None):
+        order = list(range(len(items))) if order is None else list(order)
+        chunks, offs, imgs, pos = [], [], [], 0
+        for k, (w, h, cn, _, _, _, pad) in enumerate(items):
+            img = rgb_image(seed + k, w, h) if cn == 3 else rgba_image(seed + k, w, h, "palette")
+            rows = np.full((h, w * cn + pad), GATHER_SRC_JUNK, np.uint8)
+            rows[:, :w * cn] = img.reshape(h, w * cn)
+            chunks.append(rows.reshape(-1))
+            offs.append(pos)
+            imgs.append(img)
+            pos += rows.size
+        self.flat = np.concatenate(chunks)
+        self.items = [items[k] for k in order]
+        self.index = order
+        self.dims = [(it[1], it[0], it[2]) for it in self.items]
+        self.angles = [it[3] for it in self.items]
+        self.flips = [it[4] for it in self.items]
+        self.windows = [gather_window(it) for it in self.items]
+        self.src_offsets = [offs[k] for k in order]
+        self.src_pitches = [it[0] * it[2] + it[6] for it in self.items]
+        self.crop = [it[2] == 3 for it in self.items]
+        self.wins = []
+        for k, (x0, y0, ww, wh) in zip(order, self.windows):
+            self.wins.append(np.ascontiguousarray(imgs[k][y0:y0 + wh, x0:x0 + ww]))
+
+    def plan(self, D, row_align: int = 128):
+        return D.plan_rotate_flip(self.dims, self.angles, self.flips, windows=self.windows,
+                                  src_offsets=self.src_offsets, src_pitches=self.src_pitches,
+                                  crop_to_bbox=self.crop, row_align=row_align)
+
+
+def gather_launch(order: str = "listed") -> GatherLaunch:
+    return GatherLaunch(GATHER_ITEMS, GATHER_SEED, gather_order(order))
+
+
+def gather_residue_launch(k: int) -> GatherLaunch:
+    return GatherLaunch(gather_residue_items(k), GATHER_SEED + 500 + 20 * k)
+
+
+def gather_ref(item, win: np.ndarray) -> np.ndarray:
+    """The oracle's output of one item from its window: rotations.py:55,96-101
+    for an opaque source, the uncropped canvas for one with α; then the flip."""
+    cn, angle, sym = item[2], item[3], GATHER_SYMS[item[4]]
+    if cn == 3:
+        return ops.flip(ops.rotate_and_crop(ops.to_rgba(win), angle), sym)
+    return ops.flip(ops.rotate_expand_nearest(win, angle), sym)
+
+
+def gather_refs(launch: GatherLaunch):
+    return [gather_ref(it, win) for it, win in zip(launch.items, launch.wins)]
+
+
+def _i32(v):
+    """int64 array → the value an int32 register holds (wrap-around)."""
+    return np.asarray(v, np.int64).astype(np.uint32).astype(np.int32).astype(np.int64)
+
+
+def gather_sampler(desc, prepared: bool = True):
+    """(base_off, lim, b[6]) of a descriptor: its prepared fields, or what
+    ipp_sampler.h make_sampler computes from a0..a5, off_x / off_y and flip
+    for prepared = 0."""
+    if prepared:
+        assert int(desc["prepared"]) == 1
+        return int(desc["base_off"]), int(desc["lim"]), [int(v) for v in desc["b"]]
+    g = {k: int(desc[k]) for k in desc.dtype.names if k != "b"}
+    base = g["src_off"] + g["in_y0"] * g["src_pitch"] + g["in_x0"] * g["src_cn"]
+    avail = (g["src_h"] - g["in_y0"]) * g["src_pitch"] - g["in_x0"] * g["src_cn"]
+    lim = 0 if avail < 4 else avail - 4
+    sgx, sgy = (-1 if g["flip"] & 1 else 1), (-1 if g["flip"] & 2 else 1)
+    sx0 = g["off_x"] + (g["out_w"] - 1 if g["flip"] & 1 else 0)
+    sy0 = g["off_y"] + (g["out_h"] - 1 if g["flip"] & 2 else 0)
+    b = [sgx * g["a0"], sgy * g["a1"], g["a2"] + sy0 * g["a1"] + sx0 * g["a0"],
+         sgx * g["a3"], sgy * g["a4"], g["a5"] + sy0 * g["a4"] + sx0 * g["a3"]]
+    return base, lim, [int(_i32(v)) for v in b]
+
+
+def gather_model(flat: np.ndarray, desc, prepared: bool = True) -> np.ndarray:
+    """The (out_h, out_w, 4) image k_rotate_flip_nearest makes of one
+    descriptor, on the host: for output pixel (x, y)
+
+        xin = (b2 + y·b1 + x·b0) >> 16,  yin = (b5 + y·b4 + x·b3) >> 16
+
+    in int32 wrap-around arithmetic; inside [0, in_w) × [0, in_h) the pixel is
+    read at byte base_off + yin·src_pitch + xin·cn, outside it is (0, 0, 0, 0).
+    A 4-channel pixel is the dword there.  A 3-channel pixel is the dword at
+    min(off, lim), shifted right by 8·(off − min(off, lim)), with α forced to
+    255.  Every dword read must lie inside `flat` (asserted), the one at the
+    window's origin included: the kernel reads it for every lane whose pixel
+    is outside the window, and lanes past the output's edge are such lanes.
+    """
+    flat = np.asarray(flat, np.uint8).reshape(-1)
+    base, lim, b = gather_sampler(desc, prepared)
+    cn, pitch = int(desc["src_cn"]), int(desc["src_pitch"])
+    ow, oh, iw, ih = (int(desc[k]) for k in ("out_w", "out_h", "in_w", "in_h"))
+    y = np.arange(oh, dtype=np.int64)[:, None]
+    x = np.arange(ow, dtype=np.int64)[None, :]
+    xin = _i32(b[2] + y * b[1] + x * b[0]) >> 16
+    yin = _i32(b[5] + y * b[4] + x * b[3]) >> 16
+    ok = (xin >= 0) & (xin < iw) & (yin >= 0) & (yin < ih)
+    off = np.where(ok, yin * pitch + xin * cn, 0)
+    offc = np.minimum(off, lim) if cn == 3 else off
+    shift = 8 * (off - offc)
+    assert (shift < 32).all(), "a clamped load lost its pixel"
+    first, last = base, base + int(offc.max())       # offc >= 0; the origin's dword is at offset 0
+    assert 0 <= first and last + 4 <= flat.size, \
+        "the gather reads bytes [%d, %d) of a %d-byte buffer" % (first, last + 4, flat.size)
+    at = (base + offc)[..., None] + np.arange(4)
+    dword = (flat[at].astype(np.int64) << (8 * np.arange(4))).sum(axis=-1)
+    if cn == 3:
+        dword = (dword >> shift) | 0xFF000000
+    dword = np.where(ok, dword, 0)
+    return ((dword[..., None] >> (8 * np.arange(4))) & 0xFF).astype(np.uint8)

@@ -19,6 +19,10 @@ arithmetic both paths share (``div255``, ``blend16``, ``unpremultiply``,
   6. test_alpha_bbox_ragged, test_alpha_bbox_min_ragged
   7. test_enhance_*                 ipp_enhance_lsum / _color, ipp_box_pass
   8. test_rotate_bilinear_small     ipp_rotate_bilinear + box + window copy
+  9. test_gather_ragged_vs_oracle, test_gather_ragged_unprepared_vs_oracle,
+     test_gather_block_count_residues   ipp_rotate_flip_nearest over descriptors
+     from plan_rotate_flip + ipp_gather_prepare: mixed sizes, windows, pitches
+     and channel counts in one launch, into a sentinel-filled buffer
 """
 import numpy as np
 import pytest
@@ -246,3 +250,74 @@ def test_rotate_bilinear_small(D, k):
     for a in R.ROTATE_ANGLES:
         got = D.rotate_crop_bilinear(_t(img), a).cpu().numpy()
         _same(got, ops.rotate_and_crop(img, a, "bilinear"), (R.ROTATE_SHAPES[k], a))
+
+
+# --------------------------------------------------------------------------- 9. rotate / flip gather
+
+@pytest.fixture(scope="module")
+def gather_cases():
+    """{order: (launch, oracle outputs)}; the outputs are computed once, in the
+    table's order, and shared by the three orders."""
+    listed = R.gather_launch()
+    refs = R.gather_refs(listed)
+    out = {}
+    for order in R.GATHER_ORDERS:
+        launch = R.gather_launch(order)
+        out[order] = (launch, [refs[k] for k in launch.index])
+    return out
+
+
+def _gather_vs_oracle(D, launch, refs, row_align, prepared=True):
+    """One ipp_rotate_flip_nearest launch into total_bytes + 256 bytes of
+    sentinel: every item's rows equal its reference, and the row padding and
+    the tail still hold the sentinel."""
+    plan = launch.plan(D, row_align=row_align)
+    assert len(plan.descs) == len(refs) and (plan.pitches % row_align == 0).all()
+    if not prepared:
+        plan.descs["prepared"] = 0
+        plan.descs["b"] = 0x7A7A7A7A              # junk the kernel must not read
+        plan.descs["base_off"] = 1 << 40
+        plan.descs["lim"] = 0x7A7A7A7A
+    out = torch.full((plan.total_bytes + R.GATHER_TAIL,), R.GATHER_SENTINEL, dtype=torch.uint8, device=DEV)
+    buf = D.rotate_flip_nearest(_t(launch.flat), plan, out=out)
+    assert buf.data_ptr() == out.data_ptr()
+    got = buf.cpu().numpy()
+    written = np.zeros(got.size, bool)
+    for j, ((oh, ow), off, pitch, ref) in enumerate(zip(plan.shapes, plan.offsets, plan.pitches, refs)):
+        rows = got[off:off + oh * pitch].reshape(oh, pitch)
+        _same(rows[:, :4 * ow].reshape(oh, ow, 4), ref, (j, launch.items[j]))
+        written[off:off + oh * pitch].reshape(oh, pitch)[:, :4 * ow] = True
+    stray = np.flatnonzero(~written & (got != R.GATHER_SENTINEL))
+    assert stray.size == 0, ("bytes written outside the items' rows", stray[:8].tolist(), plan.total_bytes)
+
+
+@pytest.mark.parametrize("row_align", [128, 16])
+@pytest.mark.parametrize("order", R.GATHER_ORDERS)
+def test_gather_ragged_vs_oracle(D, gather_cases, order, row_align):
+    _gather_vs_oracle(D, *gather_cases[order], row_align)
+
+
+def test_gather_ragged_unprepared_vs_oracle(D, gather_cases):
+    """prepared = 0: the kernel computes the sampler per block from a0..a5,
+    off_x / off_y and flip.  Held to the oracle, not to the prepared launch."""
+    _gather_vs_oracle(D, *gather_cases["listed"], 128, prepared=False)
+
+
+@pytest.mark.parametrize("k", range(len(R.GATHER_RESIDUE_LAUNCHES)),
+                         ids=lambda k: "{}small{}".format(R.GATHER_RESIDUE_LAUNCHES[k][0],
+                                                          "+wide" if R.GATHER_RESIDUE_LAUNCHES[k][1] else ""))
+def test_gather_block_count_residues(D, k):
+    """Block counts of every residue mod 8, and of 1 and 9 (asserted from the
+    tiling in test_plugin_refs_cpu.py): a block that xcd_remap or the FastDiv
+    split loses or sends to another image leaves a tile of sentinel."""
+    launch = R.gather_residue_launch(k)
+    _gather_vs_oracle(D, launch, R.gather_refs(launch), 16)
+
+
+@pytest.mark.parametrize("angle", [0.0, 45.0, 270.0])
+def test_gather_single_pixel_rgb_tensor(D, angle):
+    """rotate_crop_single on a 1×1×3 tensor: 3 bytes, so the wrapper launches
+    from a copy one dword long (ipp.h's contract of the 4-byte load)."""
+    img = R.rgb_image(R.GATHER_SEED + 900, 1, 1)
+    got = D.rotate_crop_single(_t(img), angle, 3).cpu().numpy()
+    _same(got, ops.flip(ops.rotate_and_crop(ops.to_rgba(img), angle), "hv"), angle)

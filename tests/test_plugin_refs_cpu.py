@@ -2,7 +2,9 @@
 tests/plugin_refs.py — the expectations test_gpu_plugin_kernels.py holds the
 plugin-path kernels to — and the properties the case tables claim (tile edges,
 row phases, corners, zone sizes), so a table edited later cannot lose them
-silently.
+silently.  For the rotate / flip gather it also holds plan_rotate_flip and
+ipp_gather_prepare to the oracle through ``plugin_refs.gather_model``, which
+asserts the bounds of every load ipp_rotate_flip_nearest would make.
 """
 import numpy as np
 import pytest
@@ -314,3 +316,172 @@ def test_rotate_bilinear_oracle_equals_pillow(k):
         assert got.shape == np.asarray(exp).shape, (R.ROTATE_SHAPES[k], a)
         assert np.array_equal(got, np.asarray(exp)), (R.ROTATE_SHAPES[k], a)
     assert {0.0, 90.0, 180.0, 270.0} <= set(R.ROTATE_ANGLES) and len(R.ROTATE_ANGLES) >= 7
+
+
+# --------------------------------------------------------------------------- rotate / flip gather
+
+@pytest.fixture(scope="module")
+def D():
+    from image_processor_pipeline_amd import device
+    return device
+
+
+def _pil_gather(item, win):
+    """rotations.py:55,96-101 (the box crop with its fallback for an opaque
+    source only) and symmetry.py:114-119 through live Pillow."""
+    rot = Image.fromarray(win).convert("RGBA").rotate(item[3], expand=True)
+    if item[2] == 3:
+        bb = rot.getbbox()
+        if bb is not None and bb[2] > bb[0] and bb[3] > bb[1]:
+            rot = rot.crop(bb)
+    if item[4] & 1:
+        rot = rot.transpose(Image.Transpose.FLIP_LEFT_RIGHT)
+    if item[4] & 2:
+        rot = rot.transpose(Image.Transpose.FLIP_TOP_BOTTOM)
+    return np.asarray(rot)
+
+
+def _gather_launches():
+    return [R.gather_launch()] + [R.gather_residue_launch(k) for k in range(len(R.GATHER_RESIDUE_LAUNCHES))]
+
+
+def test_gather_oracle_equals_pillow():
+    for launch in _gather_launches():
+        for it, win, ref in zip(launch.items, launch.wins, R.gather_refs(launch)):
+            pil = _pil_gather(it, win)
+            assert ref.shape == pil.shape and np.array_equal(ref, pil), it
+
+
+def test_gather_table_claims():
+    items = R.GATHER_ITEMS
+    assert 36 <= len(items) <= 44
+    sizes = [R.gather_out_size(it) for it in items]
+    fast = [s for it, s in zip(items, sizes) if it[3] in (0.0, 90.0, 180.0, 270.0)]
+    assert set(R.GATHER_WIDTHS) <= {s[0] for s in fast} and set(R.GATHER_HEIGHTS) <= {s[1] for s in fast}
+    assert {R.gather_last_nt(s[1]) for s in fast} == {1, 2, 3}
+    assert [R.gather_last_nt(h) for h in (1, 16, 17, 32, 33, 48, 49, 97)] == [1, 1, 2, 2, 3, 3, 1, 1]
+    assert {s[0] % 4 for s in fast} == {0, 1, 2, 3}                                # tails of 1, 2, 3 pixels
+    assert {(it[2], it[4]) for it in items if it[3] in (0.0, 90.0, 180.0, 270.0)} == \
+        {(cn, f) for cn in (3, 4) for f in range(4)}
+    assert {0.0, 90.0, 180.0, 270.0} | set(R.GATHER_ANGLES) == {it[3] for it in items}
+    for a in R.GATHER_ANGLES:                                                       # each one under both plans
+        assert {it[2] for it in items if it[3] == a} == {3, 4}, a
+    cns = [it[2] for it in items]
+    assert sum(a != b for a, b in zip(cns, cns[1:])) >= len(items) // 2             # interleaved
+    # the largest output alone sets the grid, and is split 3 × 5 (no power of two)
+    mw, mh = sizes[R.GATHER_LARGEST]
+    assert all(s[0] < mw and s[1] < mh for k, s in enumerate(sizes) if k != R.GATHER_LARGEST)
+    assert (-(-mw // R.GATHER_TILE_W), -(-mh // (R.GATHER_TILE_H * R.GATHER_RT))) == (3, 5)
+    assert mw <= 210 and mh <= 210
+    # windows
+    kinds = set()
+    for k, it in enumerate(items):
+        w, h, cn, _, _, win, pad = it
+        x0, y0, ww, wh = R.gather_window(it)
+        assert 0 <= x0 and x0 + ww <= w and 0 <= y0 and y0 + wh <= h and ww > 0 and wh > 0
+        if win is None:
+            kinds.add("full")
+        elif 0 < x0 and 0 < y0 and x0 + ww < w and y0 + wh < h:
+            kinds.add("margin")
+        elif (ww, wh) == (1, 1) and (w, h) != (1, 1):
+            kinds.add(("corner", x0 == w - 1, y0 == h - 1))
+            assert x0 in (0, w - 1) and y0 in (0, h - 1)
+        elif (x0, y0, ww, wh) == (0, h - 1, w, 1):
+            kinds.add(("last_row", cn))
+        elif (x0, y0, ww, wh) == (w - 1, 0, 1, h):
+            kinds.add(("last_col", cn))
+    assert kinds >= {"full", "margin", ("corner", False, False), ("corner", True, False), ("corner", False, True),
+                     ("corner", True, True), ("last_row", 3), ("last_row", 4), ("last_col", 3), ("last_col", 4)}
+    # padded pitches: two per channel count, one of a single byte for each
+    for cn in (3, 4):
+        pads = [it[6] for it in items if it[2] == cn and it[6] > 0]
+        assert len(pads) >= 2 and 1 in pads, cn
+    # the 3-channel bottom-right 1×1 window, tight rows: mid-buffer and as the buffer's last bytes
+    tail3 = [k for k, it in enumerate(items)
+             if it[2] == 3 and it[6] == 0 and R.gather_window(it) == (it[0] - 1, it[1] - 1, 1, 1)]
+    assert tail3[-1] == len(items) - 1 and any(0 < k < len(items) - 1 for k in tail3)
+    launch = R.gather_launch()
+    assert launch.flat.size == launch.src_offsets[-1] + 3 * items[-1][0] * items[-1][1]
+    assert any(o % 2 for o in launch.src_offsets) and any(o % 4 == 0 for o in launch.src_offsets[1:])
+    assert (launch.flat == R.GATHER_SRC_JUNK).sum() >= sum(it[6] * it[1] for it in items)
+    # the three orders
+    n = len(items)
+    orders = [R.gather_order(o) for o in R.GATHER_ORDERS]
+    assert all(sorted(o) == list(range(n)) for o in orders) and len({tuple(o) for o in orders}) == 3
+    assert orders[0] == list(range(n)) and orders[1] == orders[0][::-1]
+    assert orders[2].index(R.GATHER_LARGEST) == (n - 1) // 2 and orders[0].index(R.GATHER_LARGEST) != (n - 1) // 2
+
+
+def test_gather_residue_table_claims():
+    """Block counts ⌈max_w / 64⌉ · ⌈max_h / 48⌉ · n of the residue launches:
+    every residue mod 8, and 1 and 9 blocks."""
+    counts = []
+    for k, (n_small, wide) in enumerate(R.GATHER_RESIDUE_LAUNCHES):
+        items = R.gather_residue_items(k)
+        assert len(items) == n_small + wide
+        sizes = [R.gather_out_size(it) for it in items]
+        small = [s for it, s in zip(items, sizes) if it is not R.GATHER_WIDE]
+        assert all(s[0] <= R.GATHER_TILE_W and s[1] <= R.GATHER_TILE_H for s in small)      # one tile
+        if wide:
+            assert 0 < items.index(R.GATHER_WIDE) < len(items) - 1 or len(items) <= 2
+            assert R.gather_blocks(sizes) == 3 * len(items)
+        else:
+            assert R.gather_blocks(sizes) == len(items)
+        counts.append(R.gather_blocks(sizes))
+    assert {c % 8 for c in counts} == set(range(8)) and {1, 9} <= set(counts)
+    assert R.gather_blocks([(183, 206)] * 5) == 3 * 5 * 5
+
+
+def _wrapper_buffer(flat, plan):
+    """The bytes device.rotate_flip_nearest launches from: the caller's
+    buffer, made longer when it is shorter than the plan's min_src_bytes."""
+    return np.concatenate([flat, np.zeros(max(0, plan.min_src_bytes - flat.size), np.uint8)])
+
+
+@pytest.mark.parametrize("order", R.GATHER_ORDERS)
+def test_gather_model_equals_oracle(D, order):
+    """plan_rotate_flip + ipp_gather_prepare, held to the oracle without a GPU:
+    the host model of the kernel, evaluated from the prepared fields and again
+    from a0..a5 / off_x / off_y / flip as make_sampler does for prepared = 0."""
+    launch = R.gather_launch(order)
+    plan = launch.plan(D)
+    assert (plan.descs["prepared"] == 1).all()
+    assert (plan.max_w, plan.max_h) == R.gather_out_size(R.GATHER_ITEMS[R.GATHER_LARGEST])
+    buf = _wrapper_buffer(launch.flat, plan)
+    for j, ref in enumerate(R.gather_refs(launch)):
+        assert plan.shapes[j] == ref.shape[:2], launch.items[j]
+        for prepared in (True, False):
+            got = R.gather_model(buf, plan.descs[j], prepared)
+            assert np.array_equal(got, ref), (launch.items[j], prepared)
+
+
+def test_gather_model_equals_oracle_on_the_residue_launches(D):
+    for k in range(len(R.GATHER_RESIDUE_LAUNCHES)):
+        launch = R.gather_residue_launch(k)
+        plan = launch.plan(D, row_align=16)
+        assert plan.min_src_bytes <= launch.flat.size
+        for j, ref in enumerate(R.gather_refs(launch)):
+            assert np.array_equal(R.gather_model(launch.flat, plan.descs[j]), ref), (k, launch.items[j])
+
+
+def test_gather_needs_one_byte_past_a_last_pixel_window(D):
+    """A 1×1 window on the last pixel of a 3-channel source that ends the
+    buffer: 3 bytes are left for a 4-byte load.  ipp_gather_prepare stores
+    lim = 0 (not 2³² − 1), the plan asks for one byte more than the buffer
+    has, and the model's bounds assertion is what notices a launch from the
+    short buffer."""
+    launch = R.gather_launch()
+    plan = launch.plan(D)
+    last = plan.descs[-1]
+    assert int(last["base_off"]) == launch.flat.size - 3 and int(last["lim"]) == 0
+    assert plan.min_src_bytes == launch.flat.size + 1
+    assert R.gather_sampler(last, prepared=False)[:2] == (launch.flat.size - 3, 0)
+    with pytest.raises(AssertionError, match="the gather reads bytes"):
+        R.gather_model(launch.flat, last)
+    mid = plan.descs[17]
+    assert int(mid["lim"]) == 0 and int(mid["base_off"]) + 4 <= launch.flat.size
+    # what rotate_crop_single plans for a 1×1×3 tensor
+    one = D.plan_rotate_flip([(1, 1, 3)], [0.0], [0])
+    assert one.min_src_bytes == 4 and int(one.descs[0]["lim"]) == 0
+    # 4-channel windows never need it
+    assert D.plan_rotate_flip([(1, 1, 4)], [45.0], [0], crop_to_bbox=False).min_src_bytes == 0
