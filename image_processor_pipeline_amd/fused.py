@@ -40,9 +40,9 @@ from . import _native as N
 from . import geometry as G
 from .device import SYM_FLIP, _stream, _to_dev
 from .device import check_alpha_min as _check_alpha_min
-from .labels_fmt import (instance_ids, scene_contour_capacity, scene_instance_masks, scene_labels,  # noqa: F401
-                         scene_map_pitch, scene_seg_labels, seg_label, simplify_tolerance, xyxy2xywhn, yolo_label,
-                         yolo_labels)
+from .labels_fmt import (instance_ids, obb_corners, obb_label, scene_contour_capacity,  # noqa: F401
+                         scene_instance_masks, scene_labels, scene_map_pitch, scene_obb_labels, scene_seg_labels,
+                         seg_label, simplify_tolerance, xyxy2xywhn, yolo_label, yolo_labels)
 
 ALL_SYMS = ("o", "h", "v", "hv")
 H_RING_COLUMNS = 512   # ipp_pipe.hip RING

@@ -4,7 +4,8 @@ call and no GPU.
 ``yolo_label(s)`` write the reference's one label per composite (overlays.py:141-149),
 from its rectangle or from the tight boxes of ``PipeRunner.overlay_bboxes``.  For the
 scenes of scenes.py, ``scene_labels`` formats the box lines and ``scene_seg_labels`` the
-YOLO segmentation lines, both for the overlays ``_label_lines`` names; ``instance_ids`` and
+YOLO segmentation lines and ``scene_obb_labels`` the YOLO-OBB lines (``obb_corners`` states the
+corner rule), all for the overlays ``_label_lines`` names; ``instance_ids`` and
 ``scene_instance_masks`` turn a visibility map into instance masks.  ``fused`` re-exports it all.
 """
 from __future__ import annotations
@@ -182,4 +183,57 @@ def scene_seg_labels(polys, info, rows, bg_w: int, bg_h: int, class_ids=0, min_v
         if polys[s][k] is None:
             raise ValueError(f"scene {s} layer {k}: {int(row[5])} visible pixels but no polygon")
         out[s].append(seg_label(class_id, polys[s][k], bg_w, bg_h))
+    return out
+
+
+def obb_corners(rec) -> np.ndarray:
+    """The four corners, (4, 2) float64 in lattice coordinates, of one
+    ipp_polygons_obb record {ax, ay, dx, dy, lo, hi, hgt, m} with m >= 2: C(t, s)
+    = (ax + (t·dx − s·dy) / nn, ay + (t·dy + s·dx) / nn) for (lo, 0), (hi, 0),
+    (hi, hgt), (lo, hgt), in the rule's operation order (include/ipp.h) — clockwise
+    on the screen from the chosen hull edge.  They are NOT clipped: the rectangle
+    of an object at the image border may leave the image slightly."""
+    rec = np.asarray(rec)
+    if rec.shape != (N.IPP_OBB_REC,):
+        raise ValueError(f"a record of shape {rec.shape}: ({N.IPP_OBB_REC},) expected")
+    ax, ay, dx, dy, lo, hi, hgt, m = (int(v) for v in rec)
+    nn = dx * dx + dy * dy
+    if m < 2 or nn == 0:
+        raise ValueError(f"record {rec.tolist()}: no direction (m = {m}), it has no corners")
+    return np.array([(ax + (t * dx - s * dy) / nn, ay + (t * dy + s * dx) / nn)
+                     for t, s in ((lo, 0), (hi, 0), (hi, hgt), (lo, hgt))], np.float64)
+
+
+def obb_label(class_id: int, rec, bg_w: int, bg_h: int) -> str:
+    """One YOLO-OBB line ``class x1 y1 x2 y2 x3 y3 x4 y4`` for one
+    ipp_polygons_obb record on a bg_w×bg_h composite: the corners of
+    ``obb_corners`` as x / bg_w and y / bg_h, in the number format of
+    ``yolo_label``.  Not clipped to 0..1 (see ``obb_corners``)."""
+    return " ".join([str(class_id)] + [f"{x / bg_w:.6f} {y / bg_h:.6f}" for x, y in obb_corners(rec)])
+
+
+def scene_obb_labels(obbs, info, rows, bg_w: int, bg_h: int, class_ids=0, min_visible: float = 0.0) -> List[List[str]]:
+    """YOLO-OBB lines of every scene from what ``SceneRunner.scene_obbs``
+    returns: labels[s] lists, in layer order, one line (``obb_label``) per
+    overlay that ``scene_labels`` gives a line (``_label_lines``).
+    ``class_ids`` as there.  An overlay that would get a line but overflowed
+    ``max_edges`` (header flags bit 0) raises ValueError naming the
+    ``max_edges`` it needs, as ``scene_seg_labels`` does, and one whose record
+    has m < 3 or hgt == 0 (no rectangle) raises too: a label is never dropped.
+    The corners are not clipped to the image."""
+    info, obbs = np.asarray(info), np.asarray(obbs)
+    rows, S, K = _scene_rows(rows, "rows")
+    if info.shape != (S, K, N.IPP_CONTOUR_HDR):
+        raise ValueError(f"info of shape {info.shape}: ({S}, {K}, {N.IPP_CONTOUR_HDR}) expected")
+    if obbs.shape != (S, K, N.IPP_OBB_REC):
+        raise ValueError(f"obbs of shape {obbs.shape}: ({S}, {K}, {N.IPP_OBB_REC}) expected")
+    out: List[List[str]] = [[] for _ in range(S)]
+    for s, k, class_id, row in _label_lines(rows, class_ids, min_visible):
+        if int(info[s, k, 7]) & 1:
+            raise ValueError(f"scene {s} layer {k}: its contour has {int(info[s, k, 0])} boundary edges, "
+                             f"scene_obbs needs max_edges >= {int(info[s, k, 0])}")
+        if int(obbs[s, k, 7]) < 3 or int(obbs[s, k, 6]) == 0:
+            raise ValueError(f"scene {s} layer {k}: {int(row[5])} visible pixels but no oriented box "
+                             f"(record {obbs[s, k].tolist()})")
+        out[s].append(obb_label(class_id, obbs[s, k], bg_w, bg_h))
     return out

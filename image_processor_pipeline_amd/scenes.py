@@ -7,7 +7,8 @@ copy (``ipp_pipe_hpass``) and an in-place V launch (``ipp_pipe_vblend_over``)
 — and label each overlay by what no later layer covers (``scene_boxes``).
 ``scene_masks`` keeps that rule's per-pixel answer, one visibility map per
 composite, and ``scene_polygons`` traces (and simplifies) each overlay's outer
-contour from it on the device.  labels_fmt.py formats the lines and masks;
+contour from it on the device; ``scene_obbs`` reduces that contour there to its
+minimum-area rectangle (YOLO-OBB).  labels_fmt.py formats the lines and masks;
 every public name here is also reachable as ``fused.X``.
 """
 from __future__ import annotations
@@ -23,7 +24,8 @@ from .device import _stream, _to_dev, exclusive_offsets
 from .device import check_alpha_min as _check_alpha_min
 from .fused import (ItemParams, PipeConfig, PipePlan, _launch_hpass_bgcopy, _launch_vblend_bands, _Runner,
                     draw_params, plan_pipe)
-from .labels_fmt import scene_contour_capacity, scene_labels, scene_map_pitch, scene_seg_labels, simplify_tolerance
+from .labels_fmt import (scene_contour_capacity, scene_labels, scene_map_pitch, scene_obb_labels, scene_seg_labels,
+                         simplify_tolerance)
 
 
 def draw_scene_params(n_scenes_global: int, stop_scene: int, per_scene: int, src_hw: Tuple[int, int],
@@ -140,6 +142,7 @@ class SceneRunner(_Runner):
     _scene_layer = _scratch = None   # of the label and map launches; these four are allocated on first use
     _contour_scratch = None          # (max_edges, buffer) of scene_polygons
     _simplify_scratch = None         # buffer of scene_polygons(simplify=...), grown on demand
+    _obb_scratch = None              # buffer of scene_obbs, grown on demand
 
     def _check(self, caller: str, src: torch.Tensor, bgs: torch.Tensor, out: torch.Tensor) -> None:
         self._check_tensors(caller, src, bgs, out)
@@ -295,13 +298,28 @@ class SceneRunner(_Runner):
                              f"not exceed {SIMPLIFY_MAX_SIDE} (ipp_polygons_simplify's exact integer bounds)")
         return eps_q
 
+    def _check_obb(self, caller: str) -> None:
+        """Refuse what ipp_polygons_obb would: a background side above 16384 (its exact integer bounds)."""
+        p = self.plan.pipe
+        if p.bg_w > SIMPLIFY_MAX_SIDE or p.bg_h > SIMPLIFY_MAX_SIDE:
+            raise ValueError(f"SceneRunner.{caller}: oriented boxes on a {p.bg_w}x{p.bg_h} background: bg_w and bg_h "
+                             f"must not exceed {SIMPLIFY_MAX_SIDE} (ipp_polygons_obb's exact integer bounds)")
+
     def _polygons(self, buf: torch.Tensor, rows: torch.Tensor, max_edges: int, eps_q: Optional[int] = None):
+        """(polys, info) of ``_trace``: the polygons alone."""
+        return self._trace(buf, rows, max_edges, eps_q)[:2]
+
+    def _trace(self, buf: torch.Tensor, rows: torch.Tensor, max_edges: int, eps_q: Optional[int] = None,
+               polygons: bool = True, obb: bool = False):
         """The tracer, the header copy-back, the pack and the packed copy-back
-        on the map and device rows of one ``_launch_map``: (polys, info), both
-        in scene, layer order.  Synchronises.  With ``eps_q`` the packed
-        vertices stay on the device: ipp_polygons_simplify, the counts'
+        on the map and device rows of one ``_launch_map``: (polys, info,
+        obbs), all in scene, layer order.  Synchronises.  With ``eps_q`` the
+        packed vertices stay on the device: ipp_polygons_simplify, the counts'
         copy-back, ipp_polygons_simplify_pack, and only the kept vertices
-        come back."""
+        come back.  With ``obb`` ipp_polygons_obb runs on the packed
+        (unsimplified) vertices right after the pack and its (S, K, 8) records
+        come back, else obbs is None; without ``polygons`` no vertex is copied
+        back and polys is None."""
         p, S, K = self.plan.pipe, self.plan.n_scenes, self.plan.per_scene
         n, lib, st = S * K, self.lib, _stream(self.device)
         if self._contour_scratch is None or self._contour_scratch[0] != max_edges:
@@ -317,22 +335,46 @@ class SceneRunner(_Runner):
         offsets = exclusive_offsets(nv)
         total = int(nv.sum())
         packed = np.empty((0, 2), np.int32)
+        d_obb = None
         if total:
             verts = torch.empty(2 * total, dtype=torch.int32, device=self.device)
-            N.check(lib.ipp_scene_contours_pack(scratch.data_ptr(), hdr.data_ptr(),
-                                                _to_dev(offsets, self.device).data_ptr(), n, max_edges,
+            d_off = _to_dev(offsets, self.device)
+            N.check(lib.ipp_scene_contours_pack(scratch.data_ptr(), hdr.data_ptr(), d_off.data_ptr(), n, max_edges,
                                                 verts.data_ptr(), st), "ipp_scene_contours_pack")
-            if eps_q is None:
+            if obb:
+                d_obb = self._launch_obb(verts, d_off, hdr, total)
+            if polygons and eps_q is None:
                 packed = verts.cpu().numpy().reshape(total, 2)
-            else:
+            elif polygons:
                 nv, offsets, packed = self._simplified(verts, offsets, hdr, total, eps_q)
         info = np.empty_like(by_desc)
         info[self.plan.desc_item] = by_desc
-        polys: List[List[Optional[np.ndarray]]] = [[None] * K for _ in range(S)]
-        for d, item in enumerate(self.plan.desc_item.tolist()):
-            if nv[d]:
-                polys[item // K][item % K] = packed[offsets[d]:offsets[d] + nv[d]].copy()
-        return polys, info.reshape(S, K, N.IPP_CONTOUR_HDR)
+        obbs = None
+        if obb:     # no packed vertex at all: every header has n_vertices == 0, every record is the zero record
+            rec = d_obb.cpu().numpy().reshape(n, N.IPP_OBB_REC) if d_obb is not None else \
+                np.zeros((n, N.IPP_OBB_REC), np.int32)
+            obbs = np.empty_like(rec)
+            obbs[self.plan.desc_item] = rec
+            obbs = obbs.reshape(S, K, N.IPP_OBB_REC)
+        polys: Optional[List[List[Optional[np.ndarray]]]] = None
+        if polygons:
+            polys = [[None] * K for _ in range(S)]
+            for d, item in enumerate(self.plan.desc_item.tolist()):
+                if nv[d]:
+                    polys[item // K][item % K] = packed[offsets[d]:offsets[d] + nv[d]].copy()
+        return polys, info.reshape(S, K, N.IPP_CONTOUR_HDR), obbs
+
+    def _launch_obb(self, verts: torch.Tensor, d_off: torch.Tensor, hdr: torch.Tensor, total: int) -> torch.Tensor:
+        """ipp_polygons_obb on the packed device polygons: the device records, 8 int32 per descriptor."""
+        p, n = self.plan.pipe, len(self.plan.descs)
+        nb = max(self._scratch_bytes("ipp_polygons_obb_scratch_bytes", n, total), 16)
+        if self._obb_scratch is None or self._obb_scratch.numel() < nb:
+            self._obb_scratch = torch.empty(nb, dtype=torch.uint8, device=self.device)
+        rec = torch.empty(N.IPP_OBB_REC * n, dtype=torch.int32, device=self.device)
+        N.check(self.lib.ipp_polygons_obb(verts.data_ptr(), d_off.data_ptr(), hdr.data_ptr(), n, total, p.bg_w,
+                                          p.bg_h, self._obb_scratch.data_ptr(), rec.data_ptr(),
+                                          _stream(self.device)), "ipp_polygons_obb")
+        return rec
 
     def _simplified(self, verts: torch.Tensor, offsets: np.ndarray, hdr: torch.Tensor, total: int, eps_q: int):
         """(counts, out_offsets, kept vertices (sum counts, 2)) of the packed device polygons."""
@@ -387,9 +429,34 @@ class SceneRunner(_Runner):
         polys, info = self._polygons(buf, rows, max_edges, eps_q)
         return polys, info, self._rows_by_scene(rows)
 
+    def scene_obbs(self, alpha_min: int = 1, cover_min: int = 128, max_edges: Optional[int] = None):
+        """The oriented box (YOLO-OBB) of every overlay's visible pixels: the
+        minimum-area rectangle around the outline that ``scene_polygons``
+        traces (the largest 8-connected visible part, unsimplified), found on
+        the device by the exact rule of include/ipp.h (ipp_polygons_obb after
+        the map launch, the tracer and its pack).  Returns (obbs, info, rows):
+        obbs is (S, K, 8) int32 in scene, layer order, one record {ax, ay, dx,
+        dy, lo, hi, hgt, m} per overlay — ``obb_corners`` gives its corners,
+        which are NOT clipped to the image: the rectangle of an overlay at the
+        border may leave it slightly — and all zeros for an overlay without a
+        visible pixel or one that overflowed ``max_edges``; info and rows are
+        exactly ``scene_polygons``'.  Runs after ``run`` on the current stream
+        and synchronises; the headers, the rows and 32 B per overlay come
+        back, the packed vertices never leave the device.  Scenes of more than
+        8 layers and backgrounds of more than 16384 pixels on a side are
+        refused."""
+        alpha_min, cover_min = _check_level("alpha_min", alpha_min), _check_level("cover_min", cover_min)
+        self._check_map("scene_obbs", None)
+        max_edges = self._check_max_edges("scene_obbs", max_edges)
+        self._check_obb("scene_obbs")
+        buf, rows = self._launch_map("scene_obbs", alpha_min, cover_min, True, None)
+        _, info, obbs = self._trace(buf, rows, max_edges, None, polygons=False, obb=True)
+        return obbs, info, self._rows_by_scene(rows)
+
     def run_labelled(self, src: torch.Tensor, bgs: torch.Tensor, out: torch.Tensor, class_ids=0,
                      alpha_min: int = 1, cover_min: int = 128, min_visible: float = 0.0, masks: bool = False,
-                     polygons: bool = False, max_edges: Optional[int] = None, simplify: Optional[float] = None):
+                     polygons: bool = False, max_edges: Optional[int] = None, simplify: Optional[float] = None,
+                     obb: bool = False):
         """``run`` plus the YOLO lines of every scene (``scene_labels``):
         labels[s] lists scene s's lines in layer order, one per overlay with
         visible > 0 and visible / area >= min_visible.  Returns (out, labels);
@@ -397,17 +464,27 @@ class SceneRunner(_Runner):
         same launch as the boxes.  With ``polygons`` the tuple gains, as its
         last element, the segmentation lines of ``scene_seg_labels`` (polygons
         of ``scene_polygons`` with ``max_edges`` and ``simplify``), traced from
-        that same map launch.  ``simplify`` without ``polygons`` is refused."""
+        that same map launch.  ``simplify`` without ``polygons`` is refused.
+        With ``obb`` the tuple gains, after the segmentation lines if any, the
+        YOLO-OBB lines of ``scene_obb_labels`` (records of ``scene_obbs``):
+        the map launch, the tracer and the pack run once for both, the boxes
+        always come from the unsimplified outline (``simplify`` changes the
+        segmentation lines only), and with ``obb`` alone no vertex is copied
+        back.  Their corners are not clipped to the image."""
         alpha_min, cover_min = _check_level("alpha_min", alpha_min), _check_level("cover_min", cover_min)
         if simplify is not None and not polygons:
             raise ValueError("SceneRunner.run_labelled: simplify needs polygons=True")
-        if masks or polygons:
+        if masks or polygons or obb:
             self._check_map("run_labelled", None)
-        if polygons:
+        eps_q = None
+        if polygons or obb:
             max_edges = self._check_max_edges("run_labelled", max_edges)
+        if polygons:
             eps_q = self._check_simplify("run_labelled", simplify)
+        if obb:
+            self._check_obb("run_labelled")
         self.run(src, bgs, out)
-        if masks or polygons:
+        if masks or polygons or obb:
             buf, rows = self._launch_map("run_labelled", alpha_min, cover_min, True, None)
         else:
             rows = self._launch_boxes(alpha_min, cover_min)
@@ -416,7 +493,10 @@ class SceneRunner(_Runner):
         res = (out, scene_labels(boxes, bg_w, bg_h, class_ids, min_visible))
         if masks:
             res += (buf[:, :, :bg_w],)
-        if polygons:
-            polys, info = self._polygons(buf, rows, max_edges, eps_q)
-            res += (scene_seg_labels(polys, info, boxes, bg_w, bg_h, class_ids, min_visible),)
+        if polygons or obb:
+            polys, info, obbs = self._trace(buf, rows, max_edges, eps_q, polygons=polygons, obb=obb)
+            if polygons:
+                res += (scene_seg_labels(polys, info, boxes, bg_w, bg_h, class_ids, min_visible),)
+            if obb:
+                res += (scene_obb_labels(obbs, info, boxes, bg_w, bg_h, class_ids, min_visible),)
         return res

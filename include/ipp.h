@@ -537,6 +537,80 @@ int ipp_polygons_simplify_pack(const int32_t* verts, const int64_t* offsets, con
                                const uint8_t* scratch, const int32_t* counts, const int64_t* out_offsets,
                                int32_t n_images, int32_t* out, void* stream);
 
+/* Oriented boxes (YOLO-OBB) of the packed polygons on the device: the
+ * minimum-area enclosing rectangle of each ring, this project's own normative
+ * definition in exact integers.
+ *
+ * INPUT.  A ring P[0..n-1] of lattice points with both coordinates in
+ * 0..16384; for traced polygons exactly what ipp_scene_contours_pack wrote.
+ * The result depends on the POINT SET only, not on the order of the points:
+ * pinch vertices, repeated points and self-crossing rings are legal input.
+ * With cross(u, v) = ux·vy − uy·vx:
+ * HULL.  H[0..m-1] are the vertices of the strictly convex hull (no hull
+ * vertex lies on the segment between two others).  H[0] is the point least in
+ * (y, x) order; the others follow so that cross(H[e+1]−H[e], H[e+2]−H[e+1]) >
+ * 0, indices mod m.  With y down this leaves H[0] towards +x: clockwise on the
+ * screen, the direction in which the tracer walks an outer contour.  m = 1
+ * when all points coincide, m = 2 when they are collinear.
+ * EDGE e (0 <= e < m, m >= 3).  a = H[e], d = H[(e+1) mod m] − a, nn = dx² +
+ * dy².  For every point p: t = dx·(px−ax) + dy·(py−ay) and s = −dy·(px−ax) +
+ * dx·(py−ay); every s is >= 0 (the interior is on the right).  lo = min t (<=
+ * 0), hi = max t (>= nn), hgt = max s.  The rectangle on edge e has area
+ * (hi−lo)·hgt / nn.
+ * CHOICE.  The edge of least area, compared exactly: e1 beats e2 iff
+ * (hi1−lo1)·hgt1·nn2 < (hi2−lo2)·hgt2·nn1; ties go to the lesser e.
+ * OVERFLOW BOUNDS.  |t| <= 2^29, hi−lo <= 2^30, hgt <= 2^29, nn <= 2^29: every
+ * record word fits int32, (hi−lo)·hgt <= 2^59 fits 64 bits, and the compared
+ * products reach 2^88: the comparison is 128-bit (no division anywhere).
+ * RECORD.  IPP_OBB_REC int32 words {ax, ay, dx, dy, lo, hi, hgt, m} of the
+ * chosen edge.  m = 2: e = 0, lo = 0, hi = nn, hgt = 0.  m = 1: {ax, ay, 0, 0,
+ * 0, 0, 0, 1}.
+ * CORNERS (host, float64, part of the rule).  C(t, s) = (ax + (t·dx − s·dy) /
+ * nn, ay + (t·dy + s·dx) / nn), evaluated in exactly that operation order, for
+ * (lo, 0), (hi, 0), (hi, hgt), (lo, hgt) in this order.  They are NOT clipped
+ * to the image: the rectangle of an object at the border may leave it.
+ *
+ * ipp_polygons_obb: verts, offsets, hdr and total_vertices are exactly what
+ * ipp_polygons_simplify takes (ring i = hdr[i].n_vertices pairs at verts +
+ * 2·offsets[i], the rings disjoint and below total_vertices); it runs on the
+ * same stream after ipp_scene_contours_pack and is independent of the simplify
+ * entries (it reads the unsimplified ring).  obb (device int32[n_images][
+ * IPP_OBB_REC]) receives one record per descriptor, all eight words 0 where
+ * the header has n_vertices == 0 or flags != 0; every word of every record is
+ * written and nothing else is, but the ring's own slots of the scratch (below).
+ * The coordinate range is the CALLER'S CONTRACT: bg_w and bg_h are checked,
+ * the vertices (device data) are not.  Vertices outside 0..16384 give an
+ * unspecified record (they are clamped on load), but no access outside the
+ * rings, the scratch and the records.
+ * One workgroup of IPP_OBB_THREADS threads per ring, any n_vertices (the
+ * tracer emits up to max_edges = 2^22): never refused, never truncated.  It
+ * reduces the ring to the least and greatest x of each lattice row, a window
+ * of IPP_OBB_LDS_ROWS rows at a time in LDS (a ring spanning more rows sweeps
+ * its vertices once per window), and extends the hull's right and left
+ * monotone chains after each window.  The first IPP_OBB_LDS_HULL points of
+ * each chain live in LDS, later ones in the scratch; the rectangle search runs
+ * over the hull alone.  The only atomics are integer min and max: the result
+ * does not depend on their order.
+ * scratch: device, 16-B aligned, ipp_polygons_obb_scratch_bytes(n_images,
+ * total_vertices) = 8·total_vertices rounded up to 256 B: uint32 slots
+ * offsets[i] .. offsets[i] + n_vertices − 1 for ring i's right chain and the
+ * same slots + total_vertices for its left chain.  A chain of at most
+ * IPP_OBB_LDS_HULL points (so every ring of at most that many vertices)
+ * touches none of them; what a longer chain leaves in its ring's slots is
+ * unspecified.
+ * IPP_E_ARG, before any launch: a NULL pointer; scratch not 16-B, offsets not
+ * 8-B, another pointer not 4-B aligned; bg_w or bg_h outside 1..16384;
+ * n_images or total_vertices negative; n_images >= 2^24 (the grid);
+ * total_vertices > 2^40.  n_images == 0 is IPP_OK and launches nothing. */
+#define IPP_OBB_REC 8
+#define IPP_OBB_LDS_ROWS 2048 /* lattice rows of one window of the row reduction */
+#define IPP_OBB_LDS_HULL 512  /* points of each monotone chain kept in LDS */
+#define IPP_OBB_THREADS 256   /* threads of a ring's workgroup: thread t owns vertices and hull edges t, t + 256, ... */
+int64_t ipp_polygons_obb_scratch_bytes(int32_t n_images, int64_t total_vertices);
+int ipp_polygons_obb(const int32_t* verts, const int64_t* offsets, const int32_t* hdr, int32_t n_images,
+                     int64_t total_vertices, int32_t bg_w, int32_t bg_h, uint8_t* scratch,
+                     int32_t* obb /* [n_images][IPP_OBB_REC] */, void* stream);
+
 /* ------------------------------------------------------------------------ */
 /* K10-K13: pixels_isolés.keep_largest_component                             */
 /* :32 threshold(α,1,255) :35 connectedComponentsWithStats(8) :38-55 keep    */

@@ -1,7 +1,7 @@
 """Scene batch against the flat batch of the same overlays ("Scenes").
 
     python tools/scene_probe.py [--scenes 1024] [--per-scene 4] [--size 1024] [--backgrounds 16]
-                                [--steps 20] [--warmup 3] [--seed 0] [--simplify EPS]
+                                [--steps 20] [--warmup 3] [--seed 0] [--simplify EPS] [--obb]
 
 Workload: S scenes × K overlays of size² sources on size² backgrounds with the
 config-3 parameters (fused.PipeConfig()), against PipeRunner.run on the flat
@@ -15,7 +15,9 @@ per overlay (default fused.scene_contour_capacity).  With --simplify EPS (pixels
 the same steps time the simplification of those packed polygons
 (ipp_polygons_simplify) and its pack launch (ipp_polygons_simplify_pack) next
 to the tracer's, and the report gains the vertices before and after and the
-bytes copied back.  A second series times each launch of the scene run on its own.  Prints one
+bytes copied back.  With --obb the same steps time the oriented boxes of those
+packed polygons (ipp_polygons_obb) as well, and the report gains the bytes that
+come back per overlay against the packed ring's.  A second series times each launch of the scene run on its own.  Prints one
 JSON line."""
 import argparse
 import json
@@ -38,6 +40,7 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--max-edges", type=int, default=0)
     ap.add_argument("--simplify", type=float, default=None, metavar="EPS")
+    ap.add_argument("--obb", action="store_true")
     args = ap.parse_args()
 
     import torch
@@ -116,6 +119,16 @@ def main():
                                                      simp["out"].data_ptr(), _stream(dev)),
                 "ipp_polygons_simplify_pack")
 
+    # the oriented boxes of the packed polygons: scratch and records sized with the packed buffer
+    obb = {}
+
+    def oriented():
+        N.check(scene.lib.ipp_polygons_obb(tracer["verts"].data_ptr(), tracer["offsets"].data_ptr(),
+                                           tracer["hdr"].data_ptr(), n, obb["total"], Z, Z,
+                                           obb["scratch"].data_ptr(), obb["rec"].data_ptr(), _stream(dev)),
+                "ipp_polygons_obb")
+
+    ms_obb = []
     ms_flat, ms_scene, ms_label, ms_map, ms_both, ms_trace, ms_pack = [], [], [], [], [], [], []
     ms_simp, ms_simp_pack = [], []
     hdrs = kept = None
@@ -129,6 +142,8 @@ def main():
             et = timed(trace)
             if hdrs is not None:
                 ep = timed(pack)
+                if args.obb:
+                    eo = timed(oriented)
                 if eps_q is not None:
                     ey = timed(simplify)
                     if kept is not None:
@@ -137,6 +152,8 @@ def main():
         if with_map:
             if hdrs is not None and step >= args.warmup:
                 ms_pack.append(ep[0].elapsed_time(ep[1]))
+                if args.obb:
+                    ms_obb.append(eo[0].elapsed_time(eo[1]))
                 if eps_q is not None:
                     ms_simp.append(ey[0].elapsed_time(ey[1]))
                     if kept is not None:
@@ -150,6 +167,11 @@ def main():
                 nv = hdrs[:, 3].astype(np.int64)
                 tracer["offsets"] = torch.from_numpy(np.concatenate([[0], np.cumsum(nv)[:-1]]).astype(np.int64)).to(dev)
                 tracer["verts"] = torch.empty(2 * max(int(nv.sum()), 1), dtype=torch.int32, device=dev)
+                if args.obb:
+                    obb["total"] = int(nv.sum())
+                    nb = scene.lib.ipp_polygons_obb_scratch_bytes(n, obb["total"])
+                    obb["scratch"] = torch.empty(max(int(nb), 16), dtype=torch.uint8, device=dev)
+                    obb["rec"] = torch.zeros(N.IPP_OBB_REC * n, dtype=torch.int32, device=dev)
                 if eps_q is not None:
                     simp["total"] = int(nv.sum())
                     nb = scene.lib.ipp_polygons_simplify_scratch_bytes(n, simp["total"])
@@ -189,6 +211,8 @@ def main():
             for name, (a, b) in evs:
                 per[name].append(a.elapsed_time(b))
 
+    scene_rows = tracer["rows"].cpu().numpy().reshape(n, 6) if with_map else None
+
     def summary(v):
         return {"median_ms": round(statistics.median(v), 3), "min_ms": round(min(v), 3), "max_ms": round(max(v), 3)}
 
@@ -213,6 +237,13 @@ def main():
             "vertices_after": int(kept.sum()), "largest_before": int(hdrs[:, 3].max()),
             "largest_after": int(kept.max()), "largest_before_ring_after": int(kept[int(hdrs[:, 3].argmax())]), "counts_bytes": int(4 * n), "kept_bytes": int(8 * kept.sum()),
             "bytes_back": int(hdrs.nbytes + 4 * n + 8 * kept.sum()), "scratch_bytes": int(simp["scratch"].numel())},
+        "obb_launch": summary(ms_obb) if ms_obb else None,
+        "obb": None if not ms_obb else (lambda r: {
+            "records_bytes": int(r.nbytes), "bytes_back_per_overlay": 4 * N.IPP_OBB_REC,
+            "packed_bytes_per_overlay_mean": round(float(8 * hdrs[:, 3].astype(np.int64).sum()) / n, 1),
+            "boxes": int((r[:, 7] >= 3).sum()), "largest_hull": int(r[:, 7].max()),
+            "rows_spanned_max": int((hdrs[:, 3] > 0).any() and (scene_rows[:, 3] - scene_rows[:, 1]).max()),
+            "scratch_bytes": int(obb["scratch"].numel())})(obb["rec"].cpu().numpy().reshape(n, N.IPP_OBB_REC)),
         "scene_launches": {name: summary(v) for name, v in per.items()},
         "copy_read_bytes": {"flat": flat_plan.copy_read_bytes, "scenes": scene_plan.copy_read_bytes},
         "composite_bytes": {"flat": out_flat.numel(), "scenes": out_scene.numel()},
