@@ -6,7 +6,10 @@ from its rectangle or from the tight boxes of ``PipeRunner.overlay_bboxes``.  Fo
 scenes of scenes.py, ``scene_labels`` formats the box lines and ``scene_seg_labels`` the
 YOLO segmentation lines and ``scene_obb_labels`` the YOLO-OBB lines (``obb_corners`` states the
 corner rule), all for the overlays ``_label_lines`` names; ``instance_ids`` and
-``scene_instance_masks`` turn a visibility map into instance masks.  ``fused`` re-exports it all.
+``scene_instance_masks`` turn a visibility map into instance masks.  ``scene_coco_annotations``
+writes the COCO annotations of ``SceneRunner.scene_rles``' run-length encodings, ``rle_counts_string``
+/ ``rle_counts_from_string`` are the COCO API's compressed ``counts`` string and ``rle_decode``
+reads a mask back.  ``fused`` re-exports it all.
 """
 from __future__ import annotations
 
@@ -236,4 +239,120 @@ def scene_obb_labels(obbs, info, rows, bg_w: int, bg_h: int, class_ids=0, min_vi
             raise ValueError(f"scene {s} layer {k}: {int(row[5])} visible pixels but no oriented box "
                              f"(record {obbs[s, k].tolist()})")
         out[s].append(obb_label(class_id, obbs[s, k], bg_w, bg_h))
+    return out
+
+
+def _rle_counts(counts) -> List[int]:
+    """`counts` as a list of Python ints: a 1-D sequence of non-negative integers."""
+    a = np.asarray(counts)
+    if a.ndim != 1 or (a.size and a.dtype.kind not in "iu"):
+        raise ValueError(f"RLE counts of shape {a.shape} and type {a.dtype}: a 1-D integer sequence expected")
+    out = [int(v) for v in a]
+    if any(v < 0 for v in out):
+        raise ValueError("RLE counts must not be negative")
+    return out
+
+
+def rle_counts_string(counts) -> str:
+    """The COCO API's compressed ``counts`` string of uncompressed RLE counts
+    (its ``rleToString`` rule).  Count i is coded as x = counts[i] for i < 3 and
+    x = counts[i] - counts[i - 2] from the fourth count on (a signed
+    difference).  x is written in 5-bit groups, least significant first: c = x &
+    0x1f, x >>= 5 (arithmetic); the group is the last when x has become 0 and
+    bit 0x10 of c is clear, or x has become -1 and bit 0x10 is set (that bit is
+    the sign); every other group gets the continuation bit 0x20; the character
+    is chr(c + 48)."""
+    cnts = _rle_counts(counts)
+    out = []
+    for i, x in enumerate(cnts):
+        if i > 2:
+            x -= cnts[i - 2]
+        while True:
+            c = x & 0x1f
+            x >>= 5
+            more = (x != -1) if c & 0x10 else (x != 0)
+            out.append(chr((c | 0x20 if more else c) + 48))
+            if not more:
+                break
+    return "".join(out)
+
+
+def rle_counts_from_string(s: str) -> np.ndarray:
+    """The uint32 counts of a COCO compressed ``counts`` string (the API's
+    ``rleFrString`` rule, the inverse of ``rle_counts_string``): 5-bit groups
+    c = ord(ch) - 48, least significant first, up to the first without the
+    continuation bit 0x20; bit 0x10 of that last group extends the sign; from
+    the fourth count on the value is a difference against the count two
+    before.  A string that is not such a code raises ValueError."""
+    if isinstance(s, bytes):
+        s = s.decode("ascii")
+    cnts: List[int] = []
+    p, n = 0, len(s)
+    while p < n:
+        x, k = 0, 0
+        while True:
+            if p >= n:
+                raise ValueError("RLE string ends inside a count")
+            c = ord(s[p]) - 48
+            if not 0 <= c < 64:
+                raise ValueError(f"RLE string: character {s[p]!r} at {p}")
+            x |= (c & 0x1f) << (5 * k)
+            p += 1
+            k += 1
+            if not c & 0x20:
+                if c & 0x10:
+                    x |= -1 << (5 * k)
+                break
+        if len(cnts) > 2:
+            x += cnts[-2]
+        if not 0 <= x < 1 << 32:
+            raise ValueError(f"RLE string: count {len(cnts)} decodes to {x}")
+        cnts.append(x)
+    return np.array(cnts, np.uint32)
+
+
+def rle_decode(counts, bg_h: int, bg_w: int) -> np.ndarray:
+    """The boolean (bg_h, bg_w) mask of uncompressed RLE counts (or of a
+    compressed string): runs of zeros and ones alternate, zeros first, over the
+    pixels in column-major order (include/ipp.h: ipp_scene_rle).  The counts
+    must sum to bg_h·bg_w."""
+    cnts = np.asarray(rle_counts_from_string(counts) if isinstance(counts, (str, bytes)) else _rle_counts(counts),
+                      np.int64)
+    if int(cnts.sum()) != int(bg_h) * int(bg_w):
+        raise ValueError(f"RLE counts sum to {int(cnts.sum())}, a {bg_h}x{bg_w} mask has {int(bg_h) * int(bg_w)} pixels")
+    flat = np.repeat(np.arange(len(cnts)) & 1, cnts).astype(bool)
+    return flat.reshape(int(bg_w), int(bg_h)).T.copy()
+
+
+def scene_coco_annotations(rles, rows, bg_w: int, bg_h: int, class_ids=0, min_visible: float = 0.0,
+                           compressed: bool = True, image_ids=None, first_id: int = 1) -> List[List[dict]]:
+    """COCO annotations of every scene from what ``SceneRunner.scene_rles``
+    returns: anns[s] lists, in layer order, one dict per overlay that
+    ``scene_labels`` gives a line (``_label_lines``, ``class_ids`` as there):
+    {"id", "image_id", "category_id", "bbox": [x0, y0, x1 - x0, y1 - y0],
+    "area": visible, "iscrowd": 0, "segmentation": {"size": [bg_h, bg_w],
+    "counts": ...}} — counts is the compressed string (``rle_counts_string``),
+    or with ``compressed=False`` the list of counts.  Ids run from ``first_id``
+    in scene, layer order; ``image_ids`` (one per scene) defaults to the scene
+    index.  Every value is a plain int, list or str: ``json.dumps`` takes the
+    result.  An overlay that would get an annotation but has no encoding
+    raises ValueError: an annotation is never dropped."""
+    rows, S, K = _scene_rows(rows, "rows")
+    if len(rles) != S or any(len(r) != K for r in rles):
+        raise ValueError(f"rles does not hold {S} scenes of {K} overlays")
+    img = list(range(S)) if image_ids is None else [int(v) for v in image_ids]
+    if len(img) != S:
+        raise ValueError(f"{len(img)} image ids for {S} scenes")
+    out: List[List[dict]] = [[] for _ in range(S)]
+    next_id = int(first_id)
+    for s, k, class_id, row in _label_lines(rows, class_ids, min_visible):
+        if rles[s][k] is None:
+            raise ValueError(f"scene {s} layer {k}: {int(row[5])} visible pixels but no run-length encoding")
+        cnts = _rle_counts(rles[s][k])
+        x0, y0, x1, y1 = (int(v) for v in row[:4])
+        out[s].append({"id": next_id, "image_id": img[s], "category_id": int(class_id),
+                       "bbox": [x0, y0, x1 - x0, y1 - y0], "area": int(row[5]), "iscrowd": 0,
+                       "segmentation": {"size": [int(bg_h), int(bg_w)],
+                                        "counts": rle_counts_string(cnts) if compressed else cnts}})
+        next_id += 1
     return out

@@ -8,8 +8,9 @@ copy (``ipp_pipe_hpass``) and an in-place V launch (``ipp_pipe_vblend_over``)
 ``scene_masks`` keeps that rule's per-pixel answer, one visibility map per
 composite, and ``scene_polygons`` traces (and simplifies) each overlay's outer
 contour from it on the device; ``scene_obbs`` reduces that contour there to its
-minimum-area rectangle (YOLO-OBB).  labels_fmt.py formats the lines and masks;
-every public name here is also reachable as ``fused.X``.
+minimum-area rectangle (YOLO-OBB), and ``scene_rles`` run-length encodes each
+overlay's exact visible mask there (COCO RLE).  labels_fmt.py formats the lines,
+masks and annotations; every public name here is also reachable as ``fused.X``.
 """
 from __future__ import annotations
 
@@ -24,8 +25,8 @@ from .device import _stream, _to_dev, exclusive_offsets
 from .device import check_alpha_min as _check_alpha_min
 from .fused import (ItemParams, PipeConfig, PipePlan, _launch_hpass_bgcopy, _launch_vblend_bands, _Runner,
                     draw_params, plan_pipe)
-from .labels_fmt import (scene_contour_capacity, scene_labels, scene_map_pitch, scene_obb_labels, scene_seg_labels,
-                         simplify_tolerance)
+from .labels_fmt import (scene_coco_annotations, scene_contour_capacity, scene_labels, scene_map_pitch,
+                         scene_obb_labels, scene_seg_labels, simplify_tolerance)
 
 
 def draw_scene_params(n_scenes_global: int, stop_scene: int, per_scene: int, src_hw: Tuple[int, int],
@@ -143,6 +144,7 @@ class SceneRunner(_Runner):
     _contour_scratch = None          # (max_edges, buffer) of scene_polygons
     _simplify_scratch = None         # buffer of scene_polygons(simplify=...), grown on demand
     _obb_scratch = None              # buffer of scene_obbs, grown on demand
+    _rle_scratch = None              # buffer of scene_rles
 
     def _check(self, caller: str, src: torch.Tensor, bgs: torch.Tensor, out: torch.Tensor) -> None:
         self._check_tensors(caller, src, bgs, out)
@@ -453,10 +455,59 @@ class SceneRunner(_Runner):
         _, info, obbs = self._trace(buf, rows, max_edges, None, polygons=False, obb=True)
         return obbs, info, self._rows_by_scene(rows)
 
+    def _rles(self, buf: torch.Tensor, rows: torch.Tensor) -> List[List[Optional[np.ndarray]]]:
+        """ipp_scene_rle, the header copy-back, ipp_scene_rle_pack and the
+        packed copy-back on the map and device rows of one ``_launch_map``:
+        rles[s][k] in scene, layer order.  Synchronises."""
+        p, S, K = self.plan.pipe, self.plan.n_scenes, self.plan.per_scene
+        n, lib, st = S * K, self.lib, _stream(self.device)
+        if self._rle_scratch is None:
+            nb = max(self._scratch_bytes("ipp_scene_rle_scratch_bytes", n, p.bg_w), 16)
+            self._rle_scratch = torch.empty(nb, dtype=torch.uint8, device=self.device)
+        scratch = self._rle_scratch
+        hdr = torch.empty(N.IPP_RLE_HDR * n, dtype=torch.int32, device=self.device)
+        args = (buf.data_ptr(), buf.shape[2], p.bg_w, p.bg_h, rows.data_ptr(), self._scene_layer.data_ptr(), n, S, K,
+                scratch.data_ptr(), hdr.data_ptr())
+        N.check(lib.ipp_scene_rle(*args, st), "ipp_scene_rle")
+        nc = hdr.cpu().numpy().reshape(n, N.IPP_RLE_HDR)[:, 0].astype(np.int64)      # synchronises
+        offsets = exclusive_offsets(nc)
+        total = int(nc.sum())
+        packed = np.empty(0, np.uint32)
+        if total:
+            counts = torch.empty(total, dtype=torch.int32, device=self.device)
+            N.check(lib.ipp_scene_rle_pack(*args, _to_dev(offsets, self.device).data_ptr(), counts.data_ptr(), st),
+                    "ipp_scene_rle_pack")
+            packed = counts.cpu().numpy().view(np.uint32)
+        rles: List[List[Optional[np.ndarray]]] = [[None] * K for _ in range(S)]
+        for d, item in enumerate(self.plan.desc_item.tolist()):
+            if nc[d] > 1:       # a single count is the run of N zeros: no visible pixel
+                rles[item // K][item % K] = packed[offsets[d]:offsets[d] + nc[d]].copy()
+        return rles
+
+    def scene_rles(self, alpha_min: int = 1, cover_min: int = 128):
+        """The exact mask of every overlay's visible pixels — every part and
+        every hole, unlike ``scene_polygons`` — as the COCO API's uncompressed
+        run-length encoding of the bg_h × bg_w mask, encoded on the device
+        from the visibility map (ipp_pipe_scene_map with boxes, then
+        ipp_scene_rle and ipp_scene_rle_pack; include/ipp.h states the
+        definition).  Returns (rles, rows): rles[s][k] is the uint32 array of
+        counts of scene s, layer k — runs of zeros and ones alternating, zeros
+        first, over the pixels in column-major order; they sum to bg_w·bg_h and
+        the ones-runs to the row's `visible` — or None for an overlay without a
+        visible pixel; rows is ``scene_boxes``' (S, K, 6) from the same map
+        launch.  ``rle_decode`` reads a mask back, ``scene_coco_annotations``
+        writes the annotations.  Runs after ``run`` on the current stream; only
+        the rows, 8 B of header per overlay and the packed counts are copied
+        back (it synchronises).  Scenes of more than 8 layers are refused."""
+        alpha_min, cover_min = _check_level("alpha_min", alpha_min), _check_level("cover_min", cover_min)
+        self._check_map("scene_rles", None)
+        buf, rows = self._launch_map("scene_rles", alpha_min, cover_min, True, None)
+        return self._rles(buf, rows), self._rows_by_scene(rows)
+
     def run_labelled(self, src: torch.Tensor, bgs: torch.Tensor, out: torch.Tensor, class_ids=0,
                      alpha_min: int = 1, cover_min: int = 128, min_visible: float = 0.0, masks: bool = False,
                      polygons: bool = False, max_edges: Optional[int] = None, simplify: Optional[float] = None,
-                     obb: bool = False):
+                     obb: bool = False, rle: bool = False):
         """``run`` plus the YOLO lines of every scene (``scene_labels``):
         labels[s] lists scene s's lines in layer order, one per overlay with
         visible > 0 and visible / area >= min_visible.  Returns (out, labels);
@@ -470,11 +521,15 @@ class SceneRunner(_Runner):
         the map launch, the tracer and the pack run once for both, the boxes
         always come from the unsimplified outline (``simplify`` changes the
         segmentation lines only), and with ``obb`` alone no vertex is copied
-        back.  Their corners are not clipped to the image."""
+        back.  Their corners are not clipped to the image.  With ``rle`` the
+        tuple gains, as its last element (after the OBB lines if any), the COCO
+        annotations of ``scene_coco_annotations`` (encodings of
+        ``scene_rles``, compressed counts, image id = scene index), from that
+        same map launch."""
         alpha_min, cover_min = _check_level("alpha_min", alpha_min), _check_level("cover_min", cover_min)
         if simplify is not None and not polygons:
             raise ValueError("SceneRunner.run_labelled: simplify needs polygons=True")
-        if masks or polygons or obb:
+        if masks or polygons or obb or rle:
             self._check_map("run_labelled", None)
         eps_q = None
         if polygons or obb:
@@ -484,7 +539,7 @@ class SceneRunner(_Runner):
         if obb:
             self._check_obb("run_labelled")
         self.run(src, bgs, out)
-        if masks or polygons or obb:
+        if masks or polygons or obb or rle:
             buf, rows = self._launch_map("run_labelled", alpha_min, cover_min, True, None)
         else:
             rows = self._launch_boxes(alpha_min, cover_min)
@@ -499,4 +554,6 @@ class SceneRunner(_Runner):
                 res += (scene_seg_labels(polys, info, boxes, bg_w, bg_h, class_ids, min_visible),)
             if obb:
                 res += (scene_obb_labels(obbs, info, boxes, bg_w, bg_h, class_ids, min_visible),)
+        if rle:
+            res += (scene_coco_annotations(self._rles(buf, rows), boxes, bg_w, bg_h, class_ids, min_visible),)
         return res

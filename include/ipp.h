@@ -611,6 +611,66 @@ int ipp_polygons_obb(const int32_t* verts, const int64_t* offsets, const int32_t
                      int64_t total_vertices, int32_t bg_w, int32_t bg_h, uint8_t* scratch,
                      int32_t* obb /* [n_images][IPP_OBB_REC] */, void* stream);
 
+/* COCO run-length encoding of scenes: the exact mask of each overlay's visible
+ * pixels — every part, every hole — as the COCO API's uncompressed RLE of the
+ * bg_h x bg_w mask, encoded on the device from the visibility maps.  map,
+ * map_pitch, rows (device int32[n_images][6], descriptor order) and
+ * scene_layer are what ipp_pipe_scene_map takes and writes; only the map and
+ * the rows are read (not tmp), so these entries may run any time after the map
+ * launch on the same stream.  This project's normative definition, in exact
+ * integers:
+ *
+ * FOREGROUND.  For descriptor i = (scene s, layer k), F is what
+ * ipp_scene_contours calls the foreground: the pixels of the half-open box
+ * rows[i][0:4] whose byte in scene s's map has bit k set.
+ * ORDER.  Pixels are ordered column-major over the whole background: pixel (X,
+ * Y) has position p = X·bg_h + Y, and N = bg_w·bg_h.
+ * TRANSITIONS.  With M(p) = 1 iff p is in F, and M(-1) = 0, the transitions
+ * are the positions t_1 < ... < t_T in [0, N) with M(p) != M(p-1).
+ * COUNTS.  t_1, t_2 - t_1, ..., t_T - t_(T-1), N - t_T: T + 1 counts that
+ * alternate zeros-run, ones-run, starting with a zeros-run (the first count is
+ * 0 when pixel (0, 0) is in F), and sum to N.  A box without a set bit gives
+ * the single count N.  Runs continue across columns: the last row of column X
+ * and the first of column X + 1 are neighbours.
+ * CROSS-CHECKS.  The ones-runs (counts 1, 3, ...) sum to `visible` of
+ * ipp_pipe_scene_boxes; the mask's bounding box is the row's box.
+ *
+ * ipp_scene_rle: hdr (device int32[n_images][IPP_RLE_HDR]) receives {n_counts,
+ * n_ones} per descriptor: n_counts = T + 1, n_ones = the sum of the ones-runs.
+ * A descriptor whose row is (-1,-1,-1,-1) (or whose box does not lie in the
+ * map) or that scene_layer does not map into n_scenes x per_scene gets {0, 0}.
+ * Every word of every header is written.
+ * ipp_scene_rle_pack, after it on the same stream with the same arguments and
+ * scratch: writes descriptor i's n_counts counts as uint32 at counts +
+ * offsets[i] (offsets: device int64[n_images], computed by the caller from the
+ * copied-back headers, e.g. the running sum of n_counts, so the packed buffer
+ * is exactly as large as the encodings).  It writes nothing for a descriptor
+ * whose header has n_counts == 0, and nothing else anywhere.
+ * One lane per four adjacent columns (one dword of a map row), 256 columns per
+ * 64-thread block, ⌈bg_w / 256⌉ blocks per descriptor; those outside the box
+ * (known only on the device) exit at once.  The map is read inside the boxes
+ * only, once per entry.  There is no atomic: nothing depends on any order.
+ * scratch: device, 16-B aligned, ipp_scene_rle_scratch_bytes(n_images, bg_w) =
+ * 9·n_images·(4·⌈bg_w / 4⌉) rounded up to 256 B: per descriptor and column a
+ * uint32 transition count and a uint32 last transition (after the scan: the
+ * column's first slot and the last transition before it), and per four columns
+ * a uint32 number of set pixels.
+ * IPP_E_ARG, before any launch: a NULL pointer; map or scratch not 16-B
+ * aligned, offsets not 8-B, another pointer not 4-B aligned; per_scene outside
+ * 1..IPP_SCENE_MAP_MAX_LAYERS; map_pitch < bg_w, not a multiple of 16 or >=
+ * 2^31; bg_w or bg_h < 1; bg_w·bg_h >= 2^30 (positions and counts fit 32 bits
+ * with room); n_images or n_scenes negative; n_images·⌈bg_w / 256⌉ >= 2^31 - 1
+ * (the grid).  n_images == 0 is IPP_OK, launches and writes nothing. */
+#define IPP_RLE_HDR 2
+int64_t ipp_scene_rle_scratch_bytes(int32_t n_images, int32_t bg_w);
+int ipp_scene_rle(const uint8_t* map, int64_t map_pitch, int32_t bg_w, int32_t bg_h,
+                  const int32_t* rows, const int32_t* scene_layer, int32_t n_images,
+                  int32_t n_scenes, int32_t per_scene, uint8_t* scratch, int32_t* hdr, void* stream);
+int ipp_scene_rle_pack(const uint8_t* map, int64_t map_pitch, int32_t bg_w, int32_t bg_h,
+                       const int32_t* rows, const int32_t* scene_layer, int32_t n_images,
+                       int32_t n_scenes, int32_t per_scene, const uint8_t* scratch, const int32_t* hdr,
+                       const int64_t* offsets, uint32_t* counts, void* stream);
+
 /* ------------------------------------------------------------------------ */
 /* K10-K13: pixels_isolés.keep_largest_component                             */
 /* :32 threshold(α,1,255) :35 connectedComponentsWithStats(8) :38-55 keep    */
