@@ -158,6 +158,7 @@ SIGNATURES = {
     "ipp_pipe_scene_scratch_bytes": (_L, [_I, _I, _I, _I, _I]),
     "ipp_pipe_scene_boxes": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "ipp_pipe_scene_map": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _L, _P]),
+    "ipp_pipe_scene_cull": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "ipp_scene_contours_scratch_bytes": (_L, [_I, _I]),
     "ipp_scene_contours": (_I, [_P, _L, _I, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "ipp_scene_contours_pack": (_I, [_P, _P, _P, _I, _I, _P, _P]),

@@ -20,6 +20,11 @@
 //   per composite, bit k = layer k visible (instance masks), from the same
 //   planes; optionally the boxes with it.
 //
+//   ipp_pipe_scene_cull: the rule once more, top down and with a verdict —
+//   an overlay that the kept later layers leave too little of is culled: its T
+//   is overwritten with 0x80, the T of a transparent overlay, so the V launches
+//   paste nothing of it and every later reader of tmp sees it absent.
+//
 // All follow ipp_alpha_bbox's convention (ipp_gather.hip): the boxes are
 // pre-set to (INT_MAX, INT_MAX, -1, -1), every wave that saw a visible pixel
 // issues four device-scope atomics, and a finish kernel turns an untouched row
@@ -473,6 +478,142 @@ int scene_launches(const uint8_t* tmp, const int32_t* coefs, const ipp_pipe_desc
     return IPP_OK;
 }
 
+// ---------------------------------------------------------------------------
+// ipp_pipe_scene_cull: cull the overlays the later layers leave too little of,
+// between the H launches and the first V launch (include/ipp.h states the rule).
+//
+// Same scratch, slot table and alpha planes as the boxes (k_scene_table,
+// k_scene_alpha).  `cull` (int32[n][4] = keep, area, visible, 0) is zeroed and
+// serves as the counters.  Then one k_cull_count launch per layer, K-1 down to
+// 0: k_scene_visible's walk without the box, for the descriptors of that layer
+// alone (the unmapped ones ride with the first launch: alone in their scene,
+// they wait for nobody), whose later-layer loop skips the layers that are
+// culled.  Whether layer j > k is culled is cull_keep of its two counters,
+// which the earlier launches of the stream have finished; the counters are
+// sums of integer atomicAdds, so no result depends on the atomics' order.
+// k_cull_clear evaluates the same predicate for every descriptor, writes the
+// verdict, and stores 0x80 over the T of the culled ones.
+//
+// T of a descriptor, as the H launch writes it (ipp_pipe.hip: one block per 16
+// T rows, a lane per group): group rows [0, 4·⌈h.lines/16⌉) of h.out_len
+// 16-B groups each, at tmp + h.dst_off + g·h.dst_pitch + 16·x.  t_groups()
+// sizes the item's T for at least these rows (its first term), so the clear
+// stays inside the descriptor's own T.  The rows a V tile's window reads past
+// them are the ones no H launch writes either: every tap there is 0.
+// ---------------------------------------------------------------------------
+__host__ __device__ __forceinline__ bool cull_keep(int area, int vis, int min_q, int min_pixels) {
+    return vis >= (min_pixels > 1 ? min_pixels : 1) && (int64_t)65536 * vis >= (int64_t)min_q * area;
+}
+
+__global__ void __launch_bounds__(256)
+k_cull_count(const ipp_pipe_desc* __restrict__ descs, const int32_t* __restrict__ scene_layer,
+             const int32_t* __restrict__ table, const uint8_t* __restrict__ planes, FastDiv strips, int n,
+             int n_scenes, int K, int cur, int max_ov_w, int max_ov_h, int alpha_min, int cover_min, int min_q,
+             int min_pixels, int32_t* cull) {
+    const uint32_t b = xcd_remap(blockIdx.x, gridDim.x);
+    const int im = (int)fdiv(b, strips);
+    const int v0 = (int)(b - (uint32_t)im * strips.d) * SVR;
+    const int scene = scene_layer[2 * im], layer = scene_layer[2 * im + 1];
+    const bool mapped = (unsigned)scene < (unsigned)n_scenes && (unsigned)layer < (unsigned)K;
+    if ((mapped ? layer : K - 1) != cur) return;  // another launch's descriptor (block-uniform)
+    const ipp_paste_desc p = descs[im].p;
+    if (v0 >= p.ov_h || p.ov_w > max_ov_w || p.ov_h > max_ov_h) return;  // block-uniform
+    const int64_t pitch = scene_pitch(max_ov_w), psize = (int64_t)max_ov_h * pitch;
+    const uint8_t* plane = planes + (int64_t)im * psize;
+    const int v = v0 + (int)(threadIdx.x >> 4);
+    int area = 0, vis = 0;
+    // 4 pixels of one row per thread and step, as in k_scene_visible
+    for (int u0 = 4 * (int)(threadIdx.x & 15); u0 < p.ov_w; u0 += 64) {
+        uint32_t a4 = 0u;
+        if (v < p.ov_h) a4 = *reinterpret_cast<const uint32_t*>(plane + (int64_t)v * pitch + u0);
+        uint32_t present = 0u;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            present |= (uint32_t)(v < p.ov_h && u0 + k < p.ov_w && (int)((a4 >> (8 * k)) & 255u) >= alpha_min) << k;
+        uint32_t hidden = 0u;
+        // the kept later layers of the scene (the loop is block-uniform)
+        for (int j = mapped ? layer + 1 : K; j < K; ++j) {
+            const int dj = table[(int64_t)scene * K + j];
+            if ((unsigned)dj >= (unsigned)n) continue;
+            const ipp_paste_desc q = descs[dj].p;
+            if (q.ov_w > max_ov_w || q.ov_h > max_ov_h) continue;  // no plane
+            // layer j's counters are final: its launch came earlier in the stream
+            if (!cull_keep(cull[4 * (int64_t)dj + 1], cull[4 * (int64_t)dj + 2], min_q, min_pixels)) continue;
+            const int cy = p.y + v - q.y;  // the row in layer j's overlay
+            if ((unsigned)cy >= (unsigned)q.ov_h) continue;
+            const uint8_t* qrow = planes + (int64_t)dj * psize + (int64_t)cy * pitch;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int cx = p.x + u0 + k - q.x;
+                if (((present >> k) & 1u) && (unsigned)cx < (unsigned)q.ov_w && (int)qrow[cx] >= cover_min)
+                    hidden |= 1u << k;
+            }
+        }
+        area += __builtin_popcount(present);
+        vis += __builtin_popcount(present & ~hidden);
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        area += __shfl_xor(area, off);
+        vis += __shfl_xor(vis, off);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (area) atomicAdd(&cull[4 * (int64_t)im + 1], area);
+        if (vis) atomicAdd(&cull[4 * (int64_t)im + 2], vis);
+    }
+}
+
+constexpr int kCullClearBlocks = 16;  // blocks per descriptor of k_cull_clear, striding over its T groups
+
+__global__ void __launch_bounds__(256)
+k_cull_clear(uint8_t* __restrict__ tmp, const ipp_pipe_desc* __restrict__ descs, int max_ov_w, int max_ov_h,
+             int min_q, int min_pixels, int32_t* __restrict__ cull) {
+    const int im = (int)(blockIdx.x / kCullClearBlocks), part = (int)(blockIdx.x % kCullClearBlocks);
+    const ipp_paste_desc p = descs[im].p;
+    int32_t* row = cull + 4 * (int64_t)im;
+    // a descriptor without a plane was never counted: it is kept as it is
+    const bool keep = p.ov_w > max_ov_w || p.ov_h > max_ov_h || cull_keep(row[1], row[2], min_q, min_pixels);
+    if (part == 0 && threadIdx.x == 0) {
+        row[0] = keep ? 1 : 0;
+        row[3] = 0;
+    }
+    if (keep) return;  // block-uniform
+    const ipp_resample_desc h = descs[im].h;
+    const int G = ((h.lines + 15) >> 4) << kTGroupRowsLog2;  // the H launch's group rows, h.out_len groups each
+    const uint32_t w[4] = {0x80808080u, 0x80808080u, 0x80808080u, 0x80808080u};
+    // a wave per group row, its lanes over the row's groups
+    for (int g = 4 * part + (int)(threadIdx.x >> 6); g < G; g += 4 * kCullClearBlocks) {
+        uint8_t* trow = tmp + h.dst_off + (int64_t)g * h.dst_pitch;
+        for (int x = (int)(threadIdx.x & 63); x < h.out_len; x += 64)
+            store16<0>(trow + (int64_t)kTGroupBytes * x, kTGroupBytes, true, w);
+    }
+}
+
+int cull_launches(uint8_t* tmp, const int32_t* coefs, const ipp_pipe_desc* descs, const int32_t* scene_layer,
+                  int n_images, int n_scenes, int per_scene, int max_ov_w, int max_ov_h, int alpha_min, int cover_min,
+                  int min_q, int min_pixels, uint8_t* scratch, int32_t* cull, hipStream_t s) {
+    const int tyb = paste_max_bands(max_ov_h), strips = (max_ov_h + SVR - 1) / SVR;
+    const int64_t slots = (int64_t)n_scenes * per_scene;
+    if ((int64_t)tyb * n_images >= INT32_MAX || (int64_t)strips * n_images >= INT32_MAX || slots >= INT32_MAX ||
+        (int64_t)kCullClearBlocks * n_images >= INT32_MAX)
+        return IPP_E_ARG;
+    int32_t* table = reinterpret_cast<int32_t*>(scratch);
+    uint8_t* planes = scratch + scene_table_bytes(slots);
+    if (slots > 0 && hipMemsetAsync(table, 0xFF, 4 * (size_t)slots, s) != hipSuccess) return IPP_E_LAUNCH;
+    if (hipMemsetAsync(cull, 0, 16 * (size_t)n_images, s) != hipSuccess) return IPP_E_LAUNCH;
+    hipLaunchKernelGGL(k_scene_table, dim3((n_images + 255) / 256), dim3(256), 0, s, table, scene_layer, n_images,
+                       n_scenes, per_scene);
+    hipLaunchKernelGGL(k_scene_alpha, dim3((uint32_t)(tyb * n_images)), dim3(256), 0, s, tmp, coefs, descs,
+                       fast_div((uint32_t)tyb), max_ov_w, max_ov_h, planes);
+    for (int k = per_scene - 1; k >= 0; --k)
+        hipLaunchKernelGGL(k_cull_count, dim3((uint32_t)(strips * n_images)), dim3(256), 0, s, descs, scene_layer, table,
+                           planes, fast_div((uint32_t)strips), n_images, n_scenes, per_scene, k, max_ov_w, max_ov_h,
+                           alpha_min, cover_min, min_q, min_pixels, cull);
+    hipLaunchKernelGGL(k_cull_clear, dim3((uint32_t)(kCullClearBlocks * n_images)), dim3(256), 0, s, tmp, descs,
+                       max_ov_w, max_ov_h, min_q, min_pixels, cull);
+    IPP_CHECK_LAUNCH();
+    return IPP_OK;
+}
+
 }  // namespace
 
 extern "C" int ipp_pipe_overlay_bbox_trim(const uint8_t* tmp, const int32_t* coefs, const ipp_pipe_desc* descs,
@@ -559,4 +700,22 @@ extern "C" int ipp_pipe_scene_map(const uint8_t* tmp, const int32_t* coefs, cons
     if (((reinterpret_cast<uintptr_t>(scratch) | reinterpret_cast<uintptr_t>(map)) & 15u) != 0) return IPP_E_ARG;
     return scene_launches(tmp, coefs, descs, scene_layer, n_images, n_scenes, per_scene, bg_w, bg_h, max_ov_w,
                           max_ov_h, alpha_min, cover_min, scratch, rows, map, map_pitch, (hipStream_t)stream);
+}
+
+extern "C" int ipp_pipe_scene_cull(uint8_t* tmp, const int32_t* coefs, const ipp_pipe_desc* descs,
+                                   const int32_t* scene_layer, int32_t n_images, int32_t n_scenes, int32_t per_scene,
+                                   int32_t max_ov_w, int32_t max_ov_h, int32_t alpha_min, int32_t cover_min,
+                                   int32_t min_q, int32_t min_pixels, int32_t tap_format, uint8_t* scratch,
+                                   int32_t* cull, void* stream) {
+    if (alpha_min < 1 || alpha_min > 255 || cover_min < 1 || cover_min > 255 || tap_format != IPP_TAPS_MFMA)
+        return IPP_E_ARG;
+    if (min_q < 0 || min_q > 65536 || min_pixels < 0) return IPP_E_ARG;
+    if (!tmp || !coefs || !descs || !scene_layer || !scratch || !cull || n_images < 0 || n_scenes < 0 ||
+        per_scene < 1 || max_ov_w <= 0 || max_ov_h <= 0)
+        return IPP_E_ARG;
+    // the planes are read by dwords, T is cleared by 16-B vectors
+    if (((reinterpret_cast<uintptr_t>(scratch) | reinterpret_cast<uintptr_t>(tmp)) & 15u) != 0) return IPP_E_ARG;
+    if (n_images == 0) return IPP_OK;
+    return cull_launches(tmp, coefs, descs, scene_layer, n_images, n_scenes, per_scene, max_ov_w, max_ov_h, alpha_min,
+                         cover_min, min_q, min_pixels, scratch, cull, (hipStream_t)stream);
 }

@@ -13,6 +13,7 @@ reads a mask back.  ``fused`` re-exports it all.
 """
 from __future__ import annotations
 
+import math
 from typing import List, Optional, Tuple
 
 import numpy as np
@@ -88,6 +89,23 @@ def scene_labels(boxes: np.ndarray, bg_w: int, bg_h: int, class_ids=0, min_visib
     for s, _, class_id, row in _label_lines(boxes, class_ids, min_visible):
         out[s].append(yolo_label(class_id, tuple(int(v) for v in row[:4]), bg_w, bg_h))
     return out
+
+
+def min_visible_q(min_visible) -> int:
+    """``min_q`` of ipp_pipe_scene_cull for a visible fraction ``min_visible``,
+    a real number in [0, 1]: ⌈min_visible·65536⌉ (the product is exact, a
+    scaling by a power of two).  Anything else raises ValueError.  With the
+    ceiling, 65536·visible >= min_q·area implies visible >= min_visible·area in
+    the reals, and rounding that product to a float cannot lift it above the
+    integer `visible`: an overlay the cull keeps always passes the test of
+    ``scene_labels`` with the same ``min_visible``."""
+    if isinstance(min_visible, (bool, np.bool_)) or \
+            not isinstance(min_visible, (int, float, np.integer, np.floating)):
+        raise ValueError(f"min_visible {min_visible!r}: a real number in 0..1 expected")
+    v = float(min_visible)
+    if not 0.0 <= v <= 1.0:     # (NaN fails both comparisons)
+        raise ValueError(f"min_visible {min_visible!r}: a real number in 0..1 expected")
+    return int(math.ceil(v * 65536.0))
 
 
 def scene_map_pitch(bg_w: int) -> int:

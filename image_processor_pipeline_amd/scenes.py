@@ -9,7 +9,9 @@ copy (``ipp_pipe_hpass``) and an in-place V launch (``ipp_pipe_vblend_over``)
 composite, and ``scene_polygons`` traces (and simplifies) each overlay's outer
 contour from it on the device; ``scene_obbs`` reduces that contour there to its
 minimum-area rectangle (YOLO-OBB), and ``scene_rles`` run-length encodes each
-overlay's exact visible mask there (COCO RLE).  labels_fmt.py formats the lines,
+overlay's exact visible mask there (COCO RLE).  ``run_culled`` decides on the
+device, between the H and the V launches, which overlays the later layers leave
+too little of, and pastes only the others.  labels_fmt.py formats the lines,
 masks and annotations; every public name here is also reachable as ``fused.X``.
 """
 from __future__ import annotations
@@ -25,8 +27,8 @@ from .device import _stream, _to_dev, exclusive_offsets
 from .device import check_alpha_min as _check_alpha_min
 from .fused import (ItemParams, PipeConfig, PipePlan, _launch_hpass_bgcopy, _launch_vblend_bands, _Runner,
                     draw_params, plan_pipe)
-from .labels_fmt import (scene_coco_annotations, scene_contour_capacity, scene_labels, scene_map_pitch,
-                         scene_obb_labels, scene_seg_labels, simplify_tolerance)
+from .labels_fmt import (min_visible_q, scene_coco_annotations, scene_contour_capacity, scene_labels,
+                         scene_map_pitch, scene_obb_labels, scene_seg_labels, simplify_tolerance)
 
 
 def draw_scene_params(n_scenes_global: int, stop_scene: int, per_scene: int, src_hw: Tuple[int, int],
@@ -160,8 +162,8 @@ class SceneRunner(_Runner):
             raise ValueError(f"SceneRunner.{caller}: bgs of shape {tuple(bgs.shape)} does not hold the plan's "
                              f"backgrounds (n, {p.bg_h}, {p.bg_w}, 3)")
 
-    def run(self, src: torch.Tensor, bgs: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
-        self._check("run", src, bgs, out)
+    def _launch_h(self, src: torch.Tensor, bgs: torch.Tensor, out: torch.Tensor) -> None:
+        """The H launches of the batch: layer 0 with the background copy, the later layers in one launch."""
         p, S, K = self.plan.pipe, self.plan.n_scenes, self.plan.per_scene
         st, lib = _stream(self.device), self.lib
         _launch_hpass_bgcopy(lib, p, src.data_ptr(), self.tmp.data_ptr(), self.coefs.data_ptr(), self._dptr(0), S,
@@ -171,6 +173,11 @@ class SceneRunner(_Runner):
                                        S * (K - 1), p.max_out_w, p.max_rows, 3, N.np_ptr(p.hsv), p.tap_format, st),
                     "ipp_pipe_hpass")
         self._hpass_done = True
+
+    def _launch_v(self, bgs: torch.Tensor, out: torch.Tensor) -> None:
+        """The V launches: layer 0's, then one in-place launch per later layer."""
+        p, S, K = self.plan.pipe, self.plan.n_scenes, self.plan.per_scene
+        st, lib = _stream(self.device), self.lib
         _launch_vblend_bands(lib, p, self.tmp.data_ptr(), bgs.data_ptr(), out.data_ptr(), self.coefs.data_ptr(),
                              self._dptr(0), S, st)
         # one launch per later layer: two overlays of a scene never share a launch (ipp.h)
@@ -178,7 +185,71 @@ class SceneRunner(_Runner):
             N.check(lib.ipp_pipe_vblend_over(self.tmp.data_ptr(), out.data_ptr(), self.coefs.data_ptr(),
                                              self._dptr(k * S), S, p.bg_w, p.bg_h, p.max_ov_w, p.max_ov_h,
                                              p.tap_format, st), "ipp_pipe_vblend_over")
+
+    def run(self, src: torch.Tensor, bgs: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+        self._check("run", src, bgs, out)
+        self._launch_h(src, bgs, out)
+        self._launch_v(bgs, out)
         return out
+
+    @staticmethod
+    def _check_cull(caller: str, min_visible, min_pixels) -> Tuple[int, int]:
+        """(min_q, min_pixels) of a cull, refusing what ipp_pipe_scene_cull would."""
+        min_q = min_visible_q(min_visible)
+        if isinstance(min_pixels, (bool, np.bool_)) or not isinstance(min_pixels, (int, np.integer)) or \
+                not 0 <= min_pixels < 1 << 31:
+            raise ValueError(f"SceneRunner.{caller}: min_pixels {min_pixels!r}: an integer >= 0 (below 2^31)")
+        return min_q, int(min_pixels)
+
+    def _launch_cull(self, caller: str, alpha_min: int, cover_min: int, min_q: int, min_pixels: int) -> torch.Tensor:
+        """ipp_pipe_scene_cull between the H and the V launches: the device records, 4 int32 per descriptor."""
+        self._scene_scratch(caller)
+        p, S, K = self.plan.pipe, self.plan.n_scenes, self.plan.per_scene
+        rec = torch.empty(4 * len(self.plan.descs), dtype=torch.int32, device=self.device)
+        N.check(self.lib.ipp_pipe_scene_cull(self.tmp.data_ptr(), self.coefs.data_ptr(), self._dptr(0),
+                                             self._scene_layer.data_ptr(), S * K, S, K, p.max_ov_w, p.max_ov_h,
+                                             alpha_min, cover_min, min_q, min_pixels, p.tap_format,
+                                             self._scratch.data_ptr(), rec.data_ptr(), _stream(self.device)),
+                "ipp_pipe_scene_cull")
+        return rec
+
+    def _cull_by_scene(self, rec: torch.Tensor) -> Tuple[np.ndarray, np.ndarray]:
+        """Copy the cull records back (synchronises): kept (S, K) bool and stats (S, K, 2) int32, scene, layer order."""
+        by_desc = rec.cpu().numpy().reshape(-1, 4)
+        by_item = np.empty_like(by_desc)
+        by_item[self.plan.desc_item] = by_desc
+        by_item = by_item.reshape(self.plan.n_scenes, self.plan.per_scene, 4)
+        return by_item[..., 0] != 0, np.ascontiguousarray(by_item[..., 1:3])
+
+    def run_culled(self, src: torch.Tensor, bgs: torch.Tensor, out: torch.Tensor, alpha_min: int = 1,
+                   cover_min: int = 128, min_visible: float = 0.0, min_pixels: int = 1):
+        """``run`` without the overlays that the later layers leave too little
+        of: the H launches, ipp_pipe_scene_cull, the V launches.  The layers of
+        a scene are decided top down (include/ipp.h states the rule in
+        integers): an overlay is kept iff, counting as ``scene_boxes`` does but
+        against the KEPT later layers only, visible >= max(min_pixels, 1) and
+        visible / area >= min_visible (``min_visible_q``).  A culled overlay is
+        not pasted and hides nothing, so an overlay that only a culled one
+        would hide is kept.  Returns (out, kept, stats): kept is an (S, K) bool
+        array and stats (S, K, 2) int32 = (area, visible) at the moment of the
+        decision, both in scene, layer order; that copy back synchronises.
+        Every painted overlay then has a line in ``scene_labels`` at the same
+        thresholds, and every line a painted overlay.
+
+        The cull clears the culled overlays' part of the H launches' scratch:
+        until the next ``run`` (or ``run_culled`` / ``run_labelled``) rewrites
+        it in full, ``scene_boxes``, ``scene_masks``, ``scene_polygons``,
+        ``scene_obbs`` and ``scene_rles`` on this runner report the culled
+        overlays as absent — row (-1, -1, -1, -1, 0, 0), no bit in the map, no
+        polygon, box or encoding — which is what the composite shows."""
+        alpha_min, cover_min = _check_level("alpha_min", alpha_min), _check_level("cover_min", cover_min)
+        min_q, min_pixels = self._check_cull("run_culled", min_visible, min_pixels)
+        self._check("run_culled", src, bgs, out)
+        self._launch_h(src, bgs, out)
+        rec = self._launch_cull("run_culled", alpha_min, cover_min, min_q, min_pixels)
+        self._launch_v(bgs, out)
+        kept, stats = self._cull_by_scene(rec)
+        return out, kept, stats
 
     def _scratch_bytes(self, entry: str, *args) -> int:
         """What the library's `entry` (a ``*_scratch_bytes`` function) asks for these arguments."""
@@ -507,7 +578,7 @@ class SceneRunner(_Runner):
     def run_labelled(self, src: torch.Tensor, bgs: torch.Tensor, out: torch.Tensor, class_ids=0,
                      alpha_min: int = 1, cover_min: int = 128, min_visible: float = 0.0, masks: bool = False,
                      polygons: bool = False, max_edges: Optional[int] = None, simplify: Optional[float] = None,
-                     obb: bool = False, rle: bool = False):
+                     obb: bool = False, rle: bool = False, cull: bool = False, min_pixels: int = 1):
         """``run`` plus the YOLO lines of every scene (``scene_labels``):
         labels[s] lists scene s's lines in layer order, one per overlay with
         visible > 0 and visible / area >= min_visible.  Returns (out, labels);
@@ -525,8 +596,20 @@ class SceneRunner(_Runner):
         tuple gains, as its last element (after the OBB lines if any), the COCO
         annotations of ``scene_coco_annotations`` (encodings of
         ``scene_rles``, compressed counts, image id = scene index), from that
-        same map launch."""
+        same map launch.  With ``cull`` the run is ``run_culled``'s — the H
+        launches, the cull with ``min_visible`` as its threshold and
+        ``min_pixels``, the V launches — everything above is produced as
+        always, from the cleared scratch (a culled overlay has row (-1, -1,
+        -1, -1, 0, 0), no line, no map bit, no polygon, box or annotation; a
+        kept one always has its line), and the tuple gains ``kept``, the
+        (S, K) bool array of ``run_culled``, as its last element.  The
+        scratch stays cleared afterwards, as ``run_culled`` describes.
+        ``min_visible`` must then lie in 0..1."""
         alpha_min, cover_min = _check_level("alpha_min", alpha_min), _check_level("cover_min", cover_min)
+        if not isinstance(cull, (bool, np.bool_)):
+            raise ValueError(f"SceneRunner.run_labelled: cull {cull!r}: a bool")
+        if cull:
+            min_q, min_pixels = self._check_cull("run_labelled", min_visible, min_pixels)
         if simplify is not None and not polygons:
             raise ValueError("SceneRunner.run_labelled: simplify needs polygons=True")
         if masks or polygons or obb or rle:
@@ -538,7 +621,14 @@ class SceneRunner(_Runner):
             eps_q = self._check_simplify("run_labelled", simplify)
         if obb:
             self._check_obb("run_labelled")
-        self.run(src, bgs, out)
+        rec = None
+        if cull:
+            self._check("run_labelled", src, bgs, out)
+            self._launch_h(src, bgs, out)
+            rec = self._launch_cull("run_labelled", alpha_min, cover_min, min_q, min_pixels)
+            self._launch_v(bgs, out)
+        else:
+            self.run(src, bgs, out)
         if masks or polygons or obb or rle:
             buf, rows = self._launch_map("run_labelled", alpha_min, cover_min, True, None)
         else:
@@ -556,4 +646,6 @@ class SceneRunner(_Runner):
                 res += (scene_obb_labels(obbs, info, boxes, bg_w, bg_h, class_ids, min_visible),)
         if rle:
             res += (scene_coco_annotations(self._rles(buf, rows), boxes, bg_w, bg_h, class_ids, min_visible),)
+        if cull:
+            res += (self._cull_by_scene(rec)[0],)
         return res

@@ -403,6 +403,46 @@ int ipp_pipe_scene_map(const uint8_t* tmp, const int32_t* coefs, const ipp_pipe_
                        int32_t alpha_min, int32_t cover_min, int32_t tap_format,
                        uint8_t* scratch, int32_t* rows /* may be NULL */,
                        uint8_t* map, int64_t map_pitch, void* stream);
+/* Cull the overlays of scenes that the later layers leave too little of,
+ * BEFORE anything is pasted: after every H launch of the batch and before the
+ * first V launch, all on one stream.  A culled overlay's T (its part of tmp) is
+ * overwritten with 0x80 in every byte — the T of a fully transparent overlay:
+ * the V launches derive alpha 0 from it at every pixel and Paste.c's blend at
+ * alpha 0 returns the background byte, DIV255(255·b + 128) = b — so the V
+ * launches stay as they are (layer 0's must run anyway: it writes the band
+ * bytes the H launch's copy left out), the composite is the one without the
+ * overlay, and every later reader of tmp (ipp_pipe_scene_boxes,
+ * ipp_pipe_scene_map and what is traced or encoded from the map) sees the
+ * overlay as absent, until the next H launch rewrites its T.
+ *
+ * The rule, with A_k, PRESENT, scene_layer and the planes as for
+ * ipp_pipe_scene_boxes; area_k = the present pixels of layer k.  The layers of
+ * a scene are decided top down, k = per_scene-1, ..., 0:
+ *   vis_k  = the present pixels of layer k where every KEPT later layer j > k
+ *            of the scene that has a plane and whose rectangle holds the
+ *            composite pixel has A_j < cover_min;
+ *   keep_k = vis_k >= max(min_pixels, 1)  and  65536·vis_k >= min_q·area_k
+ *            (int64), 0 <= min_q <= 65536, min_pixels >= 0.
+ * keep_k depends only on the layers above k, and a culled layer hides nothing:
+ * an overlay that only a culled overlay would hide is kept.  A descriptor
+ * larger than (max_ov_w, max_ov_h) has no plane: it is kept, not cleared, hides
+ * nothing, and its counts are 0.  A descriptor that scene_layer does not map
+ * into n_scenes x per_scene is decided as if alone in its scene.  per_scene has
+ * no upper limit here (one counting launch per layer).
+ * cull: device int32[n_images][4] = {keep (0 or 1), area, visible, 0} of every
+ * descriptor, area and visible as they were when it was decided; every word is
+ * written.  The T that is cleared is what the H launch wrote of the
+ * descriptor: the 16-B groups x < h.out_len of group rows g < 4·⌈h.lines/16⌉ at
+ * tmp + h.dst_off + g·h.dst_pitch + 16·x, with 16-B vector stores (tmp 16-B
+ * aligned); no other byte of tmp changes.  scratch: as for
+ * ipp_pipe_scene_boxes.  IPP_E_ARG, before any launch: a NULL pointer, a
+ * threshold outside its range, per_scene < 1, a tap_format other than
+ * IPP_TAPS_MFMA, a grid of 2^31 blocks or more. */
+int ipp_pipe_scene_cull(uint8_t* tmp, const int32_t* coefs, const ipp_pipe_desc* descs,
+                        const int32_t* scene_layer, int32_t n_images, int32_t n_scenes, int32_t per_scene,
+                        int32_t max_ov_w, int32_t max_ov_h, int32_t alpha_min, int32_t cover_min,
+                        int32_t min_q, int32_t min_pixels, int32_t tap_format,
+                        uint8_t* scratch, int32_t* cull, void* stream);
 
 /* Polygons of scenes: the outer contour of each overlay's visible pixels,
  * traced on the device from the visibility maps.  map, map_pitch, rows (device
