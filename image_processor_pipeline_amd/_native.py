@@ -159,6 +159,8 @@ SIGNATURES = {
     "ipp_pipe_scene_boxes": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "ipp_pipe_scene_map": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _L, _P]),
     "ipp_pipe_scene_cull": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "ipp_pipe_scene_amodal": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P,
+                                   _L, _P]),
     "ipp_scene_contours_scratch_bytes": (_L, [_I, _I]),
     "ipp_scene_contours": (_I, [_P, _L, _I, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "ipp_scene_contours_pack": (_I, [_P, _P, _P, _I, _I, _P, _P]),

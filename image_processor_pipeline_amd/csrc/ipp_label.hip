@@ -25,6 +25,11 @@
 //   is overwritten with 0x80, the T of a transparent overlay, so the V launches
 //   paste nothing of it and every later reader of tmp sees it absent.
 //
+//   ipp_pipe_scene_amodal: what the rule hides — per overlay the box and the
+//   map of its present pixels, covered or not (the amodal ground truth), and
+//   per pair of layers how many pixels the later one covers and hides, from the
+//   same planes; optionally the visible boxes and map with them.
+//
 // All follow ipp_alpha_bbox's convention (ipp_gather.hip): the boxes are
 // pre-set to (INT_MAX, INT_MAX, -1, -1), every wave that saw a visible pixel
 // issues four device-scope atomics, and a finish kernel turns an untouched row
@@ -614,7 +619,301 @@ int cull_launches(uint8_t* tmp, const int32_t* coefs, const ipp_pipe_desc* descs
     return IPP_OK;
 }
 
+// ---------------------------------------------------------------------------
+// ipp_pipe_scene_amodal: the full extent of every overlay behind its occluders
+// (include/ipp.h states the rule): the presence map, the amodal rows and the
+// pairwise occlusion counts, with the visible rows and map of
+// ipp_pipe_scene_map from the same alpha planes.
+//
+// Same scratch, slot table and alpha planes as the boxes.  In stream order:
+//   memsets         the slot table (0xFF) and occ (0);
+//   k_amodal_init   arows and rows (INT_MAX, INT_MAX, -1, -1, 0, 0), the table;
+//   k_scene_alpha   once, whatever is asked for;
+//   k_amodal_count  k_scene_visible's blocks and pixel groups (one block per
+//     descriptor and 16-row strip, 4 pixels of a row per thread and step), the
+//     later layers walked from the top down with the per-pixel `hidden` mask:
+//     of layer j, COVERS += popcount(present & cover_j) and HIDES +=
+//     popcount(present & cover_j & ~hidden) before hidden |= cover_j.  Each
+//     count is summed over the wave and added by lane 0 (integer atomicAdd:
+//     no result depends on the atomics' order); the present box and, when
+//     `rows` is given, the visible box go through bbox_commit;
+//   k_amodal_finish untouched boxes become (-1, -1, -1, -1);
+//   k_amodal_map    k_scene_map's sweep storing the presence and / or the
+//     visibility map: one 16-B vector per thread and map, one writer per byte.
+// Phase 1 of k_amodal_count is block-uniform: a later layer is kept only when
+// it is in [0, n), has a plane and its rectangle meets the strip's rows and the
+// overlay's columns (64-bit, a foreign descriptor must not wrap), so inside
+// the loop 0 <= cy < ov_h <= max_ov_h and 0 <= cx < ov_w <= max_ov_w are the
+// only loads: every access lies in the plane of a descriptor in [0, n).
+// ---------------------------------------------------------------------------
+__global__ void k_amodal_init(int32_t* __restrict__ arows, int32_t* __restrict__ rows, int32_t* __restrict__ table,
+                              const int32_t* __restrict__ scene_layer, int n, int n_scenes, int K) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+#pragma unroll
+    for (int w = 0; w < 6; ++w) {
+        const int32_t v = w < 2 ? INT32_MAX : w < 4 ? -1 : 0;
+        arows[6 * i + w] = v;
+        if (rows) rows[6 * i + w] = v;
+    }
+    const int s = scene_layer[2 * i], k = scene_layer[2 * i + 1];
+    if ((unsigned)s < (unsigned)n_scenes && (unsigned)k < (unsigned)K) table[(int64_t)s * K + k] = i;
+}
+
+__global__ void k_amodal_finish(int32_t* __restrict__ arows, int32_t* __restrict__ rows, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (arows[6 * i + 2] < 0) arows[6 * i + 0] = arows[6 * i + 1] = -1;
+    if (rows && rows[6 * i + 2] < 0) rows[6 * i + 0] = rows[6 * i + 1] = -1;
+}
+
+__device__ __forceinline__ int wave_sum(int v) {
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+__global__ void __launch_bounds__(256)
+k_amodal_count(const ipp_pipe_desc* __restrict__ descs, const int32_t* __restrict__ scene_layer,
+               const int32_t* __restrict__ table, const uint8_t* __restrict__ planes, FastDiv strips, int n,
+               int n_scenes, int K, int max_ov_w, int max_ov_h, int alpha_min, int cover_min,
+               int32_t* __restrict__ arows, int32_t* __restrict__ occ, int32_t* __restrict__ rows) {
+    const uint32_t b = xcd_remap(blockIdx.x, gridDim.x);
+    const int im = (int)fdiv(b, strips);
+    const int v0 = (int)(b - (uint32_t)im * strips.d) * SVR;
+    const ipp_paste_desc p = descs[im].p;
+    if (v0 >= p.ov_h || p.ov_w > max_ov_w || p.ov_h > max_ov_h) return;  // block-uniform
+    const int64_t pitch = scene_pitch(max_ov_w), psize = (int64_t)max_ov_h * pitch;
+    const uint8_t* plane = planes + (int64_t)im * psize;
+    const int scene = scene_layer[2 * im], layer = scene_layer[2 * im + 1];
+    const bool mapped = (unsigned)scene < (unsigned)n_scenes && (unsigned)layer < (unsigned)K;
+
+    // Phase 1 (block-uniform): the later layers that can cover a pixel of this strip.
+    int d[kSceneMapMaxLayers], qx[kSceneMapMaxLayers], qy[kSceneMapMaxLayers], qw[kSceneMapMaxLayers],
+        qh[kSceneMapMaxLayers];
+#pragma unroll
+    for (int j = 0; j < kSceneMapMaxLayers; ++j) {
+        d[j] = -1;
+        qx[j] = qy[j] = qw[j] = qh[j] = 0;
+        if (!mapped || j <= layer || j >= K) continue;
+        const int dj = table[(int64_t)scene * K + j];
+        if ((unsigned)dj >= (unsigned)n) continue;  // no descriptor in this slot
+        const ipp_paste_desc q = descs[dj].p;
+        if (q.ov_w <= 0 || q.ov_h <= 0 || q.ov_w > max_ov_w || q.ov_h > max_ov_h) continue;  // no plane
+        const int64_t cy0 = (int64_t)p.y + v0 - q.y, cx0 = (int64_t)p.x - q.x;  // of the strip's first pixel
+        if (cy0 + SVR <= 0 || cy0 >= q.ov_h || cx0 + p.ov_w <= 0 || cx0 >= q.ov_w) continue;
+        d[j] = dj;
+        qx[j] = q.x, qy[j] = q.y, qw[j] = q.ov_w, qh[j] = q.ov_h;
+    }
+
+    const int v = v0 + (int)(threadIdx.x >> 4);
+    int axmin = INT32_MAX, aymin = INT32_MAX, axmax = -1, aymax = -1;  // the present box
+    int xmin = INT32_MAX, ymin = INT32_MAX, xmax = -1, ymax = -1;      // the visible box
+    int area = 0, vis = 0;
+    int cov[kSceneMapMaxLayers], hid[kSceneMapMaxLayers];
+#pragma unroll
+    for (int j = 0; j < kSceneMapMaxLayers; ++j) cov[j] = hid[j] = 0;
+    // 4 pixels of one row per thread and step, as in k_scene_visible
+    for (int u0 = 4 * (int)(threadIdx.x & 15); u0 < p.ov_w; u0 += 64) {
+        uint32_t a4 = 0u;
+        if (v < p.ov_h) a4 = *reinterpret_cast<const uint32_t*>(plane + (int64_t)v * pitch + u0);
+        uint32_t present = 0u;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            present |= (uint32_t)(v < p.ov_h && u0 + k < p.ov_w && (int)((a4 >> (8 * k)) & 255u) >= alpha_min) << k;
+        uint32_t hidden = 0u;
+        // Phase 2: the later layers, top down (layer 0 is nobody's later layer)
+#pragma unroll
+        for (int j = kSceneMapMaxLayers - 1; j > 0; --j) {
+            if (d[j] < 0) continue;  // block-uniform
+            const int cy = p.y + v - qy[j];  // the row in layer j's overlay
+            uint32_t c = 0u;
+            if ((unsigned)cy < (unsigned)qh[j]) {
+                const uint8_t* qrow = planes + (int64_t)d[j] * psize + (int64_t)cy * pitch;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int cx = p.x + u0 + k - qx[j];
+                    if (((present >> k) & 1u) && (unsigned)cx < (unsigned)qw[j] && (int)qrow[cx] >= cover_min)
+                        c |= 1u << k;
+                }
+            }
+            cov[j] += __builtin_popcount(c);
+            hid[j] += __builtin_popcount(c & ~hidden);
+            hidden |= c;
+        }
+        const uint32_t visible = present & ~hidden;
+        area += __builtin_popcount(present);
+        vis += __builtin_popcount(visible);
+        if (present) {
+            axmin = min(axmin, p.x + u0 + (int)__builtin_ctz(present));
+            axmax = max(axmax, p.x + u0 + 31 - (int)__builtin_clz(present));
+            aymin = min(aymin, p.y + v);
+            aymax = max(aymax, p.y + v);
+        }
+        if (visible) {
+            xmin = min(xmin, p.x + u0 + (int)__builtin_ctz(visible));
+            xmax = max(xmax, p.x + u0 + 31 - (int)__builtin_clz(visible));
+            ymin = min(ymin, p.y + v);
+            ymax = max(ymax, p.y + v);
+        }
+    }
+    area = wave_sum(area);
+    vis = wave_sum(vis);
+    const bool lane0 = (threadIdx.x & 63) == 0;
+    int32_t* arow = arows + 6 * (int64_t)im;
+    bbox_commit(arow, axmin, aymin, axmax, aymax);
+    if (lane0) {
+        if (area) atomicAdd(&arow[4], area);
+        if (vis) atomicAdd(&arow[5], vis);
+    }
+    if (rows) {  // (uniform) what k_scene_visible writes
+        int32_t* row = rows + 6 * (int64_t)im;
+        bbox_commit(row, xmin, ymin, xmax, ymax);
+        if (lane0) {
+            if (area) atomicAdd(&row[4], area);
+            if (vis) atomicAdd(&row[5], vis);
+        }
+    }
+    if (!mapped) return;  // block-uniform: alone in its scene, in no slot of occ
+    int32_t* oc0 = occ + (((int64_t)scene * 2) * K + layer) * K;  // occ[scene][0][layer][.]
+    int32_t* oc1 = oc0 + (int64_t)K * K;                          // occ[scene][1][layer][.]
+    if (lane0) {
+        if (area) atomicAdd(&oc0[layer], area);
+        if (vis) atomicAdd(&oc1[layer], vis);
+    }
+#pragma unroll
+    for (int j = 1; j < kSceneMapMaxLayers; ++j) {
+        if (d[j] < 0) continue;  // block-uniform
+        const int c = wave_sum(cov[j]), h = wave_sum(hid[j]);
+        if (lane0) {
+            if (c) atomicAdd(&oc0[j], c);
+            if (h) atomicAdd(&oc1[j], h);
+        }
+    }
+}
+
+// k_scene_map with two outputs: `amap` takes bit k wherever layer k is present,
+// `vmap` where it is also under no covering later layer (k_scene_map's byte).
+// Either may be null (uniform).  The thread map, the guards of every plane
+// access and the single writer per byte are k_scene_map's.
+__global__ void __launch_bounds__(256)
+k_amodal_map(const ipp_pipe_desc* __restrict__ descs, const int32_t* __restrict__ table,
+             const uint8_t* __restrict__ planes, FastDiv tiles, FastDiv tiles_x, int n, int K, int bg_w, int bg_h,
+             int max_ov_w, int max_ov_h, int alpha_min, int cover_min, uint8_t* __restrict__ amap,
+             uint8_t* __restrict__ vmap, int64_t map_pitch) {
+    const uint32_t b = xcd_remap(blockIdx.x, gridDim.x);
+    const int scene = (int)fdiv(b, tiles);
+    const uint32_t t = b - (uint32_t)scene * tiles.d;
+    const int ty = (int)fdiv(t, tiles_x), tx = (int)(t - (uint32_t)ty * tiles_x.d);
+    const int bx0 = tx * MT_W;                                                  // the block's columns
+    const int wy0 = ty * MT_H + 4 * __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // the wave's 4 rows
+    const int Y = ty * MT_H + (int)(threadIdx.x >> 4);
+    const int X0 = bx0 + MT_PX * (int)(threadIdx.x & 15);
+    const int64_t pitch = scene_pitch(max_ov_w), psize = (int64_t)max_ov_h * pitch;
+
+    // Phase 1 (block-uniform), as in k_scene_map.
+    int d[kSceneMapMaxLayers], px[kSceneMapMaxLayers], py[kSceneMapMaxLayers], pw[kSceneMapMaxLayers],
+        ph[kSceneMapMaxLayers];
+#pragma unroll
+    for (int k = 0; k < kSceneMapMaxLayers; ++k) {
+        d[k] = -1;
+        px[k] = py[k] = pw[k] = ph[k] = 0;
+        if (k >= K) continue;
+        const int dk = table[(int64_t)scene * K + k];
+        if ((unsigned)dk >= (unsigned)n) continue;  // no descriptor in this slot
+        const ipp_paste_desc p = descs[dk].p;
+        if (p.ov_w <= 0 || p.ov_h <= 0 || p.ov_w > max_ov_w || p.ov_h > max_ov_h) continue;  // no plane
+        const int64_t rx0 = max((int64_t)p.x, (int64_t)0), rx1 = min((int64_t)p.x + p.ov_w, (int64_t)bg_w);
+        const int64_t ry0 = max((int64_t)p.y, (int64_t)0), ry1 = min((int64_t)p.y + p.ov_h, (int64_t)bg_h);
+        if (rx0 >= (int64_t)bx0 + MT_W || rx1 <= bx0 || ry0 >= (int64_t)wy0 + 4 || ry1 <= wy0) continue;
+        d[k] = dk;
+        px[k] = p.x, py[k] = p.y, pw[k] = p.ov_w, ph[k] = p.ov_h;
+    }
+
+    if (Y >= bg_h || X0 >= map_pitch) return;  // (no barrier below)
+    uint32_t wa[4] = {0u, 0u, 0u, 0u}, wv[4] = {0u, 0u, 0u, 0u};
+    uint32_t covered = 0u;  // bit i: a later layer covers pixel X0 + i
+    // Phase 2: top down.
+#pragma unroll
+    for (int k = kSceneMapMaxLayers - 1; k >= 0; --k) {
+        if (d[k] < 0) continue;  // wave-uniform
+        const int cy = Y - py[k];
+        if ((unsigned)cy >= (unsigned)ph[k]) continue;
+        const uint8_t* row = planes + (int64_t)d[k] * psize + (int64_t)cy * pitch;
+        const int cx0 = X0 - px[k];
+        const int xlim = min(pw[k], bg_w - px[k]);  // columns of the overlay inside the background
+#pragma unroll
+        for (int i = 0; i < MT_PX; ++i) {
+            const int cx = cx0 + i;
+            if (cx >= 0 && cx < xlim) {
+                const int a = row[cx];
+                const uint32_t bit = (a >= alpha_min ? 1u << k : 0u) << (8 * (i & 3));
+                wa[i >> 2] |= bit;
+                if (!((covered >> i) & 1u)) wv[i >> 2] |= bit;
+                if (a >= cover_min) covered |= 1u << i;
+            }
+        }
+    }
+    const int64_t at = ((int64_t)scene * bg_h + Y) * map_pitch + X0;
+    if (amap) store16<0>(amap + at, 16, true, wa);
+    if (vmap) store16<0>(vmap + at, 16, true, wv);
+}
+
+int amodal_launches(const uint8_t* tmp, const int32_t* coefs, const ipp_pipe_desc* descs, const int32_t* scene_layer,
+                    int n_images, int n_scenes, int per_scene, int bg_w, int bg_h, int max_ov_w, int max_ov_h,
+                    int alpha_min, int cover_min, uint8_t* scratch, int32_t* arows, int32_t* occ, uint8_t* amap,
+                    int32_t* rows, uint8_t* vmap, int64_t map_pitch, hipStream_t s) {
+    const int tyb = paste_max_bands(max_ov_h), strips = (max_ov_h + SVR - 1) / SVR;
+    const int64_t slots = (int64_t)n_scenes * per_scene;
+    const int mtx = (int)((map_pitch + MT_W - 1) / MT_W), mty = (bg_h + MT_H - 1) / MT_H;
+    if ((int64_t)tyb * n_images >= INT32_MAX || (int64_t)strips * n_images >= INT32_MAX || slots >= INT32_MAX ||
+        (int64_t)mtx * mty * n_scenes >= INT32_MAX)
+        return IPP_E_ARG;
+    int32_t* table = reinterpret_cast<int32_t*>(scratch);
+    uint8_t* planes = scratch + scene_table_bytes(slots);
+    if (slots > 0 && hipMemsetAsync(table, 0xFF, 4 * (size_t)slots, s) != hipSuccess) return IPP_E_LAUNCH;
+    if (slots > 0 && hipMemsetAsync(occ, 0, 8 * (size_t)slots * per_scene, s) != hipSuccess) return IPP_E_LAUNCH;
+    if (n_images > 0) {
+        const int ib = (n_images + 255) / 256;
+        hipLaunchKernelGGL(k_amodal_init, dim3(ib), dim3(256), 0, s, arows, rows, table, scene_layer, n_images,
+                           n_scenes, per_scene);
+        hipLaunchKernelGGL(k_scene_alpha, dim3((uint32_t)(tyb * n_images)), dim3(256), 0, s, tmp, coefs, descs,
+                           fast_div((uint32_t)tyb), max_ov_w, max_ov_h, planes);
+        hipLaunchKernelGGL(k_amodal_count, dim3((uint32_t)(strips * n_images)), dim3(256), 0, s, descs, scene_layer,
+                           table, planes, fast_div((uint32_t)strips), n_images, n_scenes, per_scene, max_ov_w,
+                           max_ov_h, alpha_min, cover_min, arows, occ, rows);
+        hipLaunchKernelGGL(k_amodal_finish, dim3(ib), dim3(256), 0, s, arows, rows, n_images);
+    }
+    if ((amap || vmap) && n_scenes > 0)
+        hipLaunchKernelGGL(k_amodal_map, dim3((uint32_t)(mtx * mty * n_scenes)), dim3(256), 0, s, descs, table,
+                           planes, fast_div((uint32_t)(mtx * mty)), fast_div((uint32_t)mtx), n_images, per_scene, bg_w,
+                           bg_h, max_ov_w, max_ov_h, alpha_min, cover_min, amap, vmap, map_pitch);
+    IPP_CHECK_LAUNCH();
+    return IPP_OK;
+}
+
 }  // namespace
+
+extern "C" int ipp_pipe_scene_amodal(const uint8_t* tmp, const int32_t* coefs, const ipp_pipe_desc* descs,
+                                     const int32_t* scene_layer, int32_t n_images, int32_t n_scenes,
+                                     int32_t per_scene, int32_t bg_w, int32_t bg_h, int32_t max_ov_w,
+                                     int32_t max_ov_h, int32_t alpha_min, int32_t cover_min, int32_t tap_format,
+                                     uint8_t* scratch, int32_t* arows, int32_t* occ, uint8_t* amap, int32_t* rows,
+                                     uint8_t* vmap, int64_t map_pitch, void* stream) {
+    if (alpha_min < 1 || alpha_min > 255 || cover_min < 1 || cover_min > 255 || tap_format != IPP_TAPS_MFMA)
+        return IPP_E_ARG;
+    if (!tmp || !coefs || !descs || !scene_layer || !scratch || !arows || !occ || n_images < 0 || n_scenes < 0 ||
+        per_scene < 1 || per_scene > IPP_SCENE_MAP_MAX_LAYERS || max_ov_w <= 0 || max_ov_h <= 0)
+        return IPP_E_ARG;
+    if (bg_w <= 0 || bg_h <= 0 || map_pitch < bg_w || (map_pitch & 15) != 0 || map_pitch > INT32_MAX)
+        return IPP_E_ARG;
+    // the planes are read by dwords, the maps are stored by 16-B vectors
+    if (((reinterpret_cast<uintptr_t>(scratch) | reinterpret_cast<uintptr_t>(amap) |
+          reinterpret_cast<uintptr_t>(vmap)) & 15u) != 0)
+        return IPP_E_ARG;
+    return amodal_launches(tmp, coefs, descs, scene_layer, n_images, n_scenes, per_scene, bg_w, bg_h, max_ov_w,
+                           max_ov_h, alpha_min, cover_min, scratch, arows, occ, amap, rows, vmap, map_pitch,
+                           (hipStream_t)stream);
+}
 
 extern "C" int ipp_pipe_overlay_bbox_trim(const uint8_t* tmp, const int32_t* coefs, const ipp_pipe_desc* descs,
                                           int32_t n_images, int32_t max_ov_w, int32_t max_ov_h, int32_t alpha_min,

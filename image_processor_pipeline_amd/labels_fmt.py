@@ -9,7 +9,8 @@ corner rule), all for the overlays ``_label_lines`` names; ``instance_ids`` and
 ``scene_instance_masks`` turn a visibility map into instance masks.  ``scene_coco_annotations``
 writes the COCO annotations of ``SceneRunner.scene_rles``' run-length encodings, ``rle_counts_string``
 / ``rle_counts_from_string`` are the COCO API's compressed ``counts`` string and ``rle_decode``
-reads a mask back.  ``fused`` re-exports it all.
+reads a mask back; ``scene_amodal_annotations`` writes the amodal ones (full and visible mask, occluders)
+of ``SceneRunner.scene_amodal_rles``.  ``fused`` re-exports it all.
 """
 from __future__ import annotations
 
@@ -372,5 +373,64 @@ def scene_coco_annotations(rles, rows, bg_w: int, bg_h: int, class_ids=0, min_vi
                        "bbox": [x0, y0, x1 - x0, y1 - y0], "area": int(row[5]), "iscrowd": 0,
                        "segmentation": {"size": [int(bg_h), int(bg_w)],
                                         "counts": rle_counts_string(cnts) if compressed else cnts}})
+        next_id += 1
+    return out
+
+
+def scene_amodal_annotations(arles, vrles, arows, rows, occ, bg_w: int, bg_h: int, class_ids=0,
+                             min_visible: float = 0.0, compressed: bool = True, image_ids=None,
+                             first_id: int = 1) -> List[List[dict]]:
+    """Amodal annotations (KINS / COCOA style) of every scene from what
+    ``SceneRunner.scene_amodal_rles`` (arles, arows, occ) and
+    ``SceneRunner.scene_rles`` (vrles, rows) return at the same thresholds:
+    anns[s] lists, in layer order, one dict per overlay that ``scene_labels``
+    gives a line (``_label_lines`` on the VISIBLE rows, ``class_ids`` as there),
+    so the lists align with every other label of the scene.  {"id", "image_id",
+    "category_id", "iscrowd": 0, "bbox": the amodal box [x0, y0, w, h], "area":
+    the amodal (present) area, "segmentation": the amodal mask's RLE {"size":
+    [bg_h, bg_w], "counts"}, "visible_bbox", "visible_area", "visible_mask": the
+    same three of the visible part, "occlude_rate": 1 - visible / area, "layer":
+    k, "occluders": the layers j > k with occ[s][0][k][j] > 0, ascending}.
+    counts, ids and ``image_ids`` as in ``scene_coco_annotations``; every value
+    is a plain int, float, list or str (``json.dumps`` takes the result).  An
+    overlay that would get an annotation but lacks one of its two encodings
+    raises ValueError: an annotation is never dropped."""
+    rows, S, K = _scene_rows(rows, "rows")
+    arows = _scene_rows(arows, "arows")[0]
+    occ = np.asarray(occ)
+    if arows.shape != rows.shape:
+        raise ValueError(f"arows of shape {arows.shape} beside rows of shape {rows.shape}")
+    if occ.shape != (S, 2, K, K):
+        raise ValueError(f"occ of shape {occ.shape}: ({S}, 2, {K}, {K}) expected")
+    for name, rl in (("arles", arles), ("vrles", vrles)):
+        if len(rl) != S or any(len(r) != K for r in rl):
+            raise ValueError(f"{name} does not hold {S} scenes of {K} overlays")
+    img = list(range(S)) if image_ids is None else [int(v) for v in image_ids]
+    if len(img) != S:
+        raise ValueError(f"{len(img)} image ids for {S} scenes")
+
+    def enc(rl, s, k, what):
+        if rl[s][k] is None:
+            raise ValueError(f"scene {s} layer {k}: an annotation without its {what} run-length encoding")
+        cnts = _rle_counts(rl[s][k])
+        return {"size": [int(bg_h), int(bg_w)], "counts": rle_counts_string(cnts) if compressed else cnts}
+
+    def xywh(row):
+        x0, y0, x1, y1 = (int(v) for v in row[:4])
+        return [x0, y0, x1 - x0, y1 - y0]
+
+    out: List[List[dict]] = [[] for _ in range(S)]
+    next_id = int(first_id)
+    for s, k, class_id, row in _label_lines(rows, class_ids, min_visible):
+        arow = arows[s, k]
+        area, vis = int(arow[4]), int(row[5])
+        if area < vis:
+            raise ValueError(f"scene {s} layer {k}: amodal area {area} below its {vis} visible pixels "
+                             f"(arows and rows of different calls?)")
+        out[s].append({"id": next_id, "image_id": img[s], "category_id": int(class_id), "iscrowd": 0,
+                       "bbox": xywh(arow), "area": area, "segmentation": enc(arles, s, k, "amodal"),
+                       "visible_bbox": xywh(row), "visible_area": vis, "visible_mask": enc(vrles, s, k, "visible"),
+                       "occlude_rate": 1.0 - vis / area, "layer": int(k),
+                       "occluders": [j for j in range(k + 1, K) if int(occ[s, 0, k, j]) > 0]})
         next_id += 1
     return out

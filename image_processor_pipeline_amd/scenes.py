@@ -11,7 +11,10 @@ contour from it on the device; ``scene_obbs`` reduces that contour there to its
 minimum-area rectangle (YOLO-OBB), and ``scene_rles`` run-length encodes each
 overlay's exact visible mask there (COCO RLE).  ``run_culled`` decides on the
 device, between the H and the V launches, which overlays the later layers leave
-too little of, and pastes only the others.  labels_fmt.py formats the lines,
+too little of, and pastes only the others.  ``scene_amodal`` reports what the
+rule hides: each overlay's full box and mask behind its occluders and the
+pairwise occlusion counts (``scene_amodal_rles``, ``scene_amodal_polygons``,
+``run_labelled(amodal=True)``).  labels_fmt.py formats the lines,
 masks and annotations; every public name here is also reachable as ``fused.X``.
 """
 from __future__ import annotations
@@ -27,8 +30,8 @@ from .device import _stream, _to_dev, exclusive_offsets
 from .device import check_alpha_min as _check_alpha_min
 from .fused import (ItemParams, PipeConfig, PipePlan, _launch_hpass_bgcopy, _launch_vblend_bands, _Runner,
                     draw_params, plan_pipe)
-from .labels_fmt import (min_visible_q, scene_coco_annotations, scene_contour_capacity, scene_labels,
-                         scene_map_pitch, scene_obb_labels, scene_seg_labels, simplify_tolerance)
+from .labels_fmt import (min_visible_q, scene_amodal_annotations, scene_coco_annotations, scene_contour_capacity,
+                         scene_labels, scene_map_pitch, scene_obb_labels, scene_seg_labels, simplify_tolerance)
 
 
 def draw_scene_params(n_scenes_global: int, stop_scene: int, per_scene: int, src_hw: Tuple[int, int],
@@ -575,10 +578,89 @@ class SceneRunner(_Runner):
         buf, rows = self._launch_map("scene_rles", alpha_min, cover_min, True, None)
         return self._rles(buf, rows), self._rows_by_scene(rows)
 
+    def _launch_amodal(self, caller: str, alpha_min: int, cover_min: int, amap: bool, visible: bool):
+        """One ipp_pipe_scene_amodal call (one alpha pass): the device amodal
+        rows (descriptor order), the device occ (S, 2, K, K), with ``amap`` the
+        (S, bg_h, pitch) presence-map buffer, and with ``visible`` the rows and
+        the map buffer of ``_launch_map`` (else None each)."""
+        self._scene_scratch(caller)
+        p, S, K = self.plan.pipe, self.plan.n_scenes, self.plan.per_scene
+        pitch = scene_map_pitch(p.bg_w)
+
+        def new_map():
+            return torch.empty((S, p.bg_h, pitch), dtype=torch.uint8, device=self.device)
+
+        arows, occ = self._rows(), torch.empty((S, 2, K, K), dtype=torch.int32, device=self.device)
+        abuf = new_map() if amap else None
+        rows, vbuf = (self._rows(), new_map()) if visible else (None, None)
+        N.check(self.lib.ipp_pipe_scene_amodal(self.tmp.data_ptr(), self.coefs.data_ptr(), self._dptr(0),
+                                               self._scene_layer.data_ptr(), S * K, S, K, p.bg_w, p.bg_h,
+                                               p.max_ov_w, p.max_ov_h, alpha_min, cover_min, p.tap_format,
+                                               self._scratch.data_ptr(), arows.data_ptr(), occ.data_ptr(),
+                                               abuf.data_ptr() if amap else None,
+                                               rows.data_ptr() if visible else None,
+                                               vbuf.data_ptr() if visible else None, pitch,
+                                               _stream(self.device)), "ipp_pipe_scene_amodal")
+        return arows, occ, abuf, rows, vbuf
+
+    def scene_amodal(self, alpha_min: int = 1, cover_min: int = 128, masks: bool = False):
+        """The amodal labels of the batch (ipp_pipe_scene_amodal; include/ipp.h
+        states the rule): what every overlay is behind its occluders, and who
+        occludes whom.  Returns (arows, occ): arows is (S, K, 6) int32 (x0, y0,
+        x1, y1, area, visible) in scene, layer order — the half-open tight box
+        of the overlay's PRESENT pixels (alpha >= alpha_min), covered or not,
+        or (-1, -1, -1, -1); area and visible are ``scene_boxes``' — and occ is
+        (S, 2, K, K) int32: occ[s, 0, k, j] (j > k) the present pixels of layer
+        k that layer j covers (alpha >= cover_min), whoever else does;
+        occ[s, 1, k, j] those whose TOPMOST covering layer is j; the diagonals
+        are area and visible, so each row of occ[s, 1] sums to the area.  With
+        ``masks`` it returns (arows, occ, amap): the presence maps, a device
+        uint8 tensor (S, bg_h, bg_w) like ``scene_masks``' (bit k of a byte =
+        layer k present there; a view of a pitched buffer).  It runs after
+        ``run`` on the current stream and synchronises for the copy back.
+        Scenes of more than 8 layers are refused (ValueError)."""
+        alpha_min, cover_min = _check_level("alpha_min", alpha_min), _check_level("cover_min", cover_min)
+        if not isinstance(masks, (bool, np.bool_)):
+            raise ValueError(f"SceneRunner.scene_amodal: masks {masks!r}: a bool")
+        self._check_map("scene_amodal", None)
+        arows, occ, abuf, _, _ = self._launch_amodal("scene_amodal", alpha_min, cover_min, bool(masks), False)
+        res = (self._rows_by_scene(arows), occ.cpu().numpy())
+        return res + (abuf[:, :, :self.plan.bg_w],) if masks else res
+
+    def scene_amodal_rles(self, alpha_min: int = 1, cover_min: int = 128):
+        """``scene_rles`` of the presence maps: (arles, arows, occ), arles[s][k]
+        the uint32 COCO counts of overlay k's full (amodal) mask — its ones-runs
+        sum to the row's `area` — or None for an overlay without a present
+        pixel; arows and occ are ``scene_amodal``'s, from the same call.
+        Encoded on the device (ipp_pipe_scene_amodal, then ipp_scene_rle and
+        ipp_scene_rle_pack on the presence map and the amodal rows); it
+        synchronises.  Scenes of more than 8 layers are refused."""
+        alpha_min, cover_min = _check_level("alpha_min", alpha_min), _check_level("cover_min", cover_min)
+        self._check_map("scene_amodal_rles", None)
+        arows, occ, abuf, _, _ = self._launch_amodal("scene_amodal_rles", alpha_min, cover_min, True, False)
+        return self._rles(abuf, arows), self._rows_by_scene(arows), occ.cpu().numpy()
+
+    def scene_amodal_polygons(self, alpha_min: int = 1, cover_min: int = 128, max_edges: Optional[int] = None,
+                              simplify: Optional[float] = None):
+        """``scene_polygons`` of the presence maps: (polys, info, arows), the
+        outer contour of every overlay's PRESENT pixels (its largest 8-connected
+        part, as there), covered or not, traced on the device from the presence
+        map and the amodal rows; ``max_edges`` and ``simplify`` as in
+        ``scene_polygons``; arows is ``scene_amodal``'s.  It synchronises.
+        Scenes of more than 8 layers are refused."""
+        alpha_min, cover_min = _check_level("alpha_min", alpha_min), _check_level("cover_min", cover_min)
+        self._check_map("scene_amodal_polygons", None)
+        max_edges = self._check_max_edges("scene_amodal_polygons", max_edges)
+        eps_q = self._check_simplify("scene_amodal_polygons", simplify)
+        arows, _, abuf, _, _ = self._launch_amodal("scene_amodal_polygons", alpha_min, cover_min, True, False)
+        polys, info = self._polygons(abuf, arows, max_edges, eps_q)
+        return polys, info, self._rows_by_scene(arows)
+
     def run_labelled(self, src: torch.Tensor, bgs: torch.Tensor, out: torch.Tensor, class_ids=0,
                      alpha_min: int = 1, cover_min: int = 128, min_visible: float = 0.0, masks: bool = False,
                      polygons: bool = False, max_edges: Optional[int] = None, simplify: Optional[float] = None,
-                     obb: bool = False, rle: bool = False, cull: bool = False, min_pixels: int = 1):
+                     obb: bool = False, rle: bool = False, cull: bool = False, min_pixels: int = 1,
+                     amodal: bool = False):
         """``run`` plus the YOLO lines of every scene (``scene_labels``):
         labels[s] lists scene s's lines in layer order, one per overlay with
         visible > 0 and visible / area >= min_visible.  Returns (out, labels);
@@ -604,15 +686,25 @@ class SceneRunner(_Runner):
         kept one always has its line), and the tuple gains ``kept``, the
         (S, K) bool array of ``run_culled``, as its last element.  The
         scratch stays cleared afterwards, as ``run_culled`` describes.
-        ``min_visible`` must then lie in 0..1."""
+        ``min_visible`` must then lie in 0..1.  With ``amodal`` the tuple
+        gains, after the COCO annotations if any and before ``kept``, the
+        amodal annotations of ``scene_amodal_annotations`` (full and visible
+        mask, occlusion rate and occluders of every overlay that has a line;
+        compressed counts, image id = scene index).  The labels of the whole
+        call then come from one ipp_pipe_scene_amodal call — one alpha pass —
+        that takes the map launch's place; without ``amodal`` the launches are
+        unchanged.  A culled overlay is absent from the amodal rows, the
+        occlusion counts and the presence map as well."""
         alpha_min, cover_min = _check_level("alpha_min", alpha_min), _check_level("cover_min", cover_min)
         if not isinstance(cull, (bool, np.bool_)):
             raise ValueError(f"SceneRunner.run_labelled: cull {cull!r}: a bool")
+        if not isinstance(amodal, (bool, np.bool_)):
+            raise ValueError(f"SceneRunner.run_labelled: amodal {amodal!r}: a bool")
         if cull:
             min_q, min_pixels = self._check_cull("run_labelled", min_visible, min_pixels)
         if simplify is not None and not polygons:
             raise ValueError("SceneRunner.run_labelled: simplify needs polygons=True")
-        if masks or polygons or obb or rle:
+        if masks or polygons or obb or rle or amodal:
             self._check_map("run_labelled", None)
         eps_q = None
         if polygons or obb:
@@ -629,7 +721,9 @@ class SceneRunner(_Runner):
             self._launch_v(bgs, out)
         else:
             self.run(src, bgs, out)
-        if masks or polygons or obb or rle:
+        if amodal:
+            arows, occ, abuf, rows, buf = self._launch_amodal("run_labelled", alpha_min, cover_min, True, True)
+        elif masks or polygons or obb or rle:
             buf, rows = self._launch_map("run_labelled", alpha_min, cover_min, True, None)
         else:
             rows = self._launch_boxes(alpha_min, cover_min)
@@ -644,8 +738,12 @@ class SceneRunner(_Runner):
                 res += (scene_seg_labels(polys, info, boxes, bg_w, bg_h, class_ids, min_visible),)
             if obb:
                 res += (scene_obb_labels(obbs, info, boxes, bg_w, bg_h, class_ids, min_visible),)
+        vrles = self._rles(buf, rows) if rle or amodal else None
         if rle:
-            res += (scene_coco_annotations(self._rles(buf, rows), boxes, bg_w, bg_h, class_ids, min_visible),)
+            res += (scene_coco_annotations(vrles, boxes, bg_w, bg_h, class_ids, min_visible),)
+        if amodal:
+            res += (scene_amodal_annotations(self._rles(abuf, arows), vrles, self._rows_by_scene(arows), boxes,
+                                             occ.cpu().numpy(), bg_w, bg_h, class_ids, min_visible),)
         if cull:
             res += (self._cull_by_scene(rec)[0],)
         return res

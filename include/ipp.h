@@ -443,6 +443,63 @@ int ipp_pipe_scene_cull(uint8_t* tmp, const int32_t* coefs, const ipp_pipe_desc*
                         int32_t max_ov_w, int32_t max_ov_h, int32_t alpha_min, int32_t cover_min,
                         int32_t min_q, int32_t min_pixels, int32_t tap_format,
                         uint8_t* scratch, int32_t* cull, void* stream);
+/* Amodal labels of scenes: the full extent of every overlay behind its
+ * occluders, and who occludes whom.  A_k, PRESENT, VISIBLE, "has a plane"
+ * (ov_w <= max_ov_w and ov_h <= max_ov_h), scene_layer and the scratch are
+ * those of ipp_pipe_scene_boxes; the map layout is ipp_pipe_scene_map's.  Same
+ * place in the stream as the boxes: after the H launches, before tmp is
+ * refilled.  One call makes one alpha pass, whatever outputs are asked for.
+ *
+ * PRESENCE MAP (amap, may be NULL): n_scenes slots of bg_h rows of map_pitch
+ * bytes.  Bit k of byte (Y, X) of slot s is 1 iff layer k of scene s is mapped
+ * by scene_layer and has a plane, (X, Y) lies in its rectangle clipped to the
+ * bg_w x bg_h background, and A_k >= alpha_min there.  Later layers play no
+ * part.  Columns [bg_w, map_pitch) are 0, a slot without descriptors is all 0,
+ * and EVERY byte of every slot is written (n_images == 0 included).
+ *
+ * AMODAL ROWS (arows, device int32[n_images][6], descriptor order): (x0, y0,
+ * x1, y1, area, visible): the half-open tight box of the descriptor's PRESENT
+ * pixels in composite coordinates, (-1,-1,-1,-1) when it has none; area and
+ * visible are exactly those of ipp_pipe_scene_boxes.  A descriptor without a
+ * plane gets (-1,-1,-1,-1, 0, 0).  area is the number of the descriptor's bits
+ * in amap and the box is their bounding box.
+ *
+ * OCCLUSION MATRIX (occ, device int32[n_scenes][2][per_scene][per_scene]),
+ * indexed by slot (scene, layer), every word written by the call:
+ *   occ[s][0][k][j], COVERS, k < j: the number of composite pixels where layer
+ *     k is PRESENT and layer j, which has a plane and whose rectangle holds the
+ *     pixel, has A_j >= cover_min — whether or not other layers cover the
+ *     pixel too.  occ[s][0][k][k] = area_k.  0 for j < k.
+ *   occ[s][1][k][j], HIDES, k < j: the number of PRESENT pixels of layer k
+ *     whose TOPMOST layer j' > k with A_j' >= cover_min (a plane, the rectangle
+ *     holds the pixel) is j.  occ[s][1][k][k] = visible_k.  0 for j < k.
+ * Each row of plane 1 partitions the present pixels: sum_{j >= k}
+ * occ[s][1][k][j] = area_k; and occ[s][1][k][j] <= occ[s][0][k][j].  An empty
+ * slot, a descriptor without a plane and a descriptor that scene_layer does not
+ * map into n_scenes x per_scene contribute 0 everywhere; the last is labelled
+ * in arows as if alone in its scene and hides nothing, as in the boxes.
+ *
+ * rows (may be NULL) and vmap (may be NULL) receive byte for byte what
+ * ipp_pipe_scene_map writes to its `rows` and `map` with the same arguments;
+ * amap and vmap share map_pitch.  With a NULL output the others are unchanged.
+ * Every result is a sum, a minimum or a maximum of integers: none depends on
+ * the order of the atomics.
+ * 1 <= per_scene <= IPP_SCENE_MAP_MAX_LAYERS.  scratch: as for
+ * ipp_pipe_scene_boxes (ipp_pipe_scene_scratch_bytes, the same table and
+ * planes), 16-B aligned; amap and vmap 16-B aligned; map_pitch >= bg_w, a
+ * multiple of 16, below 2^31 (checked even when both maps are NULL).
+ * IPP_E_ARG, before any launch: a NULL tmp, coefs, descs, scene_layer, scratch,
+ * arows or occ; a threshold outside 1..255; per_scene outside its range; a
+ * pitch or an alignment as above; a tap_format other than IPP_TAPS_MFMA; a
+ * grid of 2^31 blocks or more.  n_images == 0 still writes all of occ (zeros)
+ * and all map slots. */
+int ipp_pipe_scene_amodal(const uint8_t* tmp, const int32_t* coefs, const ipp_pipe_desc* descs,
+                          const int32_t* scene_layer, int32_t n_images, int32_t n_scenes, int32_t per_scene,
+                          int32_t bg_w, int32_t bg_h, int32_t max_ov_w, int32_t max_ov_h,
+                          int32_t alpha_min, int32_t cover_min, int32_t tap_format, uint8_t* scratch,
+                          int32_t* arows, int32_t* occ,
+                          uint8_t* amap /* may be NULL */, int32_t* rows /* may be NULL */,
+                          uint8_t* vmap /* may be NULL */, int64_t map_pitch, void* stream);
 
 /* Polygons of scenes: the outer contour of each overlay's visible pixels,
  * traced on the device from the visibility maps.  map, map_pitch, rows (device
