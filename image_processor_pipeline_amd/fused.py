@@ -40,11 +40,11 @@ from . import _native as N
 from . import geometry as G
 from .device import SYM_FLIP, _stream, _to_dev
 from .device import check_alpha_min as _check_alpha_min
-from .labels_fmt import (instance_ids, min_visible_q, obb_corners, obb_label, rle_counts_from_string,  # noqa: F401
-                         rle_counts_string, rle_decode, scene_amodal_annotations, scene_coco_annotations,
-                         scene_contour_capacity, scene_instance_masks, scene_labels, scene_map_pitch,
-                         scene_obb_labels, scene_seg_labels, seg_label, simplify_tolerance, xyxy2xywhn, yolo_label,
-                         yolo_labels)
+from .labels_fmt import (feed_lut, instance_ids, min_visible_q, obb_corners, obb_label,  # noqa: F401
+                         rle_counts_from_string, rle_counts_string, rle_decode, scene_amodal_annotations,
+                         scene_coco_annotations, scene_contour_capacity, scene_instance_masks, scene_labels,
+                         scene_map_pitch, scene_obb_labels, scene_seg_labels, seg_label, simplify_tolerance,
+                         xyxy2xywhn, yolo_label, yolo_labels)
 
 ALL_SYMS = ("o", "h", "v", "hv")
 H_RING_COLUMNS = 512   # ipp_pipe.hip RING
@@ -624,7 +624,7 @@ class PipeStream:
 
 
 # fused.X of scenes.py, which imports this module: looked up on first use, so either may be imported first
-_SCENE_NAMES = ("draw_scene_params", "ScenePlan", "plan_scenes", "SIMPLIFY_MAX_SIDE", "SceneRunner")
+_SCENE_NAMES = ("draw_scene_params", "ScenePlan", "plan_scenes", "SIMPLIFY_MAX_SIDE", "SceneRunner", "SceneFeed")
 
 
 def __getattr__(name: str):

@@ -10,7 +10,8 @@ corner rule), all for the overlays ``_label_lines`` names; ``instance_ids`` and
 writes the COCO annotations of ``SceneRunner.scene_rles``' run-length encodings, ``rle_counts_string``
 / ``rle_counts_from_string`` are the COCO API's compressed ``counts`` string and ``rle_decode``
 reads a mask back; ``scene_amodal_annotations`` writes the amodal ones (full and visible mask, occluders)
-of ``SceneRunner.scene_amodal_rles``.  ``fused`` re-exports it all.
+of ``SceneRunner.scene_amodal_rles``.  ``feed_lut`` tabulates the normalisation of ``SceneRunner.feed``'s
+images.  ``fused`` re-exports it all.
 """
 from __future__ import annotations
 
@@ -107,6 +108,39 @@ def min_visible_q(min_visible) -> int:
     if not 0.0 <= v <= 1.0:     # (NaN fails both comparisons)
         raise ValueError(f"min_visible {min_visible!r}: a real number in 0..1 expected")
     return int(math.ceil(v * 65536.0))
+
+
+def feed_lut(mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0), dtype=None, scale: float = 1.0 / 255.0):
+    """The (3, 256) table of ``SceneRunner.feed`` (ipp_scene_feed_images) as a
+    torch CPU tensor of ``dtype`` (float16, the default, bfloat16 or float32):
+    entry [c][v] = ((v·scale) − mean[c]) / std[c], computed in float64 and
+    rounded once to ``dtype`` (``torch.tensor(..., dtype=float64).to(dtype)``).
+    Row c is output plane c's, whichever input channel feeds it (``bgr``).
+    ValueError: mean or std not three finite reals, a std <= 0, a non-finite
+    scale, any other dtype."""
+    import torch
+    dtype = torch.float16 if dtype is None else dtype
+    if dtype not in (torch.float16, torch.bfloat16, torch.float32):
+        raise ValueError(f"feed_lut: dtype {dtype!r}: torch.float16, torch.bfloat16 or torch.float32 expected")
+
+    def three(name, v):
+        try:
+            out = [float(x) for x in v]
+        except (TypeError, ValueError):
+            raise ValueError(f"feed_lut: {name} {v!r}: three real numbers expected") from None
+        if len(out) != 3 or not all(math.isfinite(x) for x in out):
+            raise ValueError(f"feed_lut: {name} {v!r}: three finite real numbers expected")
+        return out
+
+    mean, std = three("mean", mean), three("std", std)
+    if any(x <= 0.0 for x in std):
+        raise ValueError(f"feed_lut: std {std!r}: every entry must be > 0")
+    if isinstance(scale, (bool, np.bool_)) or not isinstance(scale, (int, float, np.integer, np.floating)) or \
+            not math.isfinite(float(scale)):
+        raise ValueError(f"feed_lut: scale {scale!r}: a finite real number expected")
+    v = np.arange(256, dtype=np.float64) * float(scale)
+    table = np.stack([(v - mean[c]) / std[c] for c in range(3)])
+    return torch.tensor(table, dtype=torch.float64).to(dtype)
 
 
 def scene_map_pitch(bg_w: int) -> int:

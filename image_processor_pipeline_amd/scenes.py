@@ -14,13 +14,15 @@ device, between the H and the V launches, which overlays the later layers leave
 too little of, and pastes only the others.  ``scene_amodal`` reports what the
 rule hides: each overlay's full box and mask behind its occluders and the
 pairwise occlusion counts (``scene_amodal_rles``, ``scene_amodal_polygons``,
-``run_labelled(amodal=True)``).  labels_fmt.py formats the lines,
+``run_labelled(amodal=True)``).  ``feed`` / ``run_feed`` leave a training
+batch on the device instead — normalised planar images, a targets tensor, an
+instance-index map — with no copy back.  labels_fmt.py formats the lines,
 masks and annotations; every public name here is also reachable as ``fused.X``.
 """
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import List, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -30,8 +32,9 @@ from .device import _stream, _to_dev, exclusive_offsets
 from .device import check_alpha_min as _check_alpha_min
 from .fused import (ItemParams, PipeConfig, PipePlan, _launch_hpass_bgcopy, _launch_vblend_bands, _Runner,
                     draw_params, plan_pipe)
-from .labels_fmt import (min_visible_q, scene_amodal_annotations, scene_coco_annotations, scene_contour_capacity,
-                         scene_labels, scene_map_pitch, scene_obb_labels, scene_seg_labels, simplify_tolerance)
+from .labels_fmt import (feed_lut, min_visible_q, scene_amodal_annotations, scene_coco_annotations,
+                         scene_contour_capacity, scene_labels, scene_map_pitch, scene_obb_labels, scene_seg_labels,
+                         simplify_tolerance)
 
 
 def draw_scene_params(n_scenes_global: int, stop_scene: int, per_scene: int, src_hw: Tuple[int, int],
@@ -138,6 +141,17 @@ def _check_level(name: str, v) -> int:
         raise ValueError(f"{name} {v!r}: an integer in 1..255") from None
 
 
+class SceneFeed(NamedTuple):
+    """What ``SceneRunner.feed`` leaves on the device (include/ipp.h states the rules)."""
+    images: torch.Tensor                 # (S, 3, bg_h, bg_w) of the table's dtype
+    targets: torch.Tensor                # (S·K, 6) float32 (scene, class, cx, cy, w, h); unused rows all -1
+    count: torch.Tensor                  # (1,) int32: the rows in use
+    slot: torch.Tensor                   # (S, K) int32: each overlay's row of targets, or -1
+    index_map: Optional[torch.Tensor]    # (S, bg_h, bg_w) uint8, or None
+
+
+_FEED_DTYPES = (torch.float16, torch.bfloat16, torch.float32)
+
 SIMPLIFY_MAX_SIDE = 16384   # largest background side ipp_polygons_simplify takes (ipp.h: the overflow bounds)
 
 
@@ -150,6 +164,7 @@ class SceneRunner(_Runner):
     _simplify_scratch = None         # buffer of scene_polygons(simplify=...), grown on demand
     _obb_scratch = None              # buffer of scene_obbs, grown on demand
     _rle_scratch = None              # buffer of scene_rles
+    _feed_cache = None               # the small device arrays of feed, by argument
 
     def _check(self, caller: str, src: torch.Tensor, bgs: torch.Tensor, out: torch.Tensor) -> None:
         self._check_tensors(caller, src, bgs, out)
@@ -747,3 +762,179 @@ class SceneRunner(_Runner):
         if cull:
             res += (self._cull_by_scene(rec)[0],)
         return res
+
+    def _feed_lut(self, lut, mean, std, dtype) -> torch.Tensor:
+        """The device table of ``feed``: uploaded once per distinct argument."""
+        if lut is None:
+            try:
+                key = ("lut", tuple(float(v) for v in mean), tuple(float(v) for v in std), dtype)
+                hash(key)
+            except (TypeError, ValueError):
+                key = None
+            if key is None or key not in self._feed_cache:
+                table = feed_lut(mean, std, dtype).to(self.device)      # (raises on what key could not hold)
+                if key is None:
+                    return table
+                self._feed_cache[key] = table
+            return self._feed_cache[key]
+        if not isinstance(lut, torch.Tensor) or lut.dtype not in _FEED_DTYPES or tuple(lut.shape) != (3, 256):
+            raise ValueError("SceneRunner.feed: lut must be a (3, 256) tensor of torch.float16, torch.bfloat16 or "
+                             "torch.float32 (labels_fmt.feed_lut)")
+        if lut.device.type == self.device.type and self.device.index in (None, lut.device.index):
+            return lut.contiguous()
+        if lut.device.type != "cpu":
+            raise ValueError(f"SceneRunner.feed: lut on {lut.device}: a CPU tensor or one on {self.device} expected")
+        words = lut.contiguous().view(torch.int16 if lut.element_size() == 2 else torch.int32)
+        key = ("table", lut.dtype, words.numpy().tobytes())
+        if key not in self._feed_cache:
+            self._feed_cache[key] = lut.to(self.device)
+        return self._feed_cache[key]
+
+    def _feed_classes(self, class_ids) -> Optional[torch.Tensor]:
+        """Device class ids by descriptor (None = class 0 everywhere): uploaded once per distinct argument."""
+        n = len(self.plan.descs)
+        if isinstance(class_ids, (int, np.integer)) and not isinstance(class_ids, (bool, np.bool_)):
+            ids = None if int(class_ids) == 0 else [int(class_ids)] * n
+        else:
+            ids = [int(c) for c in class_ids]
+            if len(ids) != n:
+                raise ValueError(f"SceneRunner.feed: {len(ids)} class ids for {n} overlays")
+        if ids is None:
+            return None
+        if not all(0 <= c <= 1 << 24 for c in ids):
+            raise ValueError("SceneRunner.feed: class ids must lie in 0..2^24 (float32 holds them exactly)")
+        key = ("classes", tuple(ids))
+        if key not in self._feed_cache:
+            by_item = np.array(ids, np.int32)              # scene-major, as scene_labels takes them
+            self._feed_cache[key] = _to_dev(by_item[self.plan.desc_item], self.device).view(torch.int32)
+        return self._feed_cache[key]
+
+    def feed(self, out: torch.Tensor, lut: Optional[torch.Tensor] = None, mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0),
+             dtype: torch.dtype = torch.float16, bgr: bool = False, class_ids=0, alpha_min: int = 1,
+             cover_min: int = 128, min_visible: float = 0.0, index_map: bool = False,
+             images: Optional[torch.Tensor] = None) -> SceneFeed:
+        """The training batch of the composites `out` of the last ``run``, left
+        on the device (include/ipp.h: ipp_scene_feed_images, _targets,
+        _index_map): a ``SceneFeed`` of
+          images   (S, 3, bg_h, bg_w): images[s, c, y, x] = lut[c][out[s, y, x,
+                   c]] (with ``bgr`` channel 2 - c).  ``lut`` is a (3, 256)
+                   table of float16, bfloat16 or float32 (``feed_lut``), on the
+                   CPU or on the device, and its dtype is the images'; None =
+                   ``feed_lut(mean, std, dtype)``.  The table's words are
+                   copied, so the images equal the table's entries bit for bit.
+          targets  (S·K, 6) float32 rows (scene, class, cx, cy, w, h) of the
+                   overlays ``scene_labels`` gives a line at the same
+                   thresholds — visible > 0 and 65536·visible >=
+                   min_visible_q(min_visible)·area, the cull's test — in scene,
+                   layer order; cx = float32(x0 + x1) / float32(2·bg_w) and so
+                   on, one rounded division each; the unused rows are all -1
+                   (``targets[:, 0] >= 0`` masks them).  ``class_ids`` as in
+                   ``scene_labels`` (0..2^24).
+          count    (1,) int32, the rows in use.
+          slot     (S, K) int32: each overlay's row, or -1.
+          index_map  with ``index_map`` (S, bg_h, bg_w) uint8, a view of a
+                   pitched buffer like ``scene_masks``': 0 where no kept
+                   overlay is visible, else 1 + the row, within the scene's
+                   run of targets, of the topmost kept overlay visible there;
+                   else None.
+        The rows come from the box launch, or with ``index_map`` from the map
+        launch (at most 8 layers), so it runs after ``run`` on the current
+        stream.  Everything stays on the device: nothing is copied back and
+        nothing synchronises; the table and the class ids are uploaded once per
+        distinct argument and kept on the runner.  ``images`` supplies the
+        output (contiguous, on the device, of the table's dtype and the shape
+        above; every element is written)."""
+        if not self._hpass_done:
+            raise ValueError("SceneRunner.feed: no run has filled the composites and the scratch on this runner")
+        return self._feed_launch(*self._feed_args("feed", out, lut, mean, std, dtype, bgr, class_ids, alpha_min,
+                                                  cover_min, min_visible, index_map, images))
+
+    def _feed_args(self, caller: str, out, lut, mean, std, dtype, bgr, class_ids, alpha_min, cover_min, min_visible,
+                   index_map, images):
+        """Everything ``feed`` refuses with ValueError, before any launch, and the uploads: the arguments of
+        ``_feed_launch``."""
+        who = f"SceneRunner.{caller}"
+        alpha_min, cover_min = _check_level("alpha_min", alpha_min), _check_level("cover_min", cover_min)
+        min_q = min_visible_q(min_visible)
+        for name, v in (("bgr", bgr), ("index_map", index_map)):
+            if not isinstance(v, (bool, np.bool_)):
+                raise ValueError(f"{who}: {name} {v!r}: a bool")
+        p, S = self.plan.pipe, self.plan.n_scenes
+
+        def on_device(t):
+            return isinstance(t, torch.Tensor) and t.device.type == self.device.type and \
+                self.device.index in (None, t.device.index)
+
+        if not on_device(out) or out.dtype != torch.uint8 or tuple(out.shape) != (S, p.bg_h, p.bg_w, 3) or \
+                not out.is_contiguous():
+            raise ValueError(f"{who}: out must be the contiguous uint8 composites ({S}, {p.bg_h}, {p.bg_w}, 3) on "
+                             f"{self.device}")
+        if max(p.bg_w, p.bg_h) > N.IPP_FEED_MAX_SIDE:
+            raise ValueError(f"{who}: a {p.bg_w}x{p.bg_h} background: bg_w and bg_h must not exceed "
+                             f"{N.IPP_FEED_MAX_SIDE} (ipp_scene_feed_targets' exact divisions)")
+        if index_map:
+            self._check_map(caller, None)
+        if self._feed_cache is None:
+            self._feed_cache = {}
+        table = self._feed_lut(lut, mean, std, dtype)
+        classes = self._feed_classes(class_ids)
+        shape = (S, 3, p.bg_h, p.bg_w)
+        if images is None:
+            images = torch.empty(shape, dtype=table.dtype, device=self.device)
+        elif not on_device(images) or images.dtype != table.dtype or tuple(images.shape) != shape or \
+                not images.is_contiguous():
+            raise ValueError(f"{who}: images must be a contiguous {table.dtype} tensor {shape} on {self.device}")
+        return caller, out, table, bool(bgr), classes, alpha_min, cover_min, min_q, bool(index_map), images
+
+    def _feed_launch(self, caller: str, out, table, bgr: bool, classes, alpha_min: int, cover_min: int, min_q: int,
+                     index_map: bool, images) -> SceneFeed:
+        """The launches of ``feed``: the box or the map launch, then the two or three feed entries."""
+        p, S, K = self.plan.pipe, self.plan.n_scenes, self.plan.per_scene
+        st, lib = _stream(self.device), self.lib
+        buf = None
+        if index_map:
+            buf, rows = self._launch_map(caller, alpha_min, cover_min, True, None)
+        else:
+            rows = self._launch_boxes(alpha_min, cover_min)
+        N.check(lib.ipp_scene_feed_images(out.data_ptr(), images.data_ptr(), table.data_ptr(), S, p.bg_w, p.bg_h,
+                                          table.element_size(), int(bgr), st), "ipp_scene_feed_images")
+        targets = torch.empty((S * K, 6), dtype=torch.float32, device=self.device)
+        count = torch.empty(1, dtype=torch.int32, device=self.device)
+        slot = torch.empty((S, K), dtype=torch.int32, device=self.device)
+        N.check(lib.ipp_scene_feed_targets(rows.data_ptr(), self._scene_layer.data_ptr(),
+                                           classes.data_ptr() if classes is not None else None, S * K, S, K, p.bg_w,
+                                           p.bg_h, min_q, targets.data_ptr(), count.data_ptr(), slot.data_ptr(), st),
+                "ipp_scene_feed_targets")
+        idx = None
+        if index_map:
+            ibuf = torch.empty_like(buf)
+            N.check(lib.ipp_scene_feed_index_map(buf.data_ptr(), buf.shape[2], p.bg_w, p.bg_h, slot.data_ptr(), S, K,
+                                                 ibuf.data_ptr(), st), "ipp_scene_feed_index_map")
+            idx = ibuf[:, :, :p.bg_w]
+        return SceneFeed(images, targets, count, slot, idx)
+
+    def run_feed(self, src: torch.Tensor, bgs: torch.Tensor, out: torch.Tensor, lut: Optional[torch.Tensor] = None,
+                 mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0), dtype: torch.dtype = torch.float16, bgr: bool = False,
+                 class_ids=0, alpha_min: int = 1, cover_min: int = 128, min_visible: float = 0.0,
+                 index_map: bool = False, images: Optional[torch.Tensor] = None, cull: bool = False,
+                 min_pixels: int = 1) -> SceneFeed:
+        """``run`` followed by ``feed`` (same arguments), all on the current
+        stream and without a copy back.  With ``cull`` the run is
+        ``run_culled``'s — the H launches, ipp_pipe_scene_cull with
+        ``min_visible`` and ``min_pixels``, the V launches — and its records
+        stay on the device; the feed's keep rule is the cull's fraction test,
+        so every painted overlay then has a row of targets and every row a
+        painted overlay (the scratch stays cleared afterwards, as
+        ``run_culled`` describes)."""
+        if not isinstance(cull, (bool, np.bool_)):
+            raise ValueError(f"SceneRunner.run_feed: cull {cull!r}: a bool")
+        if cull:
+            min_q, min_pixels = self._check_cull("run_feed", min_visible, min_pixels)
+        self._check("run_feed", src, bgs, out)
+        args = self._feed_args("run_feed", out, lut, mean, std, dtype, bgr, class_ids, alpha_min, cover_min,
+                               min_visible, index_map, images)
+        self._launch_h(src, bgs, out)
+        if cull:
+            self._launch_cull("run_feed", args[5], args[6], min_q, min_pixels)
+        self._launch_v(bgs, out)
+        return self._feed_launch(*args)

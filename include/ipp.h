@@ -767,6 +767,85 @@ int ipp_scene_rle_pack(const uint8_t* map, int64_t map_pitch, int32_t bg_w, int3
                        const int32_t* rows, const int32_t* scene_layer, int32_t n_images,
                        int32_t n_scenes, int32_t per_scene, const uint8_t* scratch, const int32_t* hdr,
                        const int64_t* offsets, uint32_t* counts, void* stream);
+/* Training batches left on the device: what a detector's loss takes, made from
+ * the composites and the device rows of a box, map or amodal launch without a
+ * copy back.  The three entries read no tmp: they may run any time after the
+ * launches that wrote their inputs, on the same stream.
+ *
+ * ipp_scene_feed_images: in = the composites, n_scenes x bg_h x bg_w x 3
+ * contiguous uint8 (what the V launches write); out = n_scenes x 3 x bg_h x
+ * bg_w contiguous elements of elem_size bytes (2 or 4):
+ *   out[s][c][y][x] = lut[c][ in[s][y][x][ch(c)] ],  ch(c) = c, or 2 - c with bgr = 1.
+ * lut: device, 3 x 256 elements of elem_size bytes, copied as opaque words:
+ * whatever float format and per-channel curve the caller tabulated comes out
+ * bit for bit, and no float arithmetic runs on the device.  The table is kept
+ * in LDS; a scene is a flat stream of bg_w·bg_h pixels on both sides, a lane
+ * takes 16 pixels (three 16-B loads, 16-B stores per plane).  Nothing is
+ * assumed of the alignment of `in` (any byte address) or of a scene's slot: up
+ * to 15 pixels before the first 16-B boundary of a scene's bytes and fewer
+ * than 16 after its last full run go one by one, and a plane that does not
+ * start 16-B aligned behind them takes unaligned 16-B stores.  No byte
+ * outside the n_scenes·bg_h·bg_w·3 of `in` is read, none outside `out` written.
+ * IPP_E_ARG, before any launch: a NULL pointer; n_scenes, bg_w or bg_h < 1;
+ * elem_size other than 2 or 4; bgr other than 0 or 1; out or lut not aligned
+ * to elem_size; bg_w·bg_h >= 2^28; n_scenes·⌈bg_w·bg_h / 16384⌉ >= 2^31 - 1.
+ *
+ * ipp_scene_feed_targets: rows = device int32[n_images][6] (x0, y0, x1, y1,
+ * area, visible) in descriptor order, exactly what ipp_pipe_scene_boxes,
+ * ipp_pipe_scene_map or ipp_pipe_scene_amodal wrote; scene_layer as there;
+ * class_ids = device int32[n_images] by descriptor, or NULL for class 0.  With
+ * T = n_scenes·per_scene and overlay q = scene·per_scene + layer:
+ *   DESCRIPTOR of q: the highest d < n_images with scene_layer[d] = (scene,
+ *     layer) (plan_scenes maps every q exactly once); none: q is absent.
+ *   KEPT: q has a descriptor, visible > 0 and 65536·visible >= min_q·area in
+ *     int64 (ipp_pipe_scene_cull's fraction test), 0 <= min_q <= 65536.
+ *   ORDER: the kept overlays in increasing q (scene, layer order), compacted:
+ *     slot[q] = the number of kept overlays before q, or -1 when q is not kept;
+ *     *count = the number of kept overlays.
+ *   ROW slot[q] of targets (float32[T][6]) = (scene, class, cx, cy, w, h),
+ *     cx = float(x0 + x1) / float(2·bg_w), w = float(x1 - x0) / float(bg_w), cy
+ *     and h alike with y and bg_h: each ONE correctly rounded float32 division.
+ *     bg_w, bg_h <= IPP_FEED_MAX_SIDE = 2^23 guarantees that both operands are
+ *     integers of at most 2^24, which float32 holds exactly, for every box
+ *     inside the background (0 <= x0 < x1 <= bg_w); larger sides are refused.
+ *     scene and class are converted to float32 (exact below 2^24).
+ *   Rows count .. T-1 are -1 in all six elements.  EVERY element of targets
+ *   and slot and *count are written: `targets[:, 0] >= 0` masks the rows
+ *   without reading count.
+ * One workgroup of 1024 threads: it inverts the permutation into slot (an
+ * integer max, the same in any order), then sweeps the T overlays in chunks of
+ * 1024 with a carried prefix.  No float atomic, nothing depends on an order.
+ * IPP_E_ARG, before any launch: a NULL pointer other than class_ids; a pointer
+ * not 4-B aligned; n_images < 0; n_scenes or per_scene < 1; n_images or T >
+ * IPP_FEED_MAX_TARGETS; bg_w or bg_h outside 1..IPP_FEED_MAX_SIDE; min_q
+ * outside 0..65536.
+ *
+ * ipp_scene_feed_index_map: map = the visibility maps of ipp_pipe_scene_map
+ * (n_scenes slots of bg_h rows of map_pitch bytes), slot = what
+ * ipp_scene_feed_targets wrote for the same scenes.  out has the map's layout.
+ * For byte v at (Y, X < bg_w) of scene s, with keepmask_s = the bits k with
+ * slot[s·per_scene + k] >= 0 and v' = v & keepmask_s:
+ *   out = 0 when v' == 0, else 1 + the number of bits of keepmask_s below the
+ *   topmost set bit of v': 1 + the row, within the scene's run of targets, of
+ *   the topmost kept layer visible there.
+ * Columns [bg_w, map_pitch) of out are 0 whatever the map holds there; every
+ * byte of all n_scenes slots is written.  A 256-entry table per scene in LDS;
+ * 16-B loads and stores.
+ * IPP_E_ARG, before any launch: a NULL pointer; map or out not 16-B, slot not
+ * 4-B aligned; n_scenes, bg_w or bg_h < 1; per_scene outside
+ * 1..IPP_SCENE_MAP_MAX_LAYERS; map_pitch < bg_w, not a multiple of 16 or >=
+ * 2^31; bg_h·map_pitch >= 2^32; n_scenes·⌈bg_h·map_pitch / 16384⌉ >= 2^31 - 1. */
+#define IPP_FEED_MAX_SIDE 8388608
+#define IPP_FEED_MAX_TARGETS 1048576
+int ipp_scene_feed_images(const uint8_t* in, void* out, const void* lut, int32_t n_scenes,
+                          int32_t bg_w, int32_t bg_h, int32_t elem_size, int32_t bgr, void* stream);
+int ipp_scene_feed_targets(const int32_t* rows, const int32_t* scene_layer,
+                           const int32_t* class_ids /* may be NULL */, int32_t n_images,
+                           int32_t n_scenes, int32_t per_scene, int32_t bg_w, int32_t bg_h,
+                           int32_t min_q, float* targets, int32_t* count, int32_t* slot, void* stream);
+int ipp_scene_feed_index_map(const uint8_t* map, int64_t map_pitch, int32_t bg_w, int32_t bg_h,
+                             const int32_t* slot, int32_t n_scenes, int32_t per_scene, uint8_t* out,
+                             void* stream);
 
 /* ------------------------------------------------------------------------ */
 /* K10-K13: pixels_isolés.keep_largest_component                             */
