@@ -97,9 +97,24 @@ int ipp_rotate_flip_nearest(const uint8_t* src, uint8_t* dst,
  * full RGBA canvas (out_w × out_h = the expanded size) with the flip bits
  * folded into the write (bit0 mirror x, bit1 mirror y); the caller crops it
  * to its alpha bbox (ipp_alpha_bbox + ipp_copy_window).  m = Pillow's double
- * inverse matrix. */
+ * inverse matrix, and it may be any matrix: the call is
+ * Image.transform((out_w, out_h), AFFINE, m, BILINEAR) of the window
+ * [in_x0, in_x0+in_w) × [in_y0, in_y0+in_h), which is the whole image the
+ * filter sees — neighbours are clamped to the window and a row below it is
+ * never read, whatever surrounds it in src.
+ * One launch takes n_images descriptors of any sizes under one max_out_w ×
+ * max_out_h grid (each ≥ the largest out_w / out_h, both > 0).
+ *   - Every output pixel is one aligned 4-byte store: dst must be 4-byte
+ *     aligned, and dst_off and dst_pitch (≥ 4*out_w) multiples of 4.  No more
+ *     is asked (not 16), and only the 4*out_w bytes of each row are written.
+ *   - The source is read byte by byte: src, src_off and src_pitch
+ *     (≥ in_w*src_cn) need no alignment, and no byte outside the window is
+ *     read.
+ *   - Empty items are allowed: out_w = 0 or out_h = 0 writes nothing, and
+ *     in_w = 0 or in_h = 0 rejects every point, so the canvas is written as
+ *     zeros and src is not read. */
 typedef struct ipp_affine_desc {
-    int64_t src_off, dst_off;
+    int64_t src_off, dst_off;         /* dst_off: multiple of 4              */
     int32_t src_pitch, src_cn;        /* cn 3 (α = 255) or 4 (RGBA)          */
     int32_t in_x0, in_y0, in_w, in_h; /* source window seen by rotate        */
     int32_t out_w, out_h, dst_pitch;  /* canvas; dst_pitch multiple of 4     */

@@ -107,18 +107,42 @@ def rotate_expand_bilinear(img: np.ndarray, angle: float) -> np.ndarray:
     g = rotate_geometry(w, h, angle)
     if g["kind"] in ("copy", "rot90", "rot180", "rot270"):
         return rotate_expand_nearest(img, angle)
-    m0, m1, m2, m3, m4, m5 = g["matrix"]
-    nw, nh = g["nw"], g["nh"]
-    src = premultiply(img).astype(np.float64)
-    X = np.arange(nw, dtype=np.float64)[None, :] + 0.5
-    Y = np.arange(nh, dtype=np.float64)[:, None] + 0.5
-    xin = m0 * X + m1 * Y + m2
-    yin = m3 * X + m4 * Y + m5
+    return affine_bilinear(img, g["matrix"], g["nw"], g["nh"])
+
+
+def affine_bilinear_samples(m: Sequence[float], w: int, h: int, out_w: int, out_h: int) -> dict:
+    """Where ``affine_bilinear`` samples a w × h source for every pixel of an
+    out_w × out_h canvas: the source point (xin, yin) in double, ``ok`` (the
+    point is inside [0, w) × [0, h)), the integer cell (xi, yi) = floor of the
+    point shifted by -0.5, and the weights (dx, dy).  All (out_h, out_w)."""
+    m0, m1, m2, m3, m4, m5 = (float(v) for v in m)
+    X = np.arange(out_w, dtype=np.float64)[None, :] + 0.5
+    Y = np.arange(out_h, dtype=np.float64)[:, None] + 0.5
+    xin = (m0 * X + m1 * Y) + m2
+    yin = (m3 * X + m4 * Y) + m5
     ok = (xin >= 0.0) & (xin < w) & (yin >= 0.0) & (yin < h)
     xs, ys = xin - 0.5, yin - 0.5
-    xi, yi = np.floor(xs), np.floor(ys)
-    dx, dy = (xs - xi)[..., None], (ys - yi)[..., None]
-    xi, yi = xi.astype(np.int64), yi.astype(np.int64)
+    xf, yf = np.floor(xs), np.floor(ys)
+    with np.errstate(invalid="ignore"):         # points far outside are rejected, their cell is not used
+        xi = np.where(ok, xf, 0.0).astype(np.int64)
+        yi = np.where(ok, yf, 0.0).astype(np.int64)
+    return {"xin": xin, "yin": yin, "ok": ok, "xi": xi, "yi": yi, "dx": xs - xf, "dy": ys - yf}
+
+
+def affine_bilinear(img_rgba: np.ndarray, m: Sequence[float], out_w: int, out_h: int) -> np.ndarray:
+    """Pillow ``Image.transform((out_w, out_h), AFFINE, m, BILINEAR)`` of an
+    RGBA array for any double matrix m (Geometry.c ``affine_transform`` +
+    ``bilinear_filter32RGB`` through RGBa, as ``rotate_expand_bilinear``
+    describes): output (x, y) reads the source point
+    ``(m0(x+.5) + m1(y+.5)) + m2``, ``(m3(x+.5) + m4(y+.5)) + m5``.  An empty
+    source rejects every point (a canvas of zeros)."""
+    h, w = img_rgba.shape[:2]
+    if w == 0 or h == 0 or out_w == 0 or out_h == 0:
+        return np.zeros((out_h, out_w, 4), np.uint8)
+    s = affine_bilinear_samples(m, w, h, out_w, out_h)
+    ok, xi, yi = s["ok"], s["xi"], s["yi"]
+    dx, dy = s["dx"][..., None], s["dy"][..., None]
+    src = premultiply(img_rgba).astype(np.float64)
     x0, x1 = np.clip(xi, 0, w - 1), np.clip(xi + 1, 0, w - 1)
     y0, y1 = np.clip(yi, 0, h - 1), np.clip(yi + 1, 0, h - 1)
     y1ok = ((yi + 1 >= 0) & (yi + 1 < h))[..., None]

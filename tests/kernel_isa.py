@@ -22,10 +22,11 @@ needs_hipcc = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not av
 LDS_MAX = 64 * 1024
 
 
-def compile_isa(src: Path, out: Path, inc: Path = CSRC) -> None:
-    """Device code of `src` as gfx950 assembly in `out`; `inc` holds the csrc headers."""
+def compile_isa(src: Path, out: Path, inc: Path = CSRC, extra=()) -> None:
+    """Device code of `src` as gfx950 assembly in `out`; `inc` holds the csrc
+    headers, `extra` is further compiler flags."""
     subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", f"-I{ROOT / 'include'}",
-                    f"-I{inc}", "-S", "--cuda-device-only", str(src), "-o", str(out)], check=True,
+                    f"-I{inc}", *extra, "-S", "--cuda-device-only", str(src), "-o", str(out)], check=True,
                    capture_output=True)
 
 

@@ -15,7 +15,9 @@ on the same cases.  This module holds
 * the numpy references that ``oracle/ops.py`` has no routine for (window
   slices with flips, the box of α ≥ alpha_min);
 * ``gather_model``, the prepared gather evaluated on the host from a
-  descriptor, with the bounds of every load asserted.
+  descriptor, with the bounds of every load asserted;
+* ``BilinearLaunch``, the flat source, descriptors and packed destination of
+  one ipp_rotate_bilinear launch through the C ABI.
 
 No GPU work here.  Sizes are (w, h) in the tables and (h, w, cn) in arrays.
 """
@@ -403,6 +405,243 @@ ROTATE_SEED = 8800
 def rotate_image(k: int) -> np.ndarray:
     w, h = ROTATE_SHAPES[k]
     return rgba_image(ROTATE_SEED + k, w, h)
+
+
+# ---------------------------------------------------------------------------
+# 8b. ipp_rotate_bilinear through the C ABI: items
+#       (w, h, cn, window | None, matrix, (out_w, out_h) | None, flip bits,
+#        src_pad_bytes, dst_pad_bytes, exact)
+#     of ONE ragged launch.  k_rotate_bilinear: a block is 64 × 4 outputs, the
+#     grid is sized by the widest and by the tallest output (two different
+#     items), so most items leave blocks and lanes that must exit.
+#
+#     matrix is Pillow's six doubles (Image.transform(size, AFFINE, m)): output
+#     (x, y) reads the window at ((m0·X + m1·Y) + m2, (m3·X + m4·Y) + m5) with
+#     X = x + ½, Y = y + ½; or ("rot", angle), the matrix and the canvas of
+#     geometry.rotation_plan on the window (out size None).
+#
+#     A windowed source is BILINEAR_SURROUND everywhere outside its window, a
+#     colour and an α that no window pixel has: a neighbour clamped to the image
+#     and not to the window, or a row y + 1 read below the window, shows.
+#     src_pad_bytes > 0 makes src_pitch = w·cn + pad, the padding filled with
+#     BILINEAR_SRC_JUNK; dst_pad_bytes makes dst_pitch = 4·out_w + pad.  The
+#     sources are packed back to back in the table's order whatever the launch
+#     order is; the last one belongs to the item whose matrix rejects every
+#     pixel, so it is never read.
+#
+#     exact: an opaque source whose colours are multiples of 4 under a matrix of
+#     dyadic fractions.  Every product and sum of the lerps is then exact in
+#     double, many land on an integer, and the CPU module also holds the item
+#     to an evaluation in fractions.Fraction.
+# ---------------------------------------------------------------------------
+
+BILINEAR_I = (1.0, 0.0, 0.0, 0.0, 1.0, 0.0)
+
+
+def _shift(tx: float, ty: float):
+    return (1.0, 0.0, float(tx), 0.0, 1.0, float(ty))
+
+
+BILINEAR_ITEMS = [
+    # out sizes on the tile edges: widths 1 63 64 65 129, heights 1 3 4 5 9; the
+    # translations by ¼, ½ and ¾ of a pixel in x and in y
+    (9, 6, 4, None, BILINEAR_I, (1, 1), 3, 0, 0, False),                      # 0: reads pixel (0, 0) alone
+    (63, 3, 3, None, _shift(0.25, 0.5), (63, 3), 1, 0, 4, True),
+    (64, 4, 4, None, _shift(0.5, 0.25), (64, 4), 2, 0, 0, True),
+    (65, 5, 3, None, _shift(0.75, 0.75), (65, 5), 3, 1, 60, True),
+    (129, 2, 4, None, _shift(0.0, 0.5), (129, 1), 1, 5, 0, False),            # 4: the widest
+    (4, 9, 3, None, _shift(-0.5, 0.0), (3, 9), 2, 0, 4, True),                # m2 = -½: xin = 0.0 at x = 0
+    (13, 7, 3, None, BILINEAR_I, (13, 7), 0, 0, 0, False),                    # identity: the source itself
+    (6, 4, 4, None, BILINEAR_I, (6, 4), 0, 0, 60, False),                     # unpremultiply(premultiply)
+    # empty items
+    (5, 4, 4, None, BILINEAR_I, (7, 0), 0, 0, 0, False),                      # 8: out_h = 0, nothing written
+    (5, 4, 3, (2, 1, 0, 3), BILINEAR_I, (6, 3), 0, 0, 4, False),              # 9: in_w = 0, zeros written
+    # windows: strictly inside (10, 11), reaching the last row and column (12, 13)
+    (20, 12, 4, (3, 2, 11, 7), (0.5, 0.0, 0.0, 0.0, 0.5, 0.0), (22, 14), 2, 13, 0, False),
+    (17, 11, 3, (2, 3, 9, 5), ("rot", 33.3), None, 1, 5, 4, False),
+    (12, 9, 3, (4, 3, 8, 6), (0.5, 0.0, 0.0, 0.0, 0.5, 0.0), (16, 12), 3, 0, 0, True),
+    (10, 8, 4, (1, 2, 9, 6), ("rot", 117.0), None, 0, 1, 0, False),
+    # the reject test and the row fallback
+    (5, 3, 4, None, _shift(0.5, 0.0), (5, 3), 0, 0, 0, False),                # 14: last column at xin = in_w
+    (5, 3, 4, None, _shift(0.5 - 2.0 ** -50, 0.0), (5, 3), 1, 0, 0, False),   # one ulp inside: accepted
+    # rows with yi = -1 and rows with yi + 1 = in_h.  No unit translation has
+    # both (the first needs yin < ½ at y = 0, the second yin ≥ in_h - ½ at
+    # y = in_h - 1), so one item stretches y by 2 and two translate by ∓¼.
+    (6, 4, 3, None, (1.0, 0.0, 0.0, 0.0, 0.5, 0.0), (6, 8), 0, 0, 0, True),
+    (7, 5, 4, None, _shift(0.0, -0.25), (7, 5), 2, 0, 0, True),
+    (7, 5, 3, None, _shift(0.0, 0.25), (7, 5), 3, 13, 0, True),
+    # shears, ×2 down, ×4 up, mirrors, a constant canvas
+    (16, 6, 4, None, (1.0, 0.5, -1.0, 0.0, 1.0, 0.0), (16, 6), 1, 0, 0, False),
+    (10, 7, 3, None, (1.0, 0.5, -1.0, 0.25, 1.0, 0.0), (12, 7), 0, 0, 0, True),
+    (18, 10, 3, None, (2.0, 0.0, 0.0, 0.0, 2.0, 0.0), (9, 5), 1, 0, 0, True),
+    (4, 3, 4, None, (0.25, 0.0, 0.0, 0.0, 0.25, 0.0), (16, 12), 0, 0, 0, False),
+    (3, 2, 3, None, (0.25, 0.0, 0.0, 0.0, 0.25, 0.0), (12, 8), 2, 1, 0, True),
+    (9, 5, 4, None, (-1.0, 0.0, 9.0, 0.0, 1.0, 0.0), (9, 5), 0, 0, 0, False),
+    (9, 5, 4, None, (-1.0, 0.0, 9.25, 0.0, 1.0, 0.0), (9, 5), 2, 0, 0, True),
+    (6, 4, 4, None, (0.0, 0.0, 2.25, 0.0, 0.0, 1.75), (5, 3), 3, 0, 0, False),
+    # rotations about the centre (33.3 and 117 are items 11 and 13)
+    (30, 20, 3, None, ("rot", 0.01), None, 2, 0, 0, False),
+    (16, 16, 4, None, ("rot", 45.0), None, 3, 0, 4, False),
+    (34, 20, 4, None, ("rot", 89.99), None, 1, 0, 0, False),                  # 29: the tallest (21 × 35)
+    (13, 2, 3, None, ("rot", 301.7), None, 0, 5, 0, False),
+    # every pixel rejected: zeros, and the source (the buffer's last) is not read
+    (40, 8, 4, None, _shift(1e6, -1e6), (9, 4), 1, 0, 0, False),
+]
+BILINEAR_SEED = 8850
+BILINEAR_SRC_JUNK = 0x5A
+BILINEAR_SENTINEL = 0xA5
+BILINEAR_TAIL = 256                  # sentinel bytes after the packed output
+BILINEAR_SURROUND = (251, 251, 251, 77)
+BILINEAR_WIDTHS = (1, 63, 64, 65, 129)
+BILINEAR_HEIGHTS = (1, 3, 4, 5, 9)
+BILINEAR_ANGLES = (0.01, 33.3, 45.0, 89.99, 117.0, 301.7)
+BILINEAR_ORDERS = ("listed", "reversed", "widest_first")
+BILINEAR_WIDEST, BILINEAR_TALLEST = 4, 29
+BILINEAR_TILE_W, BILINEAR_TILE_H = 64, 4      # BW, BH of ipp_bilinear.hip
+
+
+def bilinear_window(item):
+    w, h, win = item[0], item[1], item[3]
+    return win if win is not None else (0, 0, w, h)
+
+
+def bilinear_matrix(item):
+    """(matrix, (out_w, out_h)) of an item; a ("rot", angle) entry is planned
+    on the window by geometry.rotation_plan."""
+    m, size = item[4], item[5]
+    if m[0] == "rot":
+        from image_processor_pipeline_amd import geometry as G
+        _, _, ww, wh = bilinear_window(item)
+        plan = G.rotation_plan(ww, wh, float(m[1]))
+        assert plan.M is not None and size is None
+        return tuple(plan.M), (plan.nw, plan.nh)
+    return tuple(float(v) for v in m), size
+
+
+def bilinear_source(seed: int, item) -> np.ndarray:
+    """The whole (h, w, cn) source of an item: the window's pixels (opaque and
+    multiples of 4 for an `exact` item), BILINEAR_SURROUND around a window."""
+    w, h, cn, win, exact = item[0], item[1], item[2], item[3], item[9]
+    x0, y0, ww, wh = bilinear_window(item)
+    px = rgb_image(seed, ww, wh) if cn == 3 else rgba_image(seed, ww, wh, "opaque" if exact else "palette")
+    if exact:
+        px[..., :3] &= 0xFC
+    if win is None:
+        return px
+    px[..., :3][px[..., :3] == BILINEAR_SURROUND[0]] = BILINEAR_SURROUND[0] - 1
+    img = np.empty((h, w, cn), np.uint8)
+    img[...] = np.asarray(BILINEAR_SURROUND[:cn], np.uint8)
+    img[y0:y0 + wh, x0:x0 + ww] = px
+    return img
+
+
+def bilinear_order(name: str, n: int = len(BILINEAR_ITEMS)):
+    idx = list(range(n))
+    if name == "reversed":
+        idx.reverse()
+    elif name == "widest_first":
+        idx.remove(BILINEAR_WIDEST)
+        idx.insert(0, BILINEAR_WIDEST)
+    elif name != "listed":
+        raise ValueError(name)
+    return idx
+
+
+class BilinearLaunch:
+    """One ipp_rotate_bilinear launch: the flat source buffer (sources in the
+    items' own order, back to back), the AFFINE_DESC array in launch order and
+    the packed destination's layout.  An output starts 4 bytes after the end of
+    the one before it (12 bytes for every third), so dst_off is a multiple of 4
+    and, for most items, not of 16.  wins[j] / fulls[j] are the window and the
+    whole source of launch item j as arrays."""
+
+    def __init__(self, items, seed: int, order=None):
+        from image_processor_pipeline_amd import _native as N
+        order = list(range(len(items))) if order is None else list(order)
+        chunks, offs, imgs, pos = [], [], [], 0
+        for k, it in enumerate(items):
+            w, h, cn, pad = it[0], it[1], it[2], it[7]
+            img = bilinear_source(seed + k, it)
+            rows = np.full((h, w * cn + pad), BILINEAR_SRC_JUNK, np.uint8)
+            rows[:, :w * cn] = img.reshape(h, w * cn)
+            chunks.append(rows.reshape(-1))
+            offs.append(pos)
+            imgs.append(img)
+            pos += rows.size
+        self.flat = np.concatenate(chunks)
+        self.items = [items[k] for k in order]
+        self.index = order
+        self.fulls = [imgs[k] for k in order]
+        self.wins, self.mats, self.shapes = [], [], []
+        n = len(order)
+        self.descs = np.zeros(n, N.AFFINE_DESC)
+        self.dst_offsets, self.dst_pitches = np.zeros(n, np.int64), np.zeros(n, np.int64)
+        off = 0
+        for j, (k, it) in enumerate(zip(order, self.items)):
+            w, cn, flip, spad, dpad = it[0], it[2], it[6], it[7], it[8]
+            x0, y0, ww, wh = bilinear_window(it)
+            m, (ow, oh) = bilinear_matrix(it)
+            self.wins.append(np.ascontiguousarray(imgs[k][y0:y0 + wh, x0:x0 + ww]))
+            self.mats.append(m)
+            self.shapes.append((oh, ow))
+            off += 12 if j % 3 == 2 else 4
+            d = self.descs[j]
+            d["src_off"], d["dst_off"] = offs[k], off
+            d["src_pitch"], d["src_cn"] = w * cn + spad, cn
+            d["in_x0"], d["in_y0"], d["in_w"], d["in_h"] = x0, y0, ww, wh
+            d["out_w"], d["out_h"], d["dst_pitch"], d["flip"] = ow, oh, 4 * ow + dpad, flip
+            d["m"] = m
+            self.dst_offsets[j], self.dst_pitches[j] = off, 4 * ow + dpad
+            off += (4 * ow + dpad) * oh
+        self.total_bytes = off
+        self.max_w = max(s[1] for s in self.shapes)
+        self.max_h = max(s[0] for s in self.shapes)
+
+
+def bilinear_launch(order: str = "listed") -> BilinearLaunch:
+    return BilinearLaunch(BILINEAR_ITEMS, BILINEAR_SEED, bilinear_order(order))
+
+
+def flip_ref(img: np.ndarray, flip: int) -> np.ndarray:
+    """img mirrored in x (flip bit 0) and / or in y (bit 1)."""
+    return window_ref(img, (0, 0, img.shape[1], img.shape[0]), flip)
+
+
+def bilinear_refs(launch: BilinearLaunch):
+    """The oracle's output of every launch item from its window: an RGB window
+    through convert('RGBA'), the affine transform, then the flip."""
+    return [flip_ref(ops.affine_bilinear(ops.to_rgba(win), m, ow, oh), it[6])
+            for it, win, m, (oh, ow) in zip(launch.items, launch.wins, launch.mats, launch.shapes)]
+
+
+def bilinear_samples(launch: BilinearLaunch, j: int) -> dict:
+    """ops.affine_bilinear_samples of launch item j (before the flip)."""
+    oh, ow = launch.shapes[j]
+    _, _, ww, wh = bilinear_window(launch.items[j])
+    return ops.affine_bilinear_samples(launch.mats[j], ww, wh, ow, oh)
+
+
+# The alpha round trip inside k_rotate_bilinear (premultiply → lerp in double →
+# truncate → unpremultiply) on the 256 × 256 square of every (α, c): under the
+# identity every weight is 0 and the kernel returns
+# unpremultiply(premultiply(img)); half a pixel along x mixes neighbouring
+# colours under one α, half a pixel along y neighbouring α under one colour.
+BILINEAR_ALPHA_MATRICES = (BILINEAR_I, _shift(0.5, 0.0), _shift(0.0, 0.5))
+
+
+def alpha_colour_square() -> np.ndarray:
+    """Pixel (a, c) = (c, 255 - c, c ^ 0x55, a): every α with every colour byte."""
+    a, c = np.meshgrid(np.arange(256, dtype=np.uint8), np.arange(256, dtype=np.uint8), indexing="ij")
+    return np.stack([c, 255 - c, c ^ 0x55, a], axis=-1)
+
+
+def bilinear_alpha_launch(k: int) -> BilinearLaunch:
+    """The single-item launch of BILINEAR_ALPHA_MATRICES[k] over the square."""
+    launch = BilinearLaunch([(256, 256, 4, None, BILINEAR_ALPHA_MATRICES[k], (256, 256), 0, 0, 0, False)], 0)
+    sq = alpha_colour_square()
+    launch.flat = sq.reshape(-1).copy()
+    launch.wins, launch.fulls = [sq], [sq]
+    return launch
 
 
 # ---------------------------------------------------------------------------

@@ -19,6 +19,11 @@ arithmetic both paths share (``div255``, ``blend16``, ``unpremultiply``,
   6. test_alpha_bbox_ragged, test_alpha_bbox_min_ragged
   7. test_enhance_*                 ipp_enhance_lsum / _color, ipp_box_pass
   8. test_rotate_bilinear_small     ipp_rotate_bilinear + box + window copy
+     test_bilinear_ragged_vs_oracle, test_bilinear_alpha_square   ipp_rotate_bilinear
+     through the C ABI: many items, windows, pitches, offsets, any matrix, the
+     alpha round trip, into a sentinel-filled buffer
+     test_rotate_bilinear_canvas_*, test_rotate_crop_bilinear_*   the wrappers on
+     RGB tensors, views, angles outside [0, 360), flips, an empty box
   9. test_gather_ragged_vs_oracle, test_gather_ragged_unprepared_vs_oracle,
      test_gather_block_count_residues   ipp_rotate_flip_nearest over descriptors
      from plan_rotate_flip + ipp_gather_prepare: mixed sizes, windows, pitches
@@ -88,24 +93,18 @@ def _h_pass_identity(D, img, flags):
     return dst.cpu().numpy()
 
 
-def _alpha_colour_square():
-    """Pixel (a, c) = (c, 255 - c, c ^ 0x55, a): every α with every colour byte."""
-    a, c = np.meshgrid(np.arange(256, dtype=np.uint8), np.arange(256, dtype=np.uint8), indexing="ij")
-    return np.stack([c, 255 - c, c ^ 0x55, a], axis=-1)
-
-
 def test_unpremultiply_whole_domain(D):
     """rgba2rgbA over its whole domain, 254 dividing α × 256 colour bytes (and
     α 0 / 255): the float quotient's two corrections and the clamp at 255."""
     from image_processor_pipeline_amd import _native as N
-    img = _alpha_colour_square()
+    img = R.alpha_colour_square()
     _same(_h_pass_identity(D, img, N.IPP_RS_UNPREMULTIPLY), ops.unpremultiply(img), "unpremultiply")
 
 
 def test_premultiply_whole_domain(D):
     """rgbA2rgba (MULDIV255) over every (α, c)."""
     from image_processor_pipeline_amd import _native as N
-    img = _alpha_colour_square()
+    img = R.alpha_colour_square()
     _same(_h_pass_identity(D, img, N.IPP_RS_PREMULTIPLY), ops.premultiply(img), "premultiply")
 
 
@@ -250,6 +249,106 @@ def test_rotate_bilinear_small(D, k):
     for a in R.ROTATE_ANGLES:
         got = D.rotate_crop_bilinear(_t(img), a).cpu().numpy()
         _same(got, ops.rotate_and_crop(img, a, "bilinear"), (R.ROTATE_SHAPES[k], a))
+
+
+@pytest.fixture(scope="module")
+def bilinear_cases():
+    """{order: (launch, oracle outputs)}; the outputs are computed once, in the
+    table's order, and shared by the three orders."""
+    listed = R.bilinear_launch()
+    refs = R.bilinear_refs(listed)
+    out = {}
+    for order in R.BILINEAR_ORDERS:
+        launch = R.bilinear_launch(order)
+        out[order] = (launch, [refs[k] for k in launch.index])
+    return out
+
+
+def _bilinear_vs_oracle(D, launch, refs):
+    """One ipp_rotate_bilinear launch through the C ABI into total_bytes + 256
+    bytes of sentinel: every item's rows equal its reference, and every byte
+    outside the items' 4·out_w row bytes — row padding, the gaps between the
+    items, the tail, the item without rows — still holds the sentinel."""
+    from image_processor_pipeline_amd import _native as N
+    assert len(launch.descs) == len(refs) == len(launch.items)
+    out = torch.full((launch.total_bytes + R.BILINEAR_TAIL,), R.BILINEAR_SENTINEL, dtype=torch.uint8, device=DEV)
+    src = _t(launch.flat)
+    dd = D._to_dev(launch.descs, src.device)
+    N.check(N.load().ipp_rotate_bilinear(src.data_ptr(), out.data_ptr(), dd.data_ptr(), len(launch.descs),
+                                         launch.max_w, launch.max_h, D._stream(src.device)), "ipp_rotate_bilinear")
+    got = out.cpu().numpy()
+    written = np.zeros(got.size, bool)
+    for j, ((oh, ow), off, pitch, ref) in enumerate(zip(launch.shapes, launch.dst_offsets, launch.dst_pitches, refs)):
+        rows = got[off:off + oh * pitch].reshape(oh, pitch)
+        _same(rows[:, :4 * ow].reshape(oh, ow, 4), ref, (j, launch.items[j]))
+        written[off:off + oh * pitch].reshape(oh, pitch)[:, :4 * ow] = True
+    stray = np.flatnonzero(~written & (got != R.BILINEAR_SENTINEL))
+    assert stray.size == 0, ("bytes written outside the items' rows", stray[:8].tolist(), launch.total_bytes)
+
+
+@pytest.mark.parametrize("order", R.BILINEAR_ORDERS)
+def test_bilinear_ragged_vs_oracle(D, bilinear_cases, order):
+    _bilinear_vs_oracle(D, *bilinear_cases[order])
+
+
+@pytest.mark.parametrize("k", range(len(R.BILINEAR_ALPHA_MATRICES)), ids=["identity", "half_x", "half_y"])
+def test_bilinear_alpha_square(D, k):
+    """premultiply → lerp in double → truncate → unpremultiply inside the
+    kernel, over every (α, c): alone, then with neighbours mixed half and half."""
+    launch = R.bilinear_alpha_launch(k)
+    refs = R.bilinear_refs(launch)
+    if k == 0:
+        sq = R.alpha_colour_square()
+        assert np.array_equal(refs[0], ops.unpremultiply(ops.premultiply(sq)))
+    _bilinear_vs_oracle(D, launch, refs)
+
+
+BILINEAR_WRAPPER_ANGLES = (-33.3, 393.3, 450.0)
+
+
+@pytest.mark.parametrize("angle", BILINEAR_WRAPPER_ANGLES + (33.3,))
+def test_rotate_bilinear_canvas_rgb_tensor(D, angle):
+    """A 3-channel tensor (src_cn = 3 through the wrapper), at angles below 0
+    and above 360; 450 is the 90° transpose."""
+    img = R.rgb_image(R.BILINEAR_SEED + 700, 21, 13)
+    got = D.rotate_bilinear_canvas(_t(img), angle).cpu().numpy()
+    _same(got, ops.rotate_expand_bilinear(ops.to_rgba(img), angle), angle)
+
+
+@pytest.mark.parametrize("angle", BILINEAR_WRAPPER_ANGLES)
+def test_rotate_bilinear_canvas_noncontiguous_view(D, angle):
+    """A strided view: every second row, columns 3 .. 19 of a wider image."""
+    big = R.rgba_image(R.BILINEAR_SEED + 701, 24, 31)
+    view = _t(big)[::2, 3:20]
+    assert not view.is_contiguous()
+    img = np.ascontiguousarray(big[::2, 3:20])
+    _same(D.rotate_bilinear_canvas(view, angle, 1).cpu().numpy(),
+          R.flip_ref(ops.rotate_expand_bilinear(img, angle), 1), angle)
+    _same(D.rotate_crop_bilinear(view, angle).cpu().numpy(), ops.rotate_and_crop(img, angle, "bilinear"), angle)
+
+
+@pytest.mark.parametrize("flip", [1, 2, 3])
+def test_rotate_crop_bilinear_flips(D, flip):
+    """rotate_crop_bilinear(img, a, flip) on an odd-sized image is the flip of
+    the oracle's crop; 450° takes the gather's transpose path."""
+    img = R.rgba_image(R.BILINEAR_SEED + 702, 15, 9)
+    img[:2] = 0                                   # a transparent band: the box is off-centre
+    img[:, :3, 3] = 0
+    for a in (33.3,) + BILINEAR_WRAPPER_ANGLES:
+        crop = ops.rotate_and_crop(img, a, "bilinear")
+        assert crop.shape != ops.rotate_expand_bilinear(img, a).shape
+        _same(D.rotate_crop_bilinear(_t(img), a, flip).cpu().numpy(), R.flip_ref(crop, flip), (a, flip))
+
+
+@pytest.mark.parametrize("angle", [33.3, 450.0])
+def test_rotate_crop_bilinear_all_transparent(D, angle):
+    """No α above 0: the box is None and the canvas comes back — zeros at
+    33.3° (RGBa has no colour under α = 0), the transposed source at 450°."""
+    img = R.rgba_image(R.BILINEAR_SEED + 703, 11, 7, "transparent")
+    exp = ops.rotate_and_crop(img, angle, "bilinear")
+    assert ops.getbbox_alpha(ops.rotate_expand_bilinear(img, angle)) is None
+    assert exp.shape == ops.rotate_expand_bilinear(img, angle).shape
+    _same(D.rotate_crop_bilinear(_t(img), angle, 2).cpu().numpy(), R.flip_ref(exp, 2), angle)
 
 
 # --------------------------------------------------------------------------- 9. rotate / flip gather

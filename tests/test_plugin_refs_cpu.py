@@ -4,7 +4,9 @@ plugin-path kernels to — and the properties the case tables claim (tile edges,
 row phases, corners, zone sizes), so a table edited later cannot lose them
 silently.  For the rotate / flip gather it also holds plan_rotate_flip and
 ipp_gather_prepare to the oracle through ``plugin_refs.gather_model``, which
-asserts the bounds of every load ipp_rotate_flip_nearest would make.
+asserts the bounds of every load ipp_rotate_flip_nearest would make.  For the
+bilinear launches ``ops.affine_bilinear`` is held to ``Image.transform`` and,
+where the arithmetic is exact, to an evaluation over the rationals.
 """
 import numpy as np
 import pytest
@@ -316,6 +318,233 @@ def test_rotate_bilinear_oracle_equals_pillow(k):
         assert got.shape == np.asarray(exp).shape, (R.ROTATE_SHAPES[k], a)
         assert np.array_equal(got, np.asarray(exp)), (R.ROTATE_SHAPES[k], a)
     assert {0.0, 90.0, 180.0, 270.0} <= set(R.ROTATE_ANGLES) and len(R.ROTATE_ANGLES) >= 7
+
+
+# --------------------------------------------------------------------------- bilinear through the C ABI
+
+def _pil_affine(win, m, ow, oh, flip):
+    """Image.transform(AFFINE, BILINEAR) of a window (an RGB one through
+    convert('RGBA')), flipped with NumPy.  A window without pixels is made
+    with Image.new (no array interface for it)."""
+    h, w, cn = win.shape
+    im = Image.fromarray(win) if w and h else Image.new("RGB" if cn == 3 else "RGBA", (w, h))
+    if win.shape[2] == 3:
+        im = im.convert("RGBA")
+    return R.flip_ref(np.asarray(im.transform((ow, oh), Image.Transform.AFFINE, m, BILINEAR)), flip)
+
+
+def _empty(launch, j):
+    oh, ow = launch.shapes[j]
+    return 0 in launch.wins[j].shape[:2] or ow == 0 or oh == 0
+
+
+@pytest.fixture(scope="module")
+def bilinear_listed():
+    launch = R.bilinear_launch()
+    return launch, R.bilinear_refs(launch)
+
+
+def test_affine_bilinear_oracle_equals_pillow(bilinear_listed):
+    launch, refs = bilinear_listed
+    assert len(refs) == len(R.BILINEAR_ITEMS) >= 30
+    for j, (it, win, m, (oh, ow), ref) in enumerate(zip(launch.items, launch.wins, launch.mats, launch.shapes, refs)):
+        assert ref.shape == (oh, ow, 4) and ref.dtype == np.uint8, it
+        if _empty(launch, j):
+            assert not ref.any(), it
+        pil = _pil_affine(win, m, ow, oh, it[6])
+        assert pil.shape == ref.shape and np.array_equal(ref, pil), (j, it)
+
+
+@pytest.mark.parametrize("k", range(len(R.BILINEAR_ALPHA_MATRICES)))
+def test_affine_bilinear_alpha_square_equals_pillow(k):
+    launch = R.bilinear_alpha_launch(k)
+    sq = R.alpha_colour_square()
+    assert np.array_equal(launch.flat.reshape(256, 256, 4), sq) and launch.descs[0]["src_pitch"] == 1024
+    ref = R.bilinear_refs(launch)[0]
+    assert np.array_equal(ref, _pil_affine(sq, launch.mats[0], 256, 256, 0))
+    if k == 0:
+        rt = ops.unpremultiply(ops.premultiply(sq))
+        assert np.array_equal(ref, rt) and (rt != sq).any()          # the round trip is lossy, and kept
+    else:
+        # neighbours are mixed: the canvas differs from the round trip of the
+        # shifted square in partial α, and the rejected last line is zero
+        assert (ref[:, -1] == 0).all() if k == 1 else (ref[-1] == 0).all()
+        moved = sq[:, 1:] if k == 1 else sq[1:]
+        part = ref[:, :-1] if k == 1 else ref[:-1]
+        assert (part != ops.unpremultiply(ops.premultiply(moved))).any()
+
+
+def _fraction_bilinear(img, m, ow, oh):
+    """Geometry.c's bilinear formula over the rationals for an OPAQUE RGBA
+    array (premultiply and unpremultiply are the identity at α = 255)."""
+    from fractions import Fraction as F
+    assert (img[..., 3] == 255).all()
+    h, w = img.shape[:2]
+    m = [F(v) for v in m]
+    half = F(1, 2)
+    out = np.zeros((oh, ow, 4), np.uint8)
+    for y in range(oh):
+        for x in range(ow):
+            X, Y = x + half, y + half
+            xin, yin = m[0] * X + m[1] * Y + m[2], m[3] * X + m[4] * Y + m[5]
+            if not (0 <= xin < w and 0 <= yin < h):
+                continue
+            xs, ys = xin - half, yin - half
+            xi, yi = xs.numerator // xs.denominator, ys.numerator // ys.denominator      # floor
+            dx, dy = xs - xi, ys - yi
+            x0, x1 = min(max(xi, 0), w - 1), min(max(xi + 1, 0), w - 1)
+            y0 = min(max(yi, 0), h - 1)
+            for c in range(4):
+                a, b = int(img[y0, x0, c]), int(img[y0, x1, c])
+                v1 = a + (b - a) * dx
+                v2 = v1
+                if 0 <= yi + 1 < h:
+                    a, b = int(img[yi + 1, x0, c]), int(img[yi + 1, x1, c])
+                    v2 = a + (b - a) * dx
+                v = v1 + (v2 - v1) * dy
+                out[y, x, c] = v.numerator // v.denominator                             # v >= 0: truncation
+    return out
+
+
+def test_affine_bilinear_oracle_equals_exact_rationals(bilinear_listed):
+    """The `exact` items: dyadic matrices on opaque colours that are multiples
+    of 4, where no double operation of the lerps rounds.  Many results are
+    integers, which a last-bit error below would truncate to the byte before."""
+    from fractions import Fraction as F
+    launch, refs = bilinear_listed
+    seen = on_integer = 0
+    for it, win, m, (oh, ow), ref in zip(launch.items, launch.wins, launch.mats, launch.shapes, refs):
+        if not it[9]:
+            continue
+        seen += 1
+        assert all(F(v).denominator in (1, 2, 4) for v in m), it
+        rgba = ops.to_rgba(win)
+        assert (rgba[..., 3] == 255).all() and (rgba[..., :3] % 4 == 0).all(), it
+        exact = _fraction_bilinear(rgba, m, ow, oh)
+        assert np.array_equal(R.flip_ref(exact, it[6]), ref), it
+        s = ops.affine_bilinear_samples(m, win.shape[1], win.shape[0], ow, oh)
+        on_integer += int((s["ok"] & ((s["dx"] * 4) % 1 == 0) & (s["dx"] > 0) & (s["dy"] == 0)).sum())
+    assert seen >= 10 and on_integer > 0
+    shifts = {(m[2], m[5]) for it, m in zip(launch.items, launch.mats) if it[9] and m[:2] + m[3:5] == (1, 0, 0, 1)}
+    assert {0.25, 0.5, 0.75} <= {s[0] for s in shifts} and {0.25, 0.5, 0.75} <= {s[1] for s in shifts}
+
+
+def test_bilinear_table_claims(bilinear_listed):
+    """What section 8b of plugin_refs.py says of its table, from the
+    reference's own index arrays."""
+    launch, refs = bilinear_listed
+    items, n = launch.items, len(launch.items)
+    sizes = [(ow, oh) for oh, ow in launch.shapes]
+    assert all(max(it[0], it[1], ow, oh) <= 256 for it, (ow, oh) in zip(items, sizes))
+    # the out sizes on the 64 × 4 tile's edges; widest and tallest are two items, each alone
+    assert set(R.BILINEAR_WIDTHS) <= {s[0] for s in sizes} and set(R.BILINEAR_HEIGHTS) <= {s[1] for s in sizes}
+    assert {0, 1, 63} <= {s[0] % R.BILINEAR_TILE_W for s in sizes}
+    assert {0, 1, 3} <= {s[1] % R.BILINEAR_TILE_H for s in sizes if s[1]}
+    assert [k for k, s in enumerate(sizes) if s[0] == launch.max_w] == [R.BILINEAR_WIDEST]
+    assert [k for k, s in enumerate(sizes) if s[1] == launch.max_h] == [R.BILINEAR_TALLEST]
+    assert -(-launch.max_w // R.BILINEAR_TILE_W) == 3 and -(-launch.max_h // R.BILINEAR_TILE_H) >= 3
+    # empty items: one writes nothing, one writes zeros
+    assert sum(s[1] == 0 for s in sizes) == 1
+    zero_w = [j for j, it in enumerate(items) if R.bilinear_window(it)[2] == 0]
+    assert len(zero_w) == 1 and sizes[zero_w[0]][0] > 0 and sizes[zero_w[0]][1] > 0 and not refs[zero_w[0]].any()
+    # what the samples visit
+    seen, both = set(), []
+    for j, it in enumerate(items):
+        if _empty(launch, j):
+            continue
+        s = R.bilinear_samples(launch, j)
+        ok, xi, yi = s["ok"], s["xi"], s["yi"]
+        _, _, ww, wh = R.bilinear_window(it)
+        if (ok & (yi == -1)).any() and (ok & (yi + 1 == wh)).any():
+            both.append(j)
+        seen |= {name for name, hit in (
+            ("xi=-1", ok & (xi == -1)), ("yi=-1", ok & (yi == -1)), ("yi+1=in_h", ok & (yi + 1 == wh)),
+            ("xi+1=in_w", ok & (xi + 1 == ww)), ("xin=0.0", ok & (s["xin"] == 0.0)),
+            ("xin=in_w", ~ok & (s["xin"] == ww) & (s["yin"] >= 0) & (s["yin"] < wh)),
+            ("ulp inside", ok & (s["xin"] == np.nextafter(float(ww), 0.0))),
+            ("all rejected", np.array(not ok.any())), ("all accepted", np.array(ok.all())),
+            ("some rejected", np.array(ok.any() and not ok.all()))) if hit.any()}
+        if not ok.any():
+            assert j == n - 1 and not refs[j].any()          # its source ends the buffer and is never read
+    assert seen == {"xi=-1", "yi=-1", "yi+1=in_h", "xi+1=in_w", "xin=0.0", "xin=in_w", "ulp inside", "all rejected",
+                    "all accepted", "some rejected"}
+    assert both                                             # first rows at yi = -1 and last rows at yi + 1 = in_h
+    # matrices
+    mats = launch.mats
+    assert sum(m == R.BILINEAR_I for m in mats) >= 3
+    assert any(m[0] == -1.0 for m in mats) and any(m[0] == 2.0 == m[4] for m in mats)
+    assert any(m[0] == 0.25 == m[4] for m in mats) and any(m[1] != 0 and m[3] == 0 and m[0] == 1 for m in mats)
+    assert any(m[0] == m[1] == m[3] == m[4] == 0.0 for m in mats)
+    rots = sorted(it[4][1] for it in items if it[4][0] == "rot")
+    assert rots == sorted(R.BILINEAR_ANGLES)
+    for it, m, (ow, oh) in zip(items, mats, sizes):
+        if it[4][0] == "rot":
+            _, _, ww, wh = R.bilinear_window(it)
+            g = ops.rotate_geometry(ww, wh, it[4][1])
+            assert m == g["matrix"] and (ow, oh) == (g["nw"], g["nh"]), it
+    # flips on odd and on even sizes, both channel counts
+    for bit, axis in ((1, 0), (2, 1)):
+        assert {s[axis] % 2 for it, s in zip(items, sizes) if it[6] & bit and s[0] and s[1]} == {0, 1}
+    assert {it[6] for it in items} == {0, 1, 2, 3}
+    assert {(it[2], it[6]) for it in items} == {(cn, f) for cn in (3, 4) for f in range(4)}
+    # pitches and offsets
+    assert {1, 5, 13} <= {it[7] for it in items} and {4, 60} == {it[8] for it in items if it[8]}
+    d = launch.descs
+    assert any(int(o) % 4 for o in d["src_off"]) and any(int(o) % 2 for o in d["src_off"])
+    assert (d["dst_off"] % 4 == 0).all() and (d["dst_pitch"] % 4 == 0).all()
+    assert (d["dst_off"] % 16 != 0).sum() >= n // 2 and int(d["dst_off"][0]) == 4
+    assert (launch.flat == R.BILINEAR_SRC_JUNK).sum() >= sum(it[7] * it[1] for it in items)
+    ends = d["dst_off"] + d["dst_pitch"].astype(np.int64) * d["out_h"]
+    assert (d["dst_off"][1:] >= ends[:-1] + 4).all() and int(ends[-1]) == launch.total_bytes
+    last = items[-1]
+    assert int(d["src_off"][-1]) + last[0] * last[1] * last[2] == launch.flat.size
+    assert last[0] * last[1] * last[2] >= int(d["src_pitch"].max())     # a row past any other source stays inside
+    # the three orders
+    orders = [R.bilinear_order(o) for o in R.BILINEAR_ORDERS]
+    assert all(sorted(o) == list(range(n)) for o in orders) and len({tuple(o) for o in orders}) == 3
+    assert orders[1] == orders[0][::-1] and orders[2][0] == R.BILINEAR_WIDEST != orders[0][0]
+    for name in R.BILINEAR_ORDERS[1:]:
+        other = R.bilinear_launch(name)
+        assert np.array_equal(other.flat, launch.flat)
+        for j, k in enumerate(other.index):
+            assert np.array_equal(other.wins[j], launch.wins[k]) and other.descs[j]["src_off"] == d[k]["src_off"]
+
+
+def test_bilinear_windows_tell_the_window_from_the_image(bilinear_listed):
+    """Every windowed item has samples with a neighbour outside the window and
+    inside the image, at a weight above zero, where the image holds another
+    pixel than the one the reference clamps to; the windows strictly inside
+    have them on all four sides, those on the last row and column on two."""
+    launch, _ = bilinear_listed
+    kinds = set()
+    for j, it in enumerate(launch.items):
+        if it[3] is None or _empty(launch, j):
+            continue
+        x0, y0, ww, wh = it[3]
+        win, full = launch.wins[j], launch.fulls[j]
+        H, W = full.shape[:2]
+        assert x0 > 0 and y0 > 0 and x0 + ww <= W and y0 + wh <= H
+        assert not (win[..., :3] == R.BILINEAR_SURROUND[0]).any()
+        assert it[2] == 3 or not (win[..., 3] == R.BILINEAR_SURROUND[3]).any()
+        s = R.bilinear_samples(launch, j)
+        ok, xi, yi, dx, dy = s["ok"], s["xi"], s["yi"], s["dx"], s["dy"]
+        sides = {"left": 0, "right": 0, "top": 0, "bottom": 0}
+        for ox, oy, wgt in ((0, 0, (1 - dx) * (1 - dy)), (1, 0, dx * (1 - dy)), (0, 1, (1 - dx) * dy), (1, 1, dx * dy)):
+            nx, ny = xi + ox, yi + oy
+            gx, gy = x0 + nx, y0 + ny
+            out = ok & (wgt > 0) & ((nx < 0) | (nx >= ww) | (ny < 0) | (ny >= wh))
+            out &= (gx >= 0) & (gx < W) & (gy >= 0) & (gy < H)
+            used = win[np.clip(ny, 0, wh - 1), np.clip(nx, 0, ww - 1)]
+            there = full[np.clip(gy, 0, H - 1), np.clip(gx, 0, W - 1)]
+            out &= (used != there).any(axis=-1)
+            for name, m in (("left", nx < 0), ("right", nx >= ww), ("top", ny < 0), ("bottom", ny >= wh)):
+                sides[name] += int((out & m).sum())
+        inside = x0 + ww < W and y0 + wh < H
+        want = ("left", "right", "top", "bottom") if inside else ("left", "top")
+        assert all(sides[k] > 0 for k in want), (it, sides)
+        assert inside or (x0 + ww == W and y0 + wh == H)
+        kinds.add((it[2], inside))
+    assert kinds == {(3, True), (4, True), (3, False), (4, False)}
 
 
 # --------------------------------------------------------------------------- rotate / flip gather
