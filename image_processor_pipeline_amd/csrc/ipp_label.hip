@@ -30,6 +30,12 @@
 //   per pair of layers how many pixels the later one covers and hides, from the
 //   same planes; optionally the visible boxes and map with them.
 //
+// The four scene entries share one statement of the visibility rule and of its
+// bounds, and one set of device helpers (the strip step present4 / cover4 /
+// hidden4, MaskBox and commit_row6, the map sweep map_tile / layer_rects /
+// map_sweep, the row and slot-table helpers) and host helpers (ScenePrep,
+// scene_args_ok); the kernels are callers of those.
+//
 // All follow ipp_alpha_bbox's convention (ipp_gather.hip): the boxes are
 // pre-set to (INT_MAX, INT_MAX, -1, -1), every wave that saw a visible pixel
 // issues four device-scope atomics, and a finish kernel turns an untouched row
@@ -223,43 +229,117 @@ k_alpha_bbox_min(const uint8_t* __restrict__ img, const ipp_image_desc* __restri
 }
 
 // ---------------------------------------------------------------------------
-// ipp_pipe_scene_boxes: occlusion-aware labels of scenes (K overlays pasted in
-// layer order onto one composite).
+// Scenes (K overlays pasted in layer order onto one composite): what the four
+// scene entries share.
 //
 // Scratch: the table slot → descriptor (int32[n_scenes·K], slot = scene·K +
 // layer, -1 = no descriptor), then one alpha plane per descriptor, max_ov_h
-// rows of scene_pitch(max_ov_w) bytes.  Three launches in stream order:
-//   k_scene_init   rows (INT_MAX, INT_MAX, -1, -1, 0, 0) and the slot table;
-//   k_scene_alpha  overlay_alpha_band, every alpha byte stored to its plane;
-//   k_scene_visible  one block per (descriptor, 16-row strip of its overlay):
-//     a pixel is present when its alpha >= alpha_min and visible when no later
-//     layer of its scene whose rectangle holds the pixel has alpha >= cover_min
-//     there (read from that layer's plane by composite coordinate); wave-wide
-//     box and counts, six atomics from lane 0;
-// then k_scene_finish turns an untouched box into (-1, -1, -1, -1).
-// A descriptor larger than (max_ov_w, max_ov_h) has no plane: it is skipped
-// and never read as a later layer, so every plane access stays in bounds.
+// rows of scene_pitch(max_ov_w) bytes, which k_scene_alpha fills from
+// overlay_alpha_band (the overlay's rows inside the background).
+//
+// THE RULE.  A pixel of an overlay is PRESENT when its alpha >= alpha_min.  A
+// later layer of its scene COVERS it when that layer's rectangle holds the
+// pixel and its alpha there (read from its plane by composite coordinate) is
+// >= cover_min.  A present pixel no later layer covers is VISIBLE.  present4
+// and cover4 are the rule on the overlay's side (4 pixels of a strip row),
+// map_sweep on the composite's (16 pixels of a map row).
+//
+// THE BOUNDS.  A later layer is read only when its slot entry lies in [0, n)
+// and it has a plane (not ScenePlanes::lacks: not larger than (max_ov_w,
+// max_ov_h); a larger descriptor is skipped and never read), and then only at
+// 0 <= cy < ov_h <= max_ov_h and 0 <= cx < ov_w <= max_ov_w: every access lies
+// in the plane of a descriptor in [0, n).
+//
+// Rows are (x0, y0, x1, y1, area, visible): reset to (INT_MAX, INT_MAX, -1, -1,
+// 0, 0), committed per wave (commit_row6), an untouched box finished to -1s.
 // ---------------------------------------------------------------------------
 __host__ __device__ constexpr int64_t scene_pitch(int max_ov_w) { return ((int64_t)max_ov_w + 15) & ~(int64_t)15; }
 __host__ __device__ constexpr int64_t scene_table_bytes(int64_t slots) { return (4 * slots + 255) & ~(int64_t)255; }
+
+struct ScenePlanes {
+    const uint8_t* base;
+    int64_t pitch, psize;
+    int max_w, max_h;
+    __device__ __forceinline__ bool lacks(const ipp_paste_desc p) const { return p.ov_w > max_w || p.ov_h > max_h; }
+    __device__ __forceinline__ const uint8_t* row(int d, int r) const {
+        return base + (int64_t)d * psize + (int64_t)r * pitch;
+    }
+};
+
+__device__ __forceinline__ ScenePlanes scene_planes(const uint8_t* planes, int max_ov_w, int max_ov_h) {
+    const int64_t pitch = scene_pitch(max_ov_w);
+    return {planes, pitch, (int64_t)max_ov_h * pitch, max_ov_w, max_ov_h};
+}
+
+// (scene, layer) of descriptor i; unmapped = alone in its scene, in no slot.
+struct SceneSlot {
+    int scene, layer;
+    bool mapped;
+};
+
+__device__ __forceinline__ SceneSlot scene_slot(const int32_t* __restrict__ scene_layer, int i, int n_scenes, int K) {
+    const int s = scene_layer[2 * i], k = scene_layer[2 * i + 1];
+    return {s, k, (unsigned)s < (unsigned)n_scenes && (unsigned)k < (unsigned)K};
+}
+
+__device__ __forceinline__ void slot_table_set(int32_t* __restrict__ table, const int32_t* __restrict__ scene_layer,
+                                               int i, int n_scenes, int K) {
+    const SceneSlot at = scene_slot(scene_layer, i, n_scenes, K);
+    if (at.mapped) table[(int64_t)at.scene * K + at.layer] = i;
+}
+
+__device__ __forceinline__ void row6_reset(int32_t* row) {
+    row[0] = INT32_MAX;
+    row[1] = INT32_MAX;
+    row[2] = -1;
+    row[3] = -1;
+    row[4] = 0;
+    row[5] = 0;
+}
+
+__device__ __forceinline__ void row6_finish(int32_t* row) {
+    if (row[2] < 0) row[0] = row[1] = -1;
+}
 
 __global__ void k_scene_init(int32_t* __restrict__ out, int32_t* __restrict__ table,
                              const int32_t* __restrict__ scene_layer, int n, int n_scenes, int K) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    out[6 * i + 0] = INT32_MAX;
-    out[6 * i + 1] = INT32_MAX;
-    out[6 * i + 2] = -1;
-    out[6 * i + 3] = -1;
-    out[6 * i + 4] = 0;
-    out[6 * i + 5] = 0;
-    const int s = scene_layer[2 * i], k = scene_layer[2 * i + 1];
-    if ((unsigned)s < (unsigned)n_scenes && (unsigned)k < (unsigned)K) table[(int64_t)s * K + k] = i;
+    row6_reset(out + 6 * i);
+    slot_table_set(table, scene_layer, i, n_scenes, K);
+}
+
+// The slot table alone, for a launch without rows.
+__global__ void k_scene_table(int32_t* __restrict__ table, const int32_t* __restrict__ scene_layer, int n,
+                              int n_scenes, int K) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) slot_table_set(table, scene_layer, i, n_scenes, K);
 }
 
 __global__ void k_scene_finish(int32_t* out, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n && out[6 * i + 2] < 0) out[6 * i + 0] = out[6 * i + 1] = -1;
+    if (i < n) row6_finish(out + 6 * i);
+}
+
+__global__ void k_amodal_init(int32_t* __restrict__ arows, int32_t* __restrict__ rows, int32_t* __restrict__ table,
+                              const int32_t* __restrict__ scene_layer, int n, int n_scenes, int K) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+#pragma unroll
+    for (int w = 0; w < 6; ++w) {
+        const int32_t v = w < 2 ? INT32_MAX : w < 4 ? -1 : 0;
+        arows[6 * i + w] = v;
+        if (rows) rows[6 * i + w] = v;
+    }
+    const int s = scene_layer[2 * i], k = scene_layer[2 * i + 1];
+    if ((unsigned)s < (unsigned)n_scenes && (unsigned)k < (unsigned)K) table[(int64_t)s * K + k] = i;
+}
+
+__global__ void k_amodal_finish(int32_t* __restrict__ arows, int32_t* __restrict__ rows, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    row6_finish(arows + 6 * i);
+    if (rows) row6_finish(rows + 6 * i);
 }
 
 __global__ void __launch_bounds__(256)
@@ -277,8 +357,105 @@ k_scene_alpha(const uint8_t* __restrict__ tmp, const int32_t* __restrict__ coefs
                        [&](int x, int o, int a) { plane[(int64_t)o * pitch + x] = (uint8_t)a; });
 }
 
-constexpr int SVR = 16;  // overlay rows per k_scene_visible block
+// ---------------------------------------------------------------------------
+// The strip walk (k_scene_visible, k_cull_count, k_amodal_count): one block per
+// (descriptor, SVR-row strip of its overlay), a thread per row and 4 pixels of
+// it per step, u0 = 4·(lane & 15) + 64·step — one aligned dword of the plane
+// (its pitch is a multiple of 16; bytes past ov_w are masked).
+// ---------------------------------------------------------------------------
+constexpr int SVR = 16;  // overlay rows per block
 
+// The present mask of pixels (u0 .. u0+3, v) of overlay p, whose plane row v is `prow`.
+__device__ __forceinline__ uint32_t present4(const uint8_t* __restrict__ prow, int v, int u0, const ipp_paste_desc p,
+                                             int alpha_min) {
+    uint32_t a4 = 0u;
+    if (v < p.ov_h) a4 = *reinterpret_cast<const uint32_t*>(prow + u0);
+    uint32_t present = 0u;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        present |= (uint32_t)(v < p.ov_h && u0 + k < p.ov_w && (int)((a4 >> (8 * k)) & 255u) >= alpha_min) << k;
+    return present;
+}
+
+// Which of the 4 present pixels a layer covers: `qrow` is the row of its plane
+// that holds them, cx0 the first one's column there, ov_w its width.
+__device__ __forceinline__ uint32_t cover4(const uint8_t* __restrict__ qrow, int cx0, int ov_w, uint32_t present,
+                                           int cover_min, uint32_t c = 0u) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int cx = cx0 + k;
+        if (((present >> k) & 1u) && (unsigned)cx < (unsigned)ov_w && (int)qrow[cx] >= cover_min) c |= 1u << k;
+    }
+    return c;
+}
+
+// What the later layers of p's scene hide of its 4 present pixels (u0.., v):
+// the runtime walk over the slots layer+1 .. K-1 (any K; block-uniform), which
+// skips a layer without a descriptor, without a plane, or not `taken(dj)`.
+// (Unlike layer_rects and k_amodal_count's tables, this walk does not test
+// ov_w <= 0 / ov_h <= 0 of a later layer: the planner emits no such descriptor,
+// and the test moves k_scene_visible's and k_cull_count's pinned VGPR counts
+// (20 -> 19, 16 -> 15).  A hand-made descriptor with a negative size is the
+// caller's error here, as it was before the walk was shared.)
+template <typename Taken>
+__device__ __forceinline__ uint32_t hidden4(const ipp_pipe_desc* __restrict__ descs, const int32_t* __restrict__ table,
+                                            const ScenePlanes pl, int n, int K, const SceneSlot at,
+                                            const ipp_paste_desc p, int v, int u0, uint32_t present, int cover_min,
+                                            Taken taken) {
+    uint32_t hidden = 0u;
+    for (int j = at.mapped ? at.layer + 1 : K; j < K; ++j) {
+        const int dj = table[(int64_t)at.scene * K + j];
+        if ((unsigned)dj >= (unsigned)n) continue;
+        const ipp_paste_desc q = descs[dj].p;
+        if (pl.lacks(q) || !taken(dj)) continue;
+        const int cy = p.y + v - q.y;  // the row in layer j's overlay
+        if ((unsigned)cy >= (unsigned)q.ov_h) continue;
+        hidden = cover4(pl.row(dj, cy), p.x + u0 - q.x, q.ov_w, present, cover_min, hidden);
+    }
+    return hidden;
+}
+
+// The box of the set bits of 4-pixel masks, bit k = pixel (x0 + k, y).
+struct MaskBox {
+    int xmin = INT32_MAX, ymin = INT32_MAX, xmax = -1, ymax = -1;
+    __device__ __forceinline__ void add(uint32_t mask, int x0, int y) {
+        if (!mask) return;
+        xmin = min(xmin, x0 + (int)__builtin_ctz(mask));
+        xmax = max(xmax, x0 + 31 - (int)__builtin_clz(mask));
+        ymin = min(ymin, y);
+        ymax = max(ymax, y);
+    }
+};
+
+__device__ __forceinline__ int wave_sum(int v) {
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+// Two counts at once, their shuffles interleaved.
+__device__ __forceinline__ void wave_sum(int& a, int& b) {
+    for (int off = 32; off > 0; off >>= 1) {
+        a += __shfl_xor(a, off);
+        b += __shfl_xor(b, off);
+    }
+}
+
+// Lane 0 adds the wave's two sums (integer atomicAdd: no result depends on the atomics' order).
+__device__ __forceinline__ void lane0_add2(int32_t* a, int va, int32_t* b, int vb) {
+    if ((threadIdx.x & 63) == 0) {
+        if (va) atomicAdd(a, va);
+        if (vb) atomicAdd(b, vb);
+    }
+}
+
+// The wave's box and its (wave-summed) counts into a row: six atomics from lane 0.
+__device__ __forceinline__ void commit_row6(int32_t* __restrict__ row, const MaskBox box, int area, int vis) {
+    bbox_commit(row, box.xmin, box.ymin, box.xmax, box.ymax);
+    lane0_add2(&row[4], area, &row[5], vis);
+}
+
+// ipp_pipe_scene_boxes: per overlay the box of its visible pixels, its present
+// and its visible pixel counts.
 __global__ void __launch_bounds__(256)
 k_scene_visible(const ipp_pipe_desc* __restrict__ descs, const int32_t* __restrict__ scene_layer,
                 const int32_t* __restrict__ table, const uint8_t* __restrict__ planes, FastDiv strips, int n,
@@ -288,66 +465,30 @@ k_scene_visible(const ipp_pipe_desc* __restrict__ descs, const int32_t* __restri
     const int im = (int)fdiv(b, strips);
     const int v0 = (int)(b - (uint32_t)im * strips.d) * SVR;
     const ipp_paste_desc p = descs[im].p;
-    if (v0 >= p.ov_h || p.ov_w > max_ov_w || p.ov_h > max_ov_h) return;  // block-uniform
-    const int64_t pitch = scene_pitch(max_ov_w), psize = (int64_t)max_ov_h * pitch;
-    const uint8_t* plane = planes + (int64_t)im * psize;
-    const int scene = scene_layer[2 * im], layer = scene_layer[2 * im + 1];
-    const bool mapped = (unsigned)scene < (unsigned)n_scenes && (unsigned)layer < (unsigned)K;
+    const ScenePlanes pl = scene_planes(planes, max_ov_w, max_ov_h);
+    if (v0 >= p.ov_h || pl.lacks(p)) return;  // block-uniform
+    const SceneSlot at = scene_slot(scene_layer, im, n_scenes, K);
     const int v = v0 + (int)(threadIdx.x >> 4);
-    int xmin = INT32_MAX, ymin = INT32_MAX, xmax = -1, ymax = -1, area = 0, vis = 0;
-    // 4 pixels of one row per thread and step (one aligned dword of the plane:
-    // its pitch is a multiple of 16, bytes past ov_w are masked below)
+    MaskBox box;
+    int area = 0, vis = 0;
     for (int u0 = 4 * (int)(threadIdx.x & 15); u0 < p.ov_w; u0 += 64) {
-        uint32_t a4 = 0u;
-        if (v < p.ov_h) a4 = *reinterpret_cast<const uint32_t*>(plane + (int64_t)v * pitch + u0);
-        uint32_t present = 0u;
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            present |= (uint32_t)(v < p.ov_h && u0 + k < p.ov_w && (int)((a4 >> (8 * k)) & 255u) >= alpha_min) << k;
-        uint32_t hidden = 0u;
-        // later layers of the scene (the loop is block-uniform)
-        for (int j = mapped ? layer + 1 : K; j < K; ++j) {
-            const int dj = table[(int64_t)scene * K + j];
-            if ((unsigned)dj >= (unsigned)n) continue;
-            const ipp_paste_desc q = descs[dj].p;
-            if (q.ov_w > max_ov_w || q.ov_h > max_ov_h) continue;  // no plane
-            const int cy = p.y + v - q.y;                          // the row in layer j's overlay
-            if ((unsigned)cy >= (unsigned)q.ov_h) continue;
-            const uint8_t* qrow = planes + (int64_t)dj * psize + (int64_t)cy * pitch;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int cx = p.x + u0 + k - q.x;
-                if (((present >> k) & 1u) && (unsigned)cx < (unsigned)q.ov_w && (int)qrow[cx] >= cover_min)
-                    hidden |= 1u << k;
-            }
-        }
-        const uint32_t visible = present & ~hidden;
+        const uint32_t present = present4(pl.row(im, v), v, u0, p, alpha_min);
+        const uint32_t visible = present & ~hidden4(descs, table, pl, n, K, at, p, v, u0, present, cover_min,
+                                                    [](int) { return true; });
         area += __builtin_popcount(present);
         vis += __builtin_popcount(visible);
-        if (visible) {
-            xmin = min(xmin, p.x + u0 + (int)__builtin_ctz(visible));
-            xmax = max(xmax, p.x + u0 + 31 - (int)__builtin_clz(visible));
-            ymin = min(ymin, p.y + v);
-            ymax = max(ymax, p.y + v);
-        }
+        box.add(visible, p.x + u0, p.y + v);
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        area += __shfl_xor(area, off);
-        vis += __shfl_xor(vis, off);
-    }
-    int32_t* row = out + 6 * (int64_t)im;
-    bbox_commit(row, xmin, ymin, xmax, ymax);
-    if ((threadIdx.x & 63) == 0) {
-        if (area) atomicAdd(&row[4], area);
-        if (vis) atomicAdd(&row[5], vis);
-    }
+    wave_sum(area, vis);
+    commit_row6(out + 6 * (int64_t)im, box, area, vis);
 }
 
 // ---------------------------------------------------------------------------
-// ipp_pipe_scene_map: the visibility rule's per-pixel answer (instance masks).
-// Byte (Y, X) of scene s's map holds bit k iff layer k is mapped, has a plane,
-// its rectangle clipped to the background holds (X, Y), A_k >= alpha_min there
-// and no later layer with a plane has A_j >= cover_min there.
+// The map sweep (k_scene_map, k_amodal_map): the rule's per-pixel answer.
+// Byte (Y, X) of scene s's visibility map holds bit k iff layer k is mapped,
+// has a plane, its rectangle clipped to the background holds (X, Y), it is
+// present there and no later layer with a plane covers it; the presence map
+// holds bit k whether covered or not.
 //
 // Composite-centric: a block is MT_H rows × MT_W columns of one scene's map,
 // a thread MT_PX consecutive pixels of one row, stored as one aligned 16-B
@@ -359,126 +500,175 @@ k_scene_visible(const ipp_pipe_desc* __restrict__ descs, const int32_t* __restri
 // misses the wave's rows or the block's columns is not touched: a block no
 // layer meets stores zeros and reads no plane.  Plane bytes are read by
 // composite coordinate with byte loads (cx = X - x_k is unaligned), each
-// guarded by the clipped rectangle: 0 <= cy < ov_h <= max_ov_h and 0 <= cx <
-// ov_w <= max_ov_w, so every access lies in the plane of a descriptor in
-// [0, n), and the rows it reads are the ones k_scene_alpha wrote (the
-// overlay's rows inside the background).
+// guarded by the clipped rectangle (THE BOUNDS above), and the rows it reads
+// are the ones k_scene_alpha wrote.
 // ---------------------------------------------------------------------------
 constexpr int MT_W = 256, MT_H = 16, MT_PX = 16;
 constexpr int kSceneMapMaxLayers = IPP_SCENE_MAP_MAX_LAYERS;
 static_assert(kSceneMapMaxLayers == 8, "one bit per layer in a map byte");
-static_assert(MT_PX == 16 && MT_W == 16 * MT_PX && MT_H * (MT_W / MT_PX) == 256, "k_scene_map's thread map");
+static_assert(MT_PX == 16 && MT_W == 16 * MT_PX && MT_H * (MT_W / MT_PX) == 256, "the map kernels' thread map");
 
-// The slot table alone, for a map without boxes (k_scene_init fills it beside the rows).
-__global__ void k_scene_table(int32_t* __restrict__ table, const int32_t* __restrict__ scene_layer, int n,
-                              int n_scenes, int K) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int s = scene_layer[2 * i], k = scene_layer[2 * i + 1];
-    if ((unsigned)s < (unsigned)n_scenes && (unsigned)k < (unsigned)K) table[(int64_t)s * K + k] = i;
-}
+struct MapTile {
+    int scene;
+    int bx0, wy0;  // the block's first column, the wave's first of 4 rows
+    int X0, Y;     // the thread's first pixel
+};
 
-__global__ void __launch_bounds__(256)
-k_scene_map(const ipp_pipe_desc* __restrict__ descs, const int32_t* __restrict__ table,
-            const uint8_t* __restrict__ planes, FastDiv tiles, FastDiv tiles_x, int n, int K, int bg_w, int bg_h,
-            int max_ov_w, int max_ov_h, int alpha_min, int cover_min, uint8_t* __restrict__ map,
-            int64_t map_pitch) {
+__device__ __forceinline__ MapTile map_tile(FastDiv tiles, FastDiv tiles_x) {
     const uint32_t b = xcd_remap(blockIdx.x, gridDim.x);
     const int scene = (int)fdiv(b, tiles);
     const uint32_t t = b - (uint32_t)scene * tiles.d;
     const int ty = (int)fdiv(t, tiles_x), tx = (int)(t - (uint32_t)ty * tiles_x.d);
-    const int bx0 = tx * MT_W;                                                  // the block's columns
-    const int wy0 = ty * MT_H + 4 * __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // the wave's 4 rows
-    const int Y = ty * MT_H + (int)(threadIdx.x >> 4);
-    const int X0 = bx0 + MT_PX * (int)(threadIdx.x & 15);
-    const int64_t pitch = scene_pitch(max_ov_w), psize = (int64_t)max_ov_h * pitch;
+    const int bx0 = tx * MT_W;
+    return {scene, bx0, ty * MT_H + 4 * __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)),
+            bx0 + MT_PX * (int)(threadIdx.x & 15), ty * MT_H + (int)(threadIdx.x >> 4)};
+}
 
-    // Phase 1 (block-uniform): each layer's descriptor and paste position; d[k]
-    // stays -1 unless the layer's clipped rectangle meets the wave's pixels.
-    int d[kSceneMapMaxLayers], px[kSceneMapMaxLayers], py[kSceneMapMaxLayers], pw[kSceneMapMaxLayers],
-        ph[kSceneMapMaxLayers];
+// Per layer of the scene the descriptor and its paste rectangle; d[k] stays -1
+// unless the layer's clipped rectangle meets the wave's pixels.
+struct LayerRects {
+    int d[kSceneMapMaxLayers], x[kSceneMapMaxLayers], y[kSceneMapMaxLayers], w[kSceneMapMaxLayers],
+        h[kSceneMapMaxLayers];
+};
+
+// Phase 1 (block-uniform).
+__device__ __forceinline__ LayerRects layer_rects(const ipp_pipe_desc* __restrict__ descs,
+                                            const int32_t* __restrict__ table, const ScenePlanes pl,
+                                            const MapTile t, int n, int K, int bg_w, int bg_h) {
+    LayerRects r;
 #pragma unroll
     for (int k = 0; k < kSceneMapMaxLayers; ++k) {
-        d[k] = -1;
-        px[k] = py[k] = pw[k] = ph[k] = 0;
+        r.d[k] = -1;
+        r.x[k] = r.y[k] = r.w[k] = r.h[k] = 0;
         if (k >= K) continue;
-        const int dk = table[(int64_t)scene * K + k];
+        const int dk = table[(int64_t)t.scene * K + k];
         if ((unsigned)dk >= (unsigned)n) continue;  // no descriptor in this slot
         const ipp_paste_desc p = descs[dk].p;
-        if (p.ov_w <= 0 || p.ov_h <= 0 || p.ov_w > max_ov_w || p.ov_h > max_ov_h) continue;  // no plane
+        if (p.ov_w <= 0 || p.ov_h <= 0 || pl.lacks(p)) continue;  // no plane
         // the rectangle clipped to the background (64-bit: x + ov_w of a foreign descriptor must not wrap)
         const int64_t rx0 = max((int64_t)p.x, (int64_t)0), rx1 = min((int64_t)p.x + p.ov_w, (int64_t)bg_w);
         const int64_t ry0 = max((int64_t)p.y, (int64_t)0), ry1 = min((int64_t)p.y + p.ov_h, (int64_t)bg_h);
-        if (rx0 >= (int64_t)bx0 + MT_W || rx1 <= bx0 || ry0 >= (int64_t)wy0 + 4 || ry1 <= wy0) continue;
-        d[k] = dk;
-        px[k] = p.x, py[k] = p.y, pw[k] = p.ov_w, ph[k] = p.ov_h;
+        if (rx0 >= (int64_t)t.bx0 + MT_W || rx1 <= t.bx0 || ry0 >= (int64_t)t.wy0 + 4 || ry1 <= t.wy0) continue;
+        r.d[k] = dk;
+        r.x[k] = p.x, r.y[k] = p.y, r.w[k] = p.ov_w, r.h[k] = p.ov_h;
     }
+    return r;
+}
 
-    if (Y >= bg_h || X0 >= map_pitch) return;  // (no barrier below)
-    uint32_t w[4] = {0u, 0u, 0u, 0u};
+// Phase 2: top down; the visibility words always, with PRESENCE the presence
+// words too, handed to `store`.  The two forms of the bit are the two kernels'
+// own (one select against one combined test): either way bit k of pixel i is
+// set iff a >= alpha_min, in wv only while no later layer has covered it.
+template <bool PRESENCE, typename Store>
+__device__ __forceinline__ void map_sweep(const LayerRects& r, const ScenePlanes pl, const MapTile t, int bg_w,
+                                          int alpha_min, int cover_min, Store store) {
+    uint32_t wa[4] = {0u, 0u, 0u, 0u}, wv[4] = {0u, 0u, 0u, 0u};
     uint32_t covered = 0u;  // bit i: a later layer covers pixel X0 + i
-    // Phase 2: top down.
 #pragma unroll
     for (int k = kSceneMapMaxLayers - 1; k >= 0; --k) {
-        if (d[k] < 0) continue;  // wave-uniform
-        const int cy = Y - py[k];
-        if ((unsigned)cy >= (unsigned)ph[k]) continue;
-        const uint8_t* row = planes + (int64_t)d[k] * psize + (int64_t)cy * pitch;
-        const int cx0 = X0 - px[k];  // (X0 < map_pitch and |x| of a met rectangle are far below 2^31)
-        const int xlim = min(pw[k], bg_w - px[k]);  // columns of the overlay inside the background
+        if (r.d[k] < 0) continue;  // wave-uniform
+        const int cy = t.Y - r.y[k];
+        if ((unsigned)cy >= (unsigned)r.h[k]) continue;
+        const uint8_t* row = pl.row(r.d[k], cy);
+        const int cx0 = t.X0 - r.x[k];  // (X0 < map_pitch and |x| of a met rectangle are far below 2^31)
+        const int xlim = min(r.w[k], bg_w - r.x[k]);  // columns of the overlay inside the background
 #pragma unroll
         for (int i = 0; i < MT_PX; ++i) {
             const int cx = cx0 + i;
             if (cx >= 0 && cx < xlim) {
                 const int a = row[cx];
-                if (!((covered >> i) & 1u) && a >= alpha_min) w[i >> 2] |= (1u << k) << (8 * (i & 3));
+                if constexpr (PRESENCE) {
+                    const uint32_t bit = (a >= alpha_min ? 1u << k : 0u) << (8 * (i & 3));
+                    wa[i >> 2] |= bit;
+                    if (!((covered >> i) & 1u)) wv[i >> 2] |= bit;
+                } else {
+                    if (!((covered >> i) & 1u) && a >= alpha_min) wv[i >> 2] |= (1u << k) << (8 * (i & 3));
+                }
                 if (a >= cover_min) covered |= 1u << i;
             }
         }
     }
-    store16<0>(map + ((int64_t)scene * bg_h + Y) * map_pitch + X0, 16, true, w);
+    store(wa, wv);
 }
 
-// The launches of ipp_pipe_scene_boxes and ipp_pipe_scene_map after their
-// argument checks: the slot table, the alpha planes, then the boxes (`rows`)
-// and / or the map, whichever is given.
+// ipp_pipe_scene_map: one visibility map per composite (instance masks).
+__global__ void __launch_bounds__(256)
+k_scene_map(const ipp_pipe_desc* __restrict__ descs, const int32_t* __restrict__ table,
+            const uint8_t* __restrict__ planes, FastDiv tiles, FastDiv tiles_x, int n, int K, int bg_w, int bg_h,
+            int max_ov_w, int max_ov_h, int alpha_min, int cover_min, uint8_t* __restrict__ map,
+            int64_t map_pitch) {
+    const MapTile t = map_tile(tiles, tiles_x);
+    const ScenePlanes pl = scene_planes(planes, max_ov_w, max_ov_h);
+    const LayerRects r = layer_rects(descs, table, pl, t, n, K, bg_w, bg_h);
+    if (t.Y >= bg_h || t.X0 >= map_pitch) return;  // (no barrier below)
+    map_sweep<false>(r, pl, t, bg_w, alpha_min, cover_min, [&](const uint32_t*, const uint32_t* wv) {
+        store16<0>(map + ((int64_t)t.scene * bg_h + t.Y) * map_pitch + t.X0, 16, true, wv);
+    });
+}
+
+// What the launches of a scene entry share after its argument checks: the grid
+// sizes and their limits, the split of the scratch into slot table and planes,
+// the table's memset, the alpha launch.
+struct ScenePrep {
+    int tyb, strips, ib;  // bands and strips per descriptor, blocks of a thread per descriptor
+    int mtx = 0, mty = 0;  // map tiles
+    int64_t slots;
+    int32_t* table;
+    uint8_t* planes;
+
+    // IPP_OK with the table memset issued, or the code to return.  map_pitch > 0: the launch has a map.
+    int begin(int n_images, int n_scenes, int per_scene, int max_ov_h, uint8_t* scratch, int bg_h, int64_t map_pitch,
+              hipStream_t s) {
+        tyb = paste_max_bands(max_ov_h), strips = (max_ov_h + SVR - 1) / SVR, ib = (n_images + 255) / 256;
+        slots = (int64_t)n_scenes * per_scene;
+        if ((int64_t)tyb * n_images >= INT32_MAX || (int64_t)strips * n_images >= INT32_MAX || slots >= INT32_MAX)
+            return IPP_E_ARG;
+        if (map_pitch > 0) {
+            mtx = (int)((map_pitch + MT_W - 1) / MT_W), mty = (bg_h + MT_H - 1) / MT_H;
+            if ((int64_t)mtx * mty * n_scenes >= INT32_MAX) return IPP_E_ARG;
+        }
+        table = reinterpret_cast<int32_t*>(scratch);
+        planes = scratch + scene_table_bytes(slots);
+        if (slots > 0 && hipMemsetAsync(table, 0xFF, 4 * (size_t)slots, s) != hipSuccess) return IPP_E_LAUNCH;
+        return IPP_OK;
+    }
+
+    void alpha(const uint8_t* tmp, const int32_t* coefs, const ipp_pipe_desc* descs, int n_images, int max_ov_w,
+               int max_ov_h, hipStream_t s) const {
+        hipLaunchKernelGGL(k_scene_alpha, dim3((uint32_t)(tyb * n_images)), dim3(256), 0, s, tmp, coefs, descs,
+                           fast_div((uint32_t)tyb), max_ov_w, max_ov_h, planes);
+    }
+};
+
+// The launches of ipp_pipe_scene_boxes and ipp_pipe_scene_map: k_scene_init
+// (with rows) or k_scene_table, k_scene_alpha, then the boxes (`rows`:
+// k_scene_visible, k_scene_finish) and / or the map, whichever is given.
 int scene_launches(const uint8_t* tmp, const int32_t* coefs, const ipp_pipe_desc* descs, const int32_t* scene_layer,
                    int n_images, int n_scenes, int per_scene, int bg_w, int bg_h, int max_ov_w, int max_ov_h,
                    int alpha_min, int cover_min, uint8_t* scratch, int32_t* rows, uint8_t* map, int64_t map_pitch,
                    hipStream_t s) {
-    const int tyb = paste_max_bands(max_ov_h), strips = (max_ov_h + SVR - 1) / SVR;
-    const int64_t slots = (int64_t)n_scenes * per_scene;
-    if ((int64_t)tyb * n_images >= INT32_MAX || (int64_t)strips * n_images >= INT32_MAX || slots >= INT32_MAX)
-        return IPP_E_ARG;
-    int mtx = 0, mty = 0;
-    if (map) {
-        mtx = (int)((map_pitch + MT_W - 1) / MT_W), mty = (bg_h + MT_H - 1) / MT_H;
-        if ((int64_t)mtx * mty * n_scenes >= INT32_MAX) return IPP_E_ARG;
-    }
-    int32_t* table = reinterpret_cast<int32_t*>(scratch);
-    uint8_t* planes = scratch + scene_table_bytes(slots);
-    if (slots > 0 && hipMemsetAsync(table, 0xFF, 4 * (size_t)slots, s) != hipSuccess) return IPP_E_LAUNCH;
+    ScenePrep sp;
+    if (const int rc = sp.begin(n_images, n_scenes, per_scene, max_ov_h, scratch, bg_h, map ? map_pitch : 0, s))
+        return rc;
     if (n_images > 0) {
-        const int ib = (n_images + 255) / 256;
         if (rows)
-            hipLaunchKernelGGL(k_scene_init, dim3(ib), dim3(256), 0, s, rows, table, scene_layer, n_images, n_scenes,
-                               per_scene);
+            hipLaunchKernelGGL(k_scene_init, dim3(sp.ib), dim3(256), 0, s, rows, sp.table, scene_layer, n_images,
+                               n_scenes, per_scene);
         else
-            hipLaunchKernelGGL(k_scene_table, dim3(ib), dim3(256), 0, s, table, scene_layer, n_images, n_scenes,
+            hipLaunchKernelGGL(k_scene_table, dim3(sp.ib), dim3(256), 0, s, sp.table, scene_layer, n_images, n_scenes,
                                per_scene);
-        hipLaunchKernelGGL(k_scene_alpha, dim3((uint32_t)(tyb * n_images)), dim3(256), 0, s, tmp, coefs, descs,
-                           fast_div((uint32_t)tyb), max_ov_w, max_ov_h, planes);
+        sp.alpha(tmp, coefs, descs, n_images, max_ov_w, max_ov_h, s);
         if (rows) {
-            hipLaunchKernelGGL(k_scene_visible, dim3((uint32_t)(strips * n_images)), dim3(256), 0, s, descs,
-                               scene_layer, table, planes, fast_div((uint32_t)strips), n_images, n_scenes, per_scene,
-                               max_ov_w, max_ov_h, alpha_min, cover_min, rows);
-            hipLaunchKernelGGL(k_scene_finish, dim3(ib), dim3(256), 0, s, rows, n_images);
+            hipLaunchKernelGGL(k_scene_visible, dim3((uint32_t)(sp.strips * n_images)), dim3(256), 0, s, descs,
+                               scene_layer, sp.table, sp.planes, fast_div((uint32_t)sp.strips), n_images, n_scenes,
+                               per_scene, max_ov_w, max_ov_h, alpha_min, cover_min, rows);
+            hipLaunchKernelGGL(k_scene_finish, dim3(sp.ib), dim3(256), 0, s, rows, n_images);
         }
     }
     if (map && n_scenes > 0)
-        hipLaunchKernelGGL(k_scene_map, dim3((uint32_t)(mtx * mty * n_scenes)), dim3(256), 0, s, descs, table, planes,
-                           fast_div((uint32_t)(mtx * mty)), fast_div((uint32_t)mtx), n_images, per_scene, bg_w, bg_h,
-                           max_ov_w, max_ov_h, alpha_min, cover_min, map, map_pitch);
+        hipLaunchKernelGGL(k_scene_map, dim3((uint32_t)(sp.mtx * sp.mty * n_scenes)), dim3(256), 0, s, descs, sp.table,
+                           sp.planes, fast_div((uint32_t)(sp.mtx * sp.mty)), fast_div((uint32_t)sp.mtx), n_images,
+                           per_scene, bg_w, bg_h, max_ov_w, max_ov_h, alpha_min, cover_min, map, map_pitch);
     IPP_CHECK_LAUNCH();
     return IPP_OK;
 }
@@ -518,53 +708,24 @@ k_cull_count(const ipp_pipe_desc* __restrict__ descs, const int32_t* __restrict_
     const uint32_t b = xcd_remap(blockIdx.x, gridDim.x);
     const int im = (int)fdiv(b, strips);
     const int v0 = (int)(b - (uint32_t)im * strips.d) * SVR;
-    const int scene = scene_layer[2 * im], layer = scene_layer[2 * im + 1];
-    const bool mapped = (unsigned)scene < (unsigned)n_scenes && (unsigned)layer < (unsigned)K;
-    if ((mapped ? layer : K - 1) != cur) return;  // another launch's descriptor (block-uniform)
+    const SceneSlot at = scene_slot(scene_layer, im, n_scenes, K);
+    if ((at.mapped ? at.layer : K - 1) != cur) return;  // another launch's descriptor (block-uniform)
     const ipp_paste_desc p = descs[im].p;
-    if (v0 >= p.ov_h || p.ov_w > max_ov_w || p.ov_h > max_ov_h) return;  // block-uniform
-    const int64_t pitch = scene_pitch(max_ov_w), psize = (int64_t)max_ov_h * pitch;
-    const uint8_t* plane = planes + (int64_t)im * psize;
+    const ScenePlanes pl = scene_planes(planes, max_ov_w, max_ov_h);
+    if (v0 >= p.ov_h || pl.lacks(p)) return;  // block-uniform
     const int v = v0 + (int)(threadIdx.x >> 4);
     int area = 0, vis = 0;
-    // 4 pixels of one row per thread and step, as in k_scene_visible
     for (int u0 = 4 * (int)(threadIdx.x & 15); u0 < p.ov_w; u0 += 64) {
-        uint32_t a4 = 0u;
-        if (v < p.ov_h) a4 = *reinterpret_cast<const uint32_t*>(plane + (int64_t)v * pitch + u0);
-        uint32_t present = 0u;
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            present |= (uint32_t)(v < p.ov_h && u0 + k < p.ov_w && (int)((a4 >> (8 * k)) & 255u) >= alpha_min) << k;
-        uint32_t hidden = 0u;
-        // the kept later layers of the scene (the loop is block-uniform)
-        for (int j = mapped ? layer + 1 : K; j < K; ++j) {
-            const int dj = table[(int64_t)scene * K + j];
-            if ((unsigned)dj >= (unsigned)n) continue;
-            const ipp_paste_desc q = descs[dj].p;
-            if (q.ov_w > max_ov_w || q.ov_h > max_ov_h) continue;  // no plane
-            // layer j's counters are final: its launch came earlier in the stream
-            if (!cull_keep(cull[4 * (int64_t)dj + 1], cull[4 * (int64_t)dj + 2], min_q, min_pixels)) continue;
-            const int cy = p.y + v - q.y;  // the row in layer j's overlay
-            if ((unsigned)cy >= (unsigned)q.ov_h) continue;
-            const uint8_t* qrow = planes + (int64_t)dj * psize + (int64_t)cy * pitch;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int cx = p.x + u0 + k - q.x;
-                if (((present >> k) & 1u) && (unsigned)cx < (unsigned)q.ov_w && (int)qrow[cx] >= cover_min)
-                    hidden |= 1u << k;
-            }
-        }
+        const uint32_t present = present4(pl.row(im, v), v, u0, p, alpha_min);
+        // the kept later layers: layer j's counters are final, its launch came earlier in the stream
+        const uint32_t hidden = hidden4(descs, table, pl, n, K, at, p, v, u0, present, cover_min, [&](int dj) {
+            return cull_keep(cull[4 * (int64_t)dj + 1], cull[4 * (int64_t)dj + 2], min_q, min_pixels);
+        });
         area += __builtin_popcount(present);
         vis += __builtin_popcount(present & ~hidden);
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        area += __shfl_xor(area, off);
-        vis += __shfl_xor(vis, off);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        if (area) atomicAdd(&cull[4 * (int64_t)im + 1], area);
-        if (vis) atomicAdd(&cull[4 * (int64_t)im + 2], vis);
-    }
+    wave_sum(area, vis);
+    lane0_add2(&cull[4 * (int64_t)im + 1], area, &cull[4 * (int64_t)im + 2], vis);
 }
 
 constexpr int kCullClearBlocks = 16;  // blocks per descriptor of k_cull_clear, striding over its T groups
@@ -596,23 +757,17 @@ k_cull_clear(uint8_t* __restrict__ tmp, const ipp_pipe_desc* __restrict__ descs,
 int cull_launches(uint8_t* tmp, const int32_t* coefs, const ipp_pipe_desc* descs, const int32_t* scene_layer,
                   int n_images, int n_scenes, int per_scene, int max_ov_w, int max_ov_h, int alpha_min, int cover_min,
                   int min_q, int min_pixels, uint8_t* scratch, int32_t* cull, hipStream_t s) {
-    const int tyb = paste_max_bands(max_ov_h), strips = (max_ov_h + SVR - 1) / SVR;
-    const int64_t slots = (int64_t)n_scenes * per_scene;
-    if ((int64_t)tyb * n_images >= INT32_MAX || (int64_t)strips * n_images >= INT32_MAX || slots >= INT32_MAX ||
-        (int64_t)kCullClearBlocks * n_images >= INT32_MAX)
-        return IPP_E_ARG;
-    int32_t* table = reinterpret_cast<int32_t*>(scratch);
-    uint8_t* planes = scratch + scene_table_bytes(slots);
-    if (slots > 0 && hipMemsetAsync(table, 0xFF, 4 * (size_t)slots, s) != hipSuccess) return IPP_E_LAUNCH;
+    if ((int64_t)kCullClearBlocks * n_images >= INT32_MAX) return IPP_E_ARG;
+    ScenePrep sp;
+    if (const int rc = sp.begin(n_images, n_scenes, per_scene, max_ov_h, scratch, 0, 0, s)) return rc;
     if (hipMemsetAsync(cull, 0, 16 * (size_t)n_images, s) != hipSuccess) return IPP_E_LAUNCH;
-    hipLaunchKernelGGL(k_scene_table, dim3((n_images + 255) / 256), dim3(256), 0, s, table, scene_layer, n_images,
-                       n_scenes, per_scene);
-    hipLaunchKernelGGL(k_scene_alpha, dim3((uint32_t)(tyb * n_images)), dim3(256), 0, s, tmp, coefs, descs,
-                       fast_div((uint32_t)tyb), max_ov_w, max_ov_h, planes);
+    hipLaunchKernelGGL(k_scene_table, dim3(sp.ib), dim3(256), 0, s, sp.table, scene_layer, n_images, n_scenes,
+                       per_scene);
+    sp.alpha(tmp, coefs, descs, n_images, max_ov_w, max_ov_h, s);
     for (int k = per_scene - 1; k >= 0; --k)
-        hipLaunchKernelGGL(k_cull_count, dim3((uint32_t)(strips * n_images)), dim3(256), 0, s, descs, scene_layer, table,
-                           planes, fast_div((uint32_t)strips), n_images, n_scenes, per_scene, k, max_ov_w, max_ov_h,
-                           alpha_min, cover_min, min_q, min_pixels, cull);
+        hipLaunchKernelGGL(k_cull_count, dim3((uint32_t)(sp.strips * n_images)), dim3(256), 0, s, descs, scene_layer,
+                           sp.table, sp.planes, fast_div((uint32_t)sp.strips), n_images, n_scenes, per_scene, k,
+                           max_ov_w, max_ov_h, alpha_min, cover_min, min_q, min_pixels, cull);
     hipLaunchKernelGGL(k_cull_clear, dim3((uint32_t)(kCullClearBlocks * n_images)), dim3(256), 0, s, tmp, descs,
                        max_ov_w, max_ov_h, min_q, min_pixels, cull);
     IPP_CHECK_LAUNCH();
@@ -627,51 +782,22 @@ int cull_launches(uint8_t* tmp, const int32_t* coefs, const ipp_pipe_desc* descs
 //
 // Same scratch, slot table and alpha planes as the boxes.  In stream order:
 //   memsets         the slot table (0xFF) and occ (0);
-//   k_amodal_init   arows and rows (INT_MAX, INT_MAX, -1, -1, 0, 0), the table;
+//   k_amodal_init   arows and rows reset, the table;
 //   k_scene_alpha   once, whatever is asked for;
-//   k_amodal_count  k_scene_visible's blocks and pixel groups (one block per
-//     descriptor and 16-row strip, 4 pixels of a row per thread and step), the
-//     later layers walked from the top down with the per-pixel `hidden` mask:
-//     of layer j, COVERS += popcount(present & cover_j) and HIDES +=
-//     popcount(present & cover_j & ~hidden) before hidden |= cover_j.  Each
-//     count is summed over the wave and added by lane 0 (integer atomicAdd:
-//     no result depends on the atomics' order); the present box and, when
-//     `rows` is given, the visible box go through bbox_commit;
+//   k_amodal_count  the strip walk with per-layer counters: of later layer j,
+//     top down, COVERS += popcount(present & cover_j) and HIDES +=
+//     popcount(present & cover_j & ~hidden) before hidden |= cover_j; the
+//     present box and, when `rows` is given, the visible box (what
+//     k_scene_visible writes);
 //   k_amodal_finish untouched boxes become (-1, -1, -1, -1);
-//   k_amodal_map    k_scene_map's sweep storing the presence and / or the
-//     visibility map: one 16-B vector per thread and map, one writer per byte.
-// Phase 1 of k_amodal_count is block-uniform: a later layer is kept only when
-// it is in [0, n), has a plane and its rectangle meets the strip's rows and the
-// overlay's columns (64-bit, a foreign descriptor must not wrap), so inside
-// the loop 0 <= cy < ov_h <= max_ov_h and 0 <= cx < ov_w <= max_ov_w are the
-// only loads: every access lies in the plane of a descriptor in [0, n).
+//   k_amodal_map    the map sweep storing the presence and / or the visibility
+//     map.
+// Scenes have at most 8 layers here, so k_amodal_count keeps the later layers
+// in unrolled block-uniform tables instead of hidden4's runtime walk: phase 1
+// keeps layer j only when it is in [0, n), has a plane and its rectangle meets
+// the strip's rows and the overlay's columns (64-bit, a foreign descriptor must
+// not wrap), so inside the loop cover4's loads are the only ones (THE BOUNDS).
 // ---------------------------------------------------------------------------
-__global__ void k_amodal_init(int32_t* __restrict__ arows, int32_t* __restrict__ rows, int32_t* __restrict__ table,
-                              const int32_t* __restrict__ scene_layer, int n, int n_scenes, int K) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-#pragma unroll
-    for (int w = 0; w < 6; ++w) {
-        const int32_t v = w < 2 ? INT32_MAX : w < 4 ? -1 : 0;
-        arows[6 * i + w] = v;
-        if (rows) rows[6 * i + w] = v;
-    }
-    const int s = scene_layer[2 * i], k = scene_layer[2 * i + 1];
-    if ((unsigned)s < (unsigned)n_scenes && (unsigned)k < (unsigned)K) table[(int64_t)s * K + k] = i;
-}
-
-__global__ void k_amodal_finish(int32_t* __restrict__ arows, int32_t* __restrict__ rows, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    if (arows[6 * i + 2] < 0) arows[6 * i + 0] = arows[6 * i + 1] = -1;
-    if (rows && rows[6 * i + 2] < 0) rows[6 * i + 0] = rows[6 * i + 1] = -1;
-}
-
-__device__ __forceinline__ int wave_sum(int v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
 __global__ void __launch_bounds__(256)
 k_amodal_count(const ipp_pipe_desc* __restrict__ descs, const int32_t* __restrict__ scene_layer,
                const int32_t* __restrict__ table, const uint8_t* __restrict__ planes, FastDiv strips, int n,
@@ -681,11 +807,11 @@ k_amodal_count(const ipp_pipe_desc* __restrict__ descs, const int32_t* __restric
     const int im = (int)fdiv(b, strips);
     const int v0 = (int)(b - (uint32_t)im * strips.d) * SVR;
     const ipp_paste_desc p = descs[im].p;
-    if (v0 >= p.ov_h || p.ov_w > max_ov_w || p.ov_h > max_ov_h) return;  // block-uniform
-    const int64_t pitch = scene_pitch(max_ov_w), psize = (int64_t)max_ov_h * pitch;
-    const uint8_t* plane = planes + (int64_t)im * psize;
-    const int scene = scene_layer[2 * im], layer = scene_layer[2 * im + 1];
-    const bool mapped = (unsigned)scene < (unsigned)n_scenes && (unsigned)layer < (unsigned)K;
+    const ScenePlanes pl = scene_planes(planes, max_ov_w, max_ov_h);
+    if (v0 >= p.ov_h || pl.lacks(p)) return;  // block-uniform
+    const SceneSlot at = scene_slot(scene_layer, im, n_scenes, K);
+    const int scene = at.scene, layer = at.layer;
+    const bool mapped = at.mapped;
 
     // Phase 1 (block-uniform): the later layers that can cover a pixel of this strip.
     int d[kSceneMapMaxLayers], qx[kSceneMapMaxLayers], qy[kSceneMapMaxLayers], qw[kSceneMapMaxLayers],
@@ -698,7 +824,7 @@ k_amodal_count(const ipp_pipe_desc* __restrict__ descs, const int32_t* __restric
         const int dj = table[(int64_t)scene * K + j];
         if ((unsigned)dj >= (unsigned)n) continue;  // no descriptor in this slot
         const ipp_paste_desc q = descs[dj].p;
-        if (q.ov_w <= 0 || q.ov_h <= 0 || q.ov_w > max_ov_w || q.ov_h > max_ov_h) continue;  // no plane
+        if (q.ov_w <= 0 || q.ov_h <= 0 || pl.lacks(q)) continue;  // no plane
         const int64_t cy0 = (int64_t)p.y + v0 - q.y, cx0 = (int64_t)p.x - q.x;  // of the strip's first pixel
         if (cy0 + SVR <= 0 || cy0 >= q.ov_h || cx0 + p.ov_w <= 0 || cx0 >= q.ov_w) continue;
         d[j] = dj;
@@ -712,14 +838,8 @@ k_amodal_count(const ipp_pipe_desc* __restrict__ descs, const int32_t* __restric
     int cov[kSceneMapMaxLayers], hid[kSceneMapMaxLayers];
 #pragma unroll
     for (int j = 0; j < kSceneMapMaxLayers; ++j) cov[j] = hid[j] = 0;
-    // 4 pixels of one row per thread and step, as in k_scene_visible
     for (int u0 = 4 * (int)(threadIdx.x & 15); u0 < p.ov_w; u0 += 64) {
-        uint32_t a4 = 0u;
-        if (v < p.ov_h) a4 = *reinterpret_cast<const uint32_t*>(plane + (int64_t)v * pitch + u0);
-        uint32_t present = 0u;
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            present |= (uint32_t)(v < p.ov_h && u0 + k < p.ov_w && (int)((a4 >> (8 * k)) & 255u) >= alpha_min) << k;
+        const uint32_t present = present4(pl.row(im, v), v, u0, p, alpha_min);
         uint32_t hidden = 0u;
         // Phase 2: the later layers, top down (layer 0 is nobody's later layer)
 #pragma unroll
@@ -727,15 +847,9 @@ k_amodal_count(const ipp_pipe_desc* __restrict__ descs, const int32_t* __restric
             if (d[j] < 0) continue;  // block-uniform
             const int cy = p.y + v - qy[j];  // the row in layer j's overlay
             uint32_t c = 0u;
-            if ((unsigned)cy < (unsigned)qh[j]) {
-                const uint8_t* qrow = planes + (int64_t)d[j] * psize + (int64_t)cy * pitch;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const int cx = p.x + u0 + k - qx[j];
-                    if (((present >> k) & 1u) && (unsigned)cx < (unsigned)qw[j] && (int)qrow[cx] >= cover_min)
-                        c |= 1u << k;
-                }
-            }
+            if ((unsigned)cy < (unsigned)qh[j])
+                c = cover4(pl.row(d[j], cy), p.x + u0 - qx[j], qw[j], present,
+                           cover_min);
             cov[j] += __builtin_popcount(c);
             hid[j] += __builtin_popcount(c & ~hidden);
             hidden |= c;
@@ -758,137 +872,86 @@ k_amodal_count(const ipp_pipe_desc* __restrict__ descs, const int32_t* __restric
     }
     area = wave_sum(area);
     vis = wave_sum(vis);
-    const bool lane0 = (threadIdx.x & 63) == 0;
     int32_t* arow = arows + 6 * (int64_t)im;
     bbox_commit(arow, axmin, aymin, axmax, aymax);
-    if (lane0) {
-        if (area) atomicAdd(&arow[4], area);
-        if (vis) atomicAdd(&arow[5], vis);
-    }
+    lane0_add2(&arow[4], area, &arow[5], vis);
     if (rows) {  // (uniform) what k_scene_visible writes
         int32_t* row = rows + 6 * (int64_t)im;
         bbox_commit(row, xmin, ymin, xmax, ymax);
-        if (lane0) {
-            if (area) atomicAdd(&row[4], area);
-            if (vis) atomicAdd(&row[5], vis);
-        }
+        lane0_add2(&row[4], area, &row[5], vis);
     }
     if (!mapped) return;  // block-uniform: alone in its scene, in no slot of occ
     int32_t* oc0 = occ + (((int64_t)scene * 2) * K + layer) * K;  // occ[scene][0][layer][.]
     int32_t* oc1 = oc0 + (int64_t)K * K;                          // occ[scene][1][layer][.]
-    if (lane0) {
-        if (area) atomicAdd(&oc0[layer], area);
-        if (vis) atomicAdd(&oc1[layer], vis);
-    }
+    lane0_add2(&oc0[layer], area, &oc1[layer], vis);
 #pragma unroll
     for (int j = 1; j < kSceneMapMaxLayers; ++j) {
         if (d[j] < 0) continue;  // block-uniform
-        const int c = wave_sum(cov[j]), h = wave_sum(hid[j]);
-        if (lane0) {
-            if (c) atomicAdd(&oc0[j], c);
-            if (h) atomicAdd(&oc1[j], h);
-        }
+        lane0_add2(&oc0[j], wave_sum(cov[j]), &oc1[j], wave_sum(hid[j]));
     }
 }
 
-// k_scene_map with two outputs: `amap` takes bit k wherever layer k is present,
-// `vmap` where it is also under no covering later layer (k_scene_map's byte).
-// Either may be null (uniform).  The thread map, the guards of every plane
-// access and the single writer per byte are k_scene_map's.
+// The presence map in `amap`, the visibility map (k_scene_map's) in `vmap`; either may be null (uniform).
 __global__ void __launch_bounds__(256)
 k_amodal_map(const ipp_pipe_desc* __restrict__ descs, const int32_t* __restrict__ table,
              const uint8_t* __restrict__ planes, FastDiv tiles, FastDiv tiles_x, int n, int K, int bg_w, int bg_h,
              int max_ov_w, int max_ov_h, int alpha_min, int cover_min, uint8_t* __restrict__ amap,
              uint8_t* __restrict__ vmap, int64_t map_pitch) {
-    const uint32_t b = xcd_remap(blockIdx.x, gridDim.x);
-    const int scene = (int)fdiv(b, tiles);
-    const uint32_t t = b - (uint32_t)scene * tiles.d;
-    const int ty = (int)fdiv(t, tiles_x), tx = (int)(t - (uint32_t)ty * tiles_x.d);
-    const int bx0 = tx * MT_W;                                                  // the block's columns
-    const int wy0 = ty * MT_H + 4 * __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // the wave's 4 rows
-    const int Y = ty * MT_H + (int)(threadIdx.x >> 4);
-    const int X0 = bx0 + MT_PX * (int)(threadIdx.x & 15);
-    const int64_t pitch = scene_pitch(max_ov_w), psize = (int64_t)max_ov_h * pitch;
-
-    // Phase 1 (block-uniform), as in k_scene_map.
-    int d[kSceneMapMaxLayers], px[kSceneMapMaxLayers], py[kSceneMapMaxLayers], pw[kSceneMapMaxLayers],
-        ph[kSceneMapMaxLayers];
-#pragma unroll
-    for (int k = 0; k < kSceneMapMaxLayers; ++k) {
-        d[k] = -1;
-        px[k] = py[k] = pw[k] = ph[k] = 0;
-        if (k >= K) continue;
-        const int dk = table[(int64_t)scene * K + k];
-        if ((unsigned)dk >= (unsigned)n) continue;  // no descriptor in this slot
-        const ipp_paste_desc p = descs[dk].p;
-        if (p.ov_w <= 0 || p.ov_h <= 0 || p.ov_w > max_ov_w || p.ov_h > max_ov_h) continue;  // no plane
-        const int64_t rx0 = max((int64_t)p.x, (int64_t)0), rx1 = min((int64_t)p.x + p.ov_w, (int64_t)bg_w);
-        const int64_t ry0 = max((int64_t)p.y, (int64_t)0), ry1 = min((int64_t)p.y + p.ov_h, (int64_t)bg_h);
-        if (rx0 >= (int64_t)bx0 + MT_W || rx1 <= bx0 || ry0 >= (int64_t)wy0 + 4 || ry1 <= wy0) continue;
-        d[k] = dk;
-        px[k] = p.x, py[k] = p.y, pw[k] = p.ov_w, ph[k] = p.ov_h;
-    }
-
-    if (Y >= bg_h || X0 >= map_pitch) return;  // (no barrier below)
-    uint32_t wa[4] = {0u, 0u, 0u, 0u}, wv[4] = {0u, 0u, 0u, 0u};
-    uint32_t covered = 0u;  // bit i: a later layer covers pixel X0 + i
-    // Phase 2: top down.
-#pragma unroll
-    for (int k = kSceneMapMaxLayers - 1; k >= 0; --k) {
-        if (d[k] < 0) continue;  // wave-uniform
-        const int cy = Y - py[k];
-        if ((unsigned)cy >= (unsigned)ph[k]) continue;
-        const uint8_t* row = planes + (int64_t)d[k] * psize + (int64_t)cy * pitch;
-        const int cx0 = X0 - px[k];
-        const int xlim = min(pw[k], bg_w - px[k]);  // columns of the overlay inside the background
-#pragma unroll
-        for (int i = 0; i < MT_PX; ++i) {
-            const int cx = cx0 + i;
-            if (cx >= 0 && cx < xlim) {
-                const int a = row[cx];
-                const uint32_t bit = (a >= alpha_min ? 1u << k : 0u) << (8 * (i & 3));
-                wa[i >> 2] |= bit;
-                if (!((covered >> i) & 1u)) wv[i >> 2] |= bit;
-                if (a >= cover_min) covered |= 1u << i;
-            }
-        }
-    }
-    const int64_t at = ((int64_t)scene * bg_h + Y) * map_pitch + X0;
-    if (amap) store16<0>(amap + at, 16, true, wa);
-    if (vmap) store16<0>(vmap + at, 16, true, wv);
+    const MapTile t = map_tile(tiles, tiles_x);
+    const ScenePlanes pl = scene_planes(planes, max_ov_w, max_ov_h);
+    const LayerRects r = layer_rects(descs, table, pl, t, n, K, bg_w, bg_h);
+    if (t.Y >= bg_h || t.X0 >= map_pitch) return;  // (no barrier below)
+    map_sweep<true>(r, pl, t, bg_w, alpha_min, cover_min, [&](const uint32_t* wa, const uint32_t* wv) {
+        const int64_t at = ((int64_t)t.scene * bg_h + t.Y) * map_pitch + t.X0;
+        if (amap) store16<0>(amap + at, 16, true, wa);
+        if (vmap) store16<0>(vmap + at, 16, true, wv);
+    });
 }
 
 int amodal_launches(const uint8_t* tmp, const int32_t* coefs, const ipp_pipe_desc* descs, const int32_t* scene_layer,
                     int n_images, int n_scenes, int per_scene, int bg_w, int bg_h, int max_ov_w, int max_ov_h,
                     int alpha_min, int cover_min, uint8_t* scratch, int32_t* arows, int32_t* occ, uint8_t* amap,
                     int32_t* rows, uint8_t* vmap, int64_t map_pitch, hipStream_t s) {
-    const int tyb = paste_max_bands(max_ov_h), strips = (max_ov_h + SVR - 1) / SVR;
-    const int64_t slots = (int64_t)n_scenes * per_scene;
-    const int mtx = (int)((map_pitch + MT_W - 1) / MT_W), mty = (bg_h + MT_H - 1) / MT_H;
-    if ((int64_t)tyb * n_images >= INT32_MAX || (int64_t)strips * n_images >= INT32_MAX || slots >= INT32_MAX ||
-        (int64_t)mtx * mty * n_scenes >= INT32_MAX)
-        return IPP_E_ARG;
-    int32_t* table = reinterpret_cast<int32_t*>(scratch);
-    uint8_t* planes = scratch + scene_table_bytes(slots);
-    if (slots > 0 && hipMemsetAsync(table, 0xFF, 4 * (size_t)slots, s) != hipSuccess) return IPP_E_LAUNCH;
-    if (slots > 0 && hipMemsetAsync(occ, 0, 8 * (size_t)slots * per_scene, s) != hipSuccess) return IPP_E_LAUNCH;
+    ScenePrep sp;
+    if (const int rc = sp.begin(n_images, n_scenes, per_scene, max_ov_h, scratch, bg_h, map_pitch, s)) return rc;
+    if (sp.slots > 0 && hipMemsetAsync(occ, 0, 8 * (size_t)sp.slots * per_scene, s) != hipSuccess)
+        return IPP_E_LAUNCH;
     if (n_images > 0) {
-        const int ib = (n_images + 255) / 256;
-        hipLaunchKernelGGL(k_amodal_init, dim3(ib), dim3(256), 0, s, arows, rows, table, scene_layer, n_images,
+        hipLaunchKernelGGL(k_amodal_init, dim3(sp.ib), dim3(256), 0, s, arows, rows, sp.table, scene_layer, n_images,
                            n_scenes, per_scene);
-        hipLaunchKernelGGL(k_scene_alpha, dim3((uint32_t)(tyb * n_images)), dim3(256), 0, s, tmp, coefs, descs,
-                           fast_div((uint32_t)tyb), max_ov_w, max_ov_h, planes);
-        hipLaunchKernelGGL(k_amodal_count, dim3((uint32_t)(strips * n_images)), dim3(256), 0, s, descs, scene_layer,
-                           table, planes, fast_div((uint32_t)strips), n_images, n_scenes, per_scene, max_ov_w,
+        sp.alpha(tmp, coefs, descs, n_images, max_ov_w, max_ov_h, s);
+        hipLaunchKernelGGL(k_amodal_count, dim3((uint32_t)(sp.strips * n_images)), dim3(256), 0, s, descs, scene_layer,
+                           sp.table, sp.planes, fast_div((uint32_t)sp.strips), n_images, n_scenes, per_scene, max_ov_w,
                            max_ov_h, alpha_min, cover_min, arows, occ, rows);
-        hipLaunchKernelGGL(k_amodal_finish, dim3(ib), dim3(256), 0, s, arows, rows, n_images);
+        hipLaunchKernelGGL(k_amodal_finish, dim3(sp.ib), dim3(256), 0, s, arows, rows, n_images);
     }
     if ((amap || vmap) && n_scenes > 0)
-        hipLaunchKernelGGL(k_amodal_map, dim3((uint32_t)(mtx * mty * n_scenes)), dim3(256), 0, s, descs, table,
-                           planes, fast_div((uint32_t)(mtx * mty)), fast_div((uint32_t)mtx), n_images, per_scene, bg_w,
-                           bg_h, max_ov_w, max_ov_h, alpha_min, cover_min, amap, vmap, map_pitch);
+        hipLaunchKernelGGL(k_amodal_map, dim3((uint32_t)(sp.mtx * sp.mty * n_scenes)), dim3(256), 0, s, descs, sp.table,
+                           sp.planes, fast_div((uint32_t)(sp.mtx * sp.mty)), fast_div((uint32_t)sp.mtx), n_images,
+                           per_scene, bg_w, bg_h, max_ov_w, max_ov_h, alpha_min, cover_min, amap, vmap, map_pitch);
     IPP_CHECK_LAUNCH();
     return IPP_OK;
+}
+
+// The checks common to the four scene entries.
+bool scene_args_ok(const void* tmp, const void* coefs, const void* descs, const void* scene_layer, const void* scratch,
+                   int n_images, int n_scenes, int per_scene, int max_ov_w, int max_ov_h, int alpha_min, int cover_min,
+                   int tap_format) {
+    return alpha_min >= 1 && alpha_min <= 255 && cover_min >= 1 && cover_min <= 255 && tap_format == IPP_TAPS_MFMA &&
+           tmp && coefs && descs && scene_layer && scratch && n_images >= 0 && n_scenes >= 0 && per_scene >= 1 &&
+           max_ov_w > 0 && max_ov_h > 0;
+}
+
+// Those of the two entries with maps: one bit per layer, the background, the maps' pitch.
+bool scene_map_args_ok(int per_scene, int bg_w, int bg_h, int64_t map_pitch) {
+    return per_scene <= IPP_SCENE_MAP_MAX_LAYERS && bg_w > 0 && bg_h > 0 && map_pitch >= bg_w &&
+           (map_pitch & 15) == 0 && map_pitch <= INT32_MAX;
+}
+
+// The planes are read by dwords, the maps and T are written by 16-B vectors.
+bool aligned16(const void* a, const void* b = nullptr, const void* c = nullptr) {
+    const uintptr_t bits = reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c);
+    return (bits & 15u) == 0;
 }
 
 }  // namespace
@@ -899,16 +962,9 @@ extern "C" int ipp_pipe_scene_amodal(const uint8_t* tmp, const int32_t* coefs, c
                                      int32_t max_ov_h, int32_t alpha_min, int32_t cover_min, int32_t tap_format,
                                      uint8_t* scratch, int32_t* arows, int32_t* occ, uint8_t* amap, int32_t* rows,
                                      uint8_t* vmap, int64_t map_pitch, void* stream) {
-    if (alpha_min < 1 || alpha_min > 255 || cover_min < 1 || cover_min > 255 || tap_format != IPP_TAPS_MFMA)
-        return IPP_E_ARG;
-    if (!tmp || !coefs || !descs || !scene_layer || !scratch || !arows || !occ || n_images < 0 || n_scenes < 0 ||
-        per_scene < 1 || per_scene > IPP_SCENE_MAP_MAX_LAYERS || max_ov_w <= 0 || max_ov_h <= 0)
-        return IPP_E_ARG;
-    if (bg_w <= 0 || bg_h <= 0 || map_pitch < bg_w || (map_pitch & 15) != 0 || map_pitch > INT32_MAX)
-        return IPP_E_ARG;
-    // the planes are read by dwords, the maps are stored by 16-B vectors
-    if (((reinterpret_cast<uintptr_t>(scratch) | reinterpret_cast<uintptr_t>(amap) |
-          reinterpret_cast<uintptr_t>(vmap)) & 15u) != 0)
+    if (!scene_args_ok(tmp, coefs, descs, scene_layer, scratch, n_images, n_scenes, per_scene, max_ov_w, max_ov_h,
+                       alpha_min, cover_min, tap_format) ||
+        !scene_map_args_ok(per_scene, bg_w, bg_h, map_pitch) || !arows || !occ || !aligned16(scratch, amap, vmap))
         return IPP_E_ARG;
     return amodal_launches(tmp, coefs, descs, scene_layer, n_images, n_scenes, per_scene, bg_w, bg_h, max_ov_w,
                            max_ov_h, alpha_min, cover_min, scratch, arows, occ, amap, rows, vmap, map_pitch,
@@ -972,12 +1028,10 @@ extern "C" int ipp_pipe_scene_boxes(const uint8_t* tmp, const int32_t* coefs, co
                                     int32_t per_scene, int32_t max_ov_w, int32_t max_ov_h, int32_t alpha_min,
                                     int32_t cover_min, int32_t tap_format, uint8_t* scratch, int32_t* out,
                                     void* stream) {
-    if (alpha_min < 1 || alpha_min > 255 || cover_min < 1 || cover_min > 255 || tap_format != IPP_TAPS_MFMA)
+    if (!scene_args_ok(tmp, coefs, descs, scene_layer, scratch, n_images, n_scenes, per_scene, max_ov_w, max_ov_h,
+                       alpha_min, cover_min, tap_format) ||
+        !out || !aligned16(scratch))
         return IPP_E_ARG;
-    if (!tmp || !coefs || !descs || !scene_layer || !scratch || !out || n_images < 0 || n_scenes < 0 ||
-        per_scene < 1 || max_ov_w <= 0 || max_ov_h <= 0)
-        return IPP_E_ARG;
-    if ((reinterpret_cast<uintptr_t>(scratch) & 15u) != 0) return IPP_E_ARG;  // the planes are read by dwords
     if (n_images == 0) return IPP_OK;
     return scene_launches(tmp, coefs, descs, scene_layer, n_images, n_scenes, per_scene, 0, 0, max_ov_w, max_ov_h,
                           alpha_min, cover_min, scratch, out, nullptr, 0, (hipStream_t)stream);
@@ -988,15 +1042,10 @@ extern "C" int ipp_pipe_scene_map(const uint8_t* tmp, const int32_t* coefs, cons
                                   int32_t bg_w, int32_t bg_h, int32_t max_ov_w, int32_t max_ov_h, int32_t alpha_min,
                                   int32_t cover_min, int32_t tap_format, uint8_t* scratch, int32_t* rows,
                                   uint8_t* map, int64_t map_pitch, void* stream) {
-    if (alpha_min < 1 || alpha_min > 255 || cover_min < 1 || cover_min > 255 || tap_format != IPP_TAPS_MFMA)
+    if (!scene_args_ok(tmp, coefs, descs, scene_layer, scratch, n_images, n_scenes, per_scene, max_ov_w, max_ov_h,
+                       alpha_min, cover_min, tap_format) ||
+        !scene_map_args_ok(per_scene, bg_w, bg_h, map_pitch) || !map || !aligned16(scratch, map))
         return IPP_E_ARG;
-    if (!tmp || !coefs || !descs || !scene_layer || !scratch || !map || n_images < 0 || n_scenes < 0 ||
-        per_scene < 1 || per_scene > IPP_SCENE_MAP_MAX_LAYERS || max_ov_w <= 0 || max_ov_h <= 0)
-        return IPP_E_ARG;
-    if (bg_w <= 0 || bg_h <= 0 || map_pitch < bg_w || (map_pitch & 15) != 0 || map_pitch > INT32_MAX)
-        return IPP_E_ARG;
-    // the planes are read by dwords, the map is stored by 16-B vectors
-    if (((reinterpret_cast<uintptr_t>(scratch) | reinterpret_cast<uintptr_t>(map)) & 15u) != 0) return IPP_E_ARG;
     return scene_launches(tmp, coefs, descs, scene_layer, n_images, n_scenes, per_scene, bg_w, bg_h, max_ov_w,
                           max_ov_h, alpha_min, cover_min, scratch, rows, map, map_pitch, (hipStream_t)stream);
 }
@@ -1006,14 +1055,10 @@ extern "C" int ipp_pipe_scene_cull(uint8_t* tmp, const int32_t* coefs, const ipp
                                    int32_t max_ov_w, int32_t max_ov_h, int32_t alpha_min, int32_t cover_min,
                                    int32_t min_q, int32_t min_pixels, int32_t tap_format, uint8_t* scratch,
                                    int32_t* cull, void* stream) {
-    if (alpha_min < 1 || alpha_min > 255 || cover_min < 1 || cover_min > 255 || tap_format != IPP_TAPS_MFMA)
+    if (!scene_args_ok(tmp, coefs, descs, scene_layer, scratch, n_images, n_scenes, per_scene, max_ov_w, max_ov_h,
+                       alpha_min, cover_min, tap_format) ||
+        min_q < 0 || min_q > 65536 || min_pixels < 0 || !cull || !aligned16(scratch, tmp))
         return IPP_E_ARG;
-    if (min_q < 0 || min_q > 65536 || min_pixels < 0) return IPP_E_ARG;
-    if (!tmp || !coefs || !descs || !scene_layer || !scratch || !cull || n_images < 0 || n_scenes < 0 ||
-        per_scene < 1 || max_ov_w <= 0 || max_ov_h <= 0)
-        return IPP_E_ARG;
-    // the planes are read by dwords, T is cleared by 16-B vectors
-    if (((reinterpret_cast<uintptr_t>(scratch) | reinterpret_cast<uintptr_t>(tmp)) & 15u) != 0) return IPP_E_ARG;
     if (n_images == 0) return IPP_OK;
     return cull_launches(tmp, coefs, descs, scene_layer, n_images, n_scenes, per_scene, max_ov_w, max_ov_h, alpha_min,
                          cover_min, min_q, min_pixels, scratch, cull, (hipStream_t)stream);

@@ -222,10 +222,9 @@ class SceneRunner(_Runner):
     def _launch_cull(self, caller: str, alpha_min: int, cover_min: int, min_q: int, min_pixels: int) -> torch.Tensor:
         """ipp_pipe_scene_cull between the H and the V launches: the device records, 4 int32 per descriptor."""
         self._scene_scratch(caller)
-        p, S, K = self.plan.pipe, self.plan.n_scenes, self.plan.per_scene
+        p = self.plan.pipe
         rec = torch.empty(4 * len(self.plan.descs), dtype=torch.int32, device=self.device)
-        N.check(self.lib.ipp_pipe_scene_cull(self.tmp.data_ptr(), self.coefs.data_ptr(), self._dptr(0),
-                                             self._scene_layer.data_ptr(), S * K, S, K, p.max_ov_w, p.max_ov_h,
+        N.check(self.lib.ipp_pipe_scene_cull(*self._scene_head(), p.max_ov_w, p.max_ov_h,
                                              alpha_min, cover_min, min_q, min_pixels, p.tap_format,
                                              self._scratch.data_ptr(), rec.data_ptr(), _stream(self.device)),
                 "ipp_pipe_scene_cull")
@@ -286,17 +285,21 @@ class SceneRunner(_Runner):
             self._scratch = torch.empty(nb, dtype=torch.uint8, device=self.device)
             self._scene_layer = _to_dev(self.plan.scene_layer, self.device)
 
+    def _scene_head(self) -> tuple:
+        """The arguments every scene entry begins with: (tmp, coefs, descs, scene_layer, S·K, S, K)."""
+        S, K = self.plan.n_scenes, self.plan.per_scene
+        return (self.tmp.data_ptr(), self.coefs.data_ptr(), self._dptr(0), self._scene_layer.data_ptr(), S * K, S, K)
+
     def _rows(self) -> torch.Tensor:   # of one label or map launch: 6 int32 per descriptor
         return torch.empty(6 * len(self.plan.descs), dtype=torch.int32, device=self.device)
 
     def _launch_boxes(self, alpha_min: int, cover_min: int) -> torch.Tensor:
         self._scene_scratch("scene_boxes")
-        p, S, K = self.plan.pipe, self.plan.n_scenes, self.plan.per_scene
+        p = self.plan.pipe
         rows = self._rows()
-        N.check(self.lib.ipp_pipe_scene_boxes(self.tmp.data_ptr(), self.coefs.data_ptr(), self._dptr(0),
-                                              self._scene_layer.data_ptr(), S * K, S, K, p.max_ov_w, p.max_ov_h,
-                                              alpha_min, cover_min, p.tap_format, self._scratch.data_ptr(),
-                                              rows.data_ptr(), _stream(self.device)), "ipp_pipe_scene_boxes")
+        N.check(self.lib.ipp_pipe_scene_boxes(*self._scene_head(), p.max_ov_w, p.max_ov_h, alpha_min, cover_min,
+                                              p.tap_format, self._scratch.data_ptr(), rows.data_ptr(),
+                                              _stream(self.device)), "ipp_pipe_scene_boxes")
         return rows
 
     def _check_map(self, caller: str, out: Optional[torch.Tensor]) -> None:
@@ -320,12 +323,11 @@ class SceneRunner(_Runner):
         """One ipp_pipe_scene_map call: the (S, bg_h, pitch) map buffer and, with
         ``with_boxes``, the device rows in descriptor order."""
         self._scene_scratch(caller)
-        p, S, K = self.plan.pipe, self.plan.n_scenes, self.plan.per_scene
+        p, S = self.plan.pipe, self.plan.n_scenes
         pitch = scene_map_pitch(p.bg_w)
         buf = out if out is not None else torch.empty((S, p.bg_h, pitch), dtype=torch.uint8, device=self.device)
         rows = self._rows() if with_boxes else None
-        N.check(self.lib.ipp_pipe_scene_map(self.tmp.data_ptr(), self.coefs.data_ptr(), self._dptr(0),
-                                            self._scene_layer.data_ptr(), S * K, S, K, p.bg_w, p.bg_h, p.max_ov_w,
+        N.check(self.lib.ipp_pipe_scene_map(*self._scene_head(), p.bg_w, p.bg_h, p.max_ov_w,
                                             p.max_ov_h, alpha_min, cover_min, p.tap_format, self._scratch.data_ptr(),
                                             rows.data_ptr() if with_boxes else None, buf.data_ptr(), pitch,
                                             _stream(self.device)), "ipp_pipe_scene_map")
@@ -608,8 +610,7 @@ class SceneRunner(_Runner):
         arows, occ = self._rows(), torch.empty((S, 2, K, K), dtype=torch.int32, device=self.device)
         abuf = new_map() if amap else None
         rows, vbuf = (self._rows(), new_map()) if visible else (None, None)
-        N.check(self.lib.ipp_pipe_scene_amodal(self.tmp.data_ptr(), self.coefs.data_ptr(), self._dptr(0),
-                                               self._scene_layer.data_ptr(), S * K, S, K, p.bg_w, p.bg_h,
+        N.check(self.lib.ipp_pipe_scene_amodal(*self._scene_head(), p.bg_w, p.bg_h,
                                                p.max_ov_w, p.max_ov_h, alpha_min, cover_min, p.tap_format,
                                                self._scratch.data_ptr(), arows.data_ptr(), occ.data_ptr(),
                                                abuf.data_ptr() if amap else None,

@@ -116,6 +116,21 @@ def test_run_labelled_matches_the_reference_rows(noise):
     assert labels == exp and len(labels) == 4
 
 
+@pytest.mark.parametrize("alpha_min,cover_min", [(1, 128), (255, 1)])
+def test_nine_layers_walk_past_the_eighth(fused, alpha_min, cover_min):
+    """k_scene_visible's later-layer walk is a runtime loop over any K: a scene
+    of 9 layers, where layer 8 (the ninth) hides pixels of the layers below."""
+    from tests import scene_mask_refs as MR
+    sc = Scenes(fused, *MR.layered_scene(fused, 9))
+    exp = sc.rows(alpha_min, cover_min)
+    # the reference alone: without layer 8's alpha, some lower layer shows more
+    bare = [o.copy() for o in sc.overlays]
+    bare[8][..., 3] = 0
+    without = SR.scene_rows(sc.plan, bare, alpha_min, cover_min)
+    assert (without[0, :8, 5] > exp[0, :8, 5]).any()
+    sc.check_rows(alpha_min, cover_min)
+
+
 # --- 9: odd width, the ungrouped path --------------------------------------------------
 def test_odd_background_width(fused):
     """Backgrounds, margins, scales and sources of test_gpu_labels.test_odd_background_width."""
@@ -247,6 +262,41 @@ def test_guards(fused, noise):
     for kw in (dict(alpha_min=0), dict(cover_min=256), dict(cover_min=1.5)):
         with pytest.raises(ValueError):
             noise.runner.scene_boxes(**kw)
+
+
+def test_c_entry_with_an_unmapped_and_an_oversized_descriptor(noise):
+    """ipp_pipe_scene_boxes itself: a descriptor whose scene index is out of
+    range is labelled alone (nothing hides it, it hides nobody), one larger than
+    (max_ov_w, max_ov_h) keeps its reset row and hides nobody; the others are
+    scene_rows without those two."""
+    from image_processor_pipeline_amd import _native as N
+    lib, r, p, plan = N.load(), noise.runner, noise.plan.pipe, noise.plan
+    n, mw, alone = len(plan.descs), p.max_ov_w - 1, 1                          # item 1 = scene 0, layer 1
+    widest = [i for i, ov in enumerate(noise.overlays) if ov.shape[1] > mw]
+    assert widest and all(i % 3 > 0 for i in widest) and alone not in widest   # later layers of their scenes
+    sl = plan.scene_layer.copy()
+    sl[plan.desc_item.tolist().index(alone)] = (4, 1)                          # 4 scenes: no such scene
+    nb = lib.ipp_pipe_scene_scratch_bytes(n, 4, 3, mw, p.max_ov_h)
+    scratch = torch.full((nb,), 0xA5, dtype=torch.uint8, device=DEV)
+    rows = torch.full((6 * n,), 99, dtype=torch.int32, device=DEV)
+    N.check(lib.ipp_pipe_scene_boxes(r.tmp.data_ptr(), r.coefs.data_ptr(), r.descs.data_ptr(), _t(sl).data_ptr(), n,
+                                     4, 3, mw, p.max_ov_h, 1, 128, p.tap_format, scratch.data_ptr(), rows.data_ptr(),
+                                     torch.cuda.current_stream().cuda_stream), "ipp_pipe_scene_boxes")
+    got = np.empty((n, 6), np.int32)
+    got[plan.desc_item] = rows.cpu().numpy().reshape(n, 6)
+    got = got.reshape(4, 3, 6)
+    # the reference: the two absent from every scene (transparent), then the lone one by itself
+    full, free = noise.rows(1, 128), noise.rows(1, 128, occlusion=False)
+    rest = [ov.copy() for ov in noise.overlays]
+    for i in widest + [alone]:
+        rest[i][..., 3] = 0
+    exp = SR.scene_rows(plan, rest, 1, 128)
+    exp[alone // 3, alone % 3] = free[alone // 3, alone % 3]
+    for i in widest + [alone]:                                                 # each was hidden and did hide
+        s, k = divmod(i, 3)
+        assert full[s, k, 5] < full[s, k, 4] and (exp[s, :k, 5] > full[s, :k, 5]).any()
+        assert exp[s, k].tolist() == ([-1, -1, -1, -1, 0, 0] if i in widest else free[s, k].tolist())
+    assert np.array_equal(got, exp), (got.tolist(), exp.tolist())
 
 
 def test_c_entry_points_refuse_bad_arguments(fused, noise):
