@@ -7,6 +7,8 @@
 //     normalize_coeffs_8bpc for the LANCZOS filter (support 3, sinc·sinc/3,
 //     double precision, the same libm sin()), PRECISION_BITS = 22 — the taps
 //     behind overlays.py:129.
+//   * ipp_plan_resample: the same for BOX, BILINEAR, HAMMING, BICUBIC and
+//     LANCZOS — the taps of Image.resize behind ipp_scene_feed_resize.
 //   * ipp_plan_opaque_bbox: the getbbox() of rotations.py:99 for an opaque
 //     source, solved per canvas row from the 16.16 affine map with exact
 //     integer inequalities (no canvas is materialised).
@@ -121,6 +123,83 @@ extern "C" int64_t ipp_plan_lanczos(int32_t in_size, double in0, double in1, int
         lanczos_one(in_size, fin0, scale, support, ss, xx, ksize, k.data(), kk + (int64_t)xx * ksize, xmin, cnt);
         bounds[2 * xx] = xmin;
         bounds[2 * xx + 1] = cnt;
+    }
+    return ksize;
+}
+
+namespace {
+// Resample.c's other filter functions, term for term.
+inline double box_filter(double x) { return (x > -0.5 && x <= 0.5) ? 1.0 : 0.0; }
+
+inline double bilinear_filter(double x) {
+    if (x < 0.0) x = -x;
+    return x < 1.0 ? 1.0 - x : 0.0;
+}
+
+inline double hamming_filter(double x) {
+    if (x < 0.0) x = -x;
+    if (x == 0.0) return 1.0;
+    if (x >= 1.0) return 0.0;
+    x = x * M_PI;
+    return sin(x) / x * (0.54f + 0.46f * cos(x));  // float literals, widened: as in Resample.c
+}
+
+inline double bicubic_filter(double x) {
+    const double a = -0.5;
+    if (x < 0.0) x = -x;
+    if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
+    if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
+    return 0.0;
+}
+
+struct ResampleFilter {
+    double (*f)(double);
+    double support;
+};
+const ResampleFilter kResampleFilters[5] = {
+    {box_filter, 0.5}, {bilinear_filter, 1.0}, {hamming_filter, 1.0}, {bicubic_filter, 2.0}, {lanczos_filter, 3.0}};
+}  // namespace
+
+// precompute_coeffs + normalize_coeffs_8bpc as in ipp_plan_lanczos, with the
+// filter and its support looked up.
+extern "C" int64_t ipp_plan_resample(int32_t filter, int32_t in_size, double in0, double in1, int32_t out_size,
+                                     int32_t* out, int64_t out_capacity) {
+    if (filter < 0 || filter > 4 || in_size <= 0 || out_size <= 0) return IPP_E_ARG;
+    const ResampleFilter& flt = kResampleFilters[filter];
+    const float fin0 = (float)in0, fin1 = (float)in1;  // Resample.c takes float box[4]
+    const double scale = (double)(fin1 - fin0) / out_size;
+    const double filterscale = scale < 1.0 ? 1.0 : scale;
+    const double support = flt.support * filterscale;
+    const int ksize = (int)ceil(support) * 2 + 1;
+    const int64_t need = 2 * (int64_t)out_size + (int64_t)out_size * ksize;
+    if (out == nullptr) return -need;
+    if (out_capacity < need) return IPP_E_ARG;
+    int32_t* bounds = out;
+    int32_t* kk = out + 2 * (int64_t)out_size;
+    std::vector<double> k(ksize);
+    const double ss = 1.0 / filterscale;
+    for (int xx = 0; xx < out_size; ++xx) {
+        const double center = fin0 + (xx + 0.5) * scale;
+        double ww = 0.0;
+        int xmin = (int)(center - support + 0.5);
+        if (xmin < 0) xmin = 0;
+        int xmax = (int)(center + support + 0.5);
+        if (xmax > in_size) xmax = in_size;
+        xmax -= xmin;
+        for (int x = 0; x < xmax; ++x) {
+            const double w = flt.f((x + xmin - center + 0.5) * ss);
+            k[x] = w;
+            ww += w;
+        }
+        for (int x = 0; x < xmax; ++x)
+            if (ww != 0.0) k[x] /= ww;
+        int32_t* kq = kk + (int64_t)xx * ksize;
+        for (int x = 0; x < ksize; ++x) {
+            const double v = x < xmax ? k[x] : 0.0;
+            kq[x] = v < 0 ? (int32_t)(-0.5 + v * (1 << 22)) : (int32_t)(0.5 + v * (1 << 22));
+        }
+        bounds[2 * xx] = xmin;
+        bounds[2 * xx + 1] = xmax;
     }
     return ksize;
 }

@@ -228,6 +228,41 @@ def lanczos_taps(in_size: int, out_size: int) -> Tuple[int, np.ndarray]:
     return int(k), buf
 
 
+def resample_taps(resample: str, in_size: int, out_size: int) -> Tuple[int, np.ndarray]:
+    """``lanczos_taps`` for any of Pillow's five convolution filters (``_native.IPP_RESAMPLE``'s
+    names): (ksize, int32[2*out + out*ksize]) of ipp_plan_resample."""
+    if resample not in N.IPP_RESAMPLE:
+        raise ValueError(f"resample {resample!r}: one of {', '.join(N.IPP_RESAMPLE)}")
+    lib, code = N.load(), N.IPP_RESAMPLE[resample]
+    need = -lib.ipp_plan_resample(code, in_size, 0.0, float(in_size), out_size, None, 0)
+    if need <= 0:
+        raise ValueError(f"invalid resize {in_size}->{out_size}")
+    buf = np.empty(need, np.int32)
+    k = lib.ipp_plan_resample(code, in_size, 0.0, float(in_size), out_size, N.np_ptr(buf), need)
+    N.check(0 if k > 0 else int(k), "ipp_plan_resample")
+    return int(k), buf
+
+
+def nearest_table(in_size: int, out_size: int) -> np.ndarray:
+    """The source index of every output of Pillow's NEAREST resize of one axis
+    (Geometry.c ImagingScaleAffine, as in ``_scale_affine_plan``): int(o) with o
+    starting at 0.5·(in / out) and advanced by repeated addition of in / out in
+    double.  An index the accumulated rounding pushes to in_size is dropped by
+    Pillow (the pixel keeps the blank image's 0); no full-axis resize gets
+    there, and it raises here instead of being sampled."""
+    if in_size < 1 or out_size < 1:
+        raise ValueError(f"invalid resize {in_size}->{out_size}")
+    step = in_size / out_size
+    o = 0.0 + step * 0.5
+    out = np.empty(out_size, np.int32)
+    for i in range(out_size):
+        out[i] = int(o)
+        o += step
+    if int(out.max()) >= in_size:
+        raise ValueError(f"resize {in_size}->{out_size}: NEAREST index {int(out.max())} beyond the axis")
+    return out
+
+
 def identity_taps(n: int) -> Tuple[int, np.ndarray]:
     """Taps that reproduce the input exactly: (2^21 + p·2^22) >> 22 = p."""
     buf = np.empty(3 * n, np.int32)

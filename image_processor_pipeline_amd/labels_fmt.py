@@ -11,7 +11,7 @@ writes the COCO annotations of ``SceneRunner.scene_rles``' run-length encodings,
 / ``rle_counts_from_string`` are the COCO API's compressed ``counts`` string and ``rle_decode``
 reads a mask back; ``scene_amodal_annotations`` writes the amodal ones (full and visible mask, occluders)
 of ``SceneRunner.scene_amodal_rles``.  ``feed_lut`` tabulates the normalisation of ``SceneRunner.feed``'s
-images.  ``fused`` re-exports it all.
+images and ``FEED_RESAMPLE`` names the filters of its ``size``.  ``fused`` re-exports it all.
 """
 from __future__ import annotations
 
@@ -108,6 +108,11 @@ def min_visible_q(min_visible) -> int:
     if not 0.0 <= v <= 1.0:     # (NaN fails both comparisons)
         raise ValueError(f"min_visible {min_visible!r}: a real number in 0..1 expected")
     return int(math.ceil(v * 65536.0))
+
+
+# The filters of ``SceneRunner.feed(size=..., resample=...)``: Pillow's five convolution filters, by the names of
+# ``PIL.Image.Resampling`` in lower case, in the order of ipp_plan_resample's codes (ipp.h IPP_RESAMPLE_*).
+FEED_RESAMPLE = ("box", "bilinear", "hamming", "bicubic", "lanczos")
 
 
 def feed_lut(mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0), dtype=None, scale: float = 1.0 / 255.0):

@@ -16,7 +16,8 @@ rule hides: each overlay's full box and mask behind its occluders and the
 pairwise occlusion counts (``scene_amodal_rles``, ``scene_amodal_polygons``,
 ``run_labelled(amodal=True)``).  ``feed`` / ``run_feed`` leave a training
 batch on the device instead — normalised planar images, a targets tensor, an
-instance-index map — with no copy back.  labels_fmt.py formats the lines,
+instance-index map — with no copy back, at the composites' size or, with
+``size``, resized on the device exactly as Pillow would.  labels_fmt.py formats the lines,
 masks and annotations; every public name here is also reachable as ``fused.X``.
 """
 from __future__ import annotations
@@ -28,11 +29,12 @@ import numpy as np
 import torch
 
 from . import _native as N
+from . import geometry as G
 from .device import _stream, _to_dev, exclusive_offsets
 from .device import check_alpha_min as _check_alpha_min
 from .fused import (ItemParams, PipeConfig, PipePlan, _launch_hpass_bgcopy, _launch_vblend_bands, _Runner,
                     draw_params, plan_pipe)
-from .labels_fmt import (feed_lut, min_visible_q, scene_amodal_annotations, scene_coco_annotations,
+from .labels_fmt import (FEED_RESAMPLE, feed_lut, min_visible_q, scene_amodal_annotations, scene_coco_annotations,
                          scene_contour_capacity, scene_labels, scene_map_pitch, scene_obb_labels, scene_seg_labels,
                          simplify_tolerance)
 
@@ -143,11 +145,11 @@ def _check_level(name: str, v) -> int:
 
 class SceneFeed(NamedTuple):
     """What ``SceneRunner.feed`` leaves on the device (include/ipp.h states the rules)."""
-    images: torch.Tensor                 # (S, 3, bg_h, bg_w) of the table's dtype
+    images: torch.Tensor                 # (S, 3, bg_h, bg_w) of the table's dtype; (S, 3, out_h, out_w) with size
     targets: torch.Tensor                # (S·K, 6) float32 (scene, class, cx, cy, w, h); unused rows all -1
     count: torch.Tensor                  # (1,) int32: the rows in use
     slot: torch.Tensor                   # (S, K) int32: each overlay's row of targets, or -1
-    index_map: Optional[torch.Tensor]    # (S, bg_h, bg_w) uint8, or None
+    index_map: Optional[torch.Tensor]    # (S, bg_h, bg_w) uint8 ((S, out_h, out_w) with size), or None
 
 
 _FEED_DTYPES = (torch.float16, torch.bfloat16, torch.float32)
@@ -813,7 +815,7 @@ class SceneRunner(_Runner):
     def feed(self, out: torch.Tensor, lut: Optional[torch.Tensor] = None, mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0),
              dtype: torch.dtype = torch.float16, bgr: bool = False, class_ids=0, alpha_min: int = 1,
              cover_min: int = 128, min_visible: float = 0.0, index_map: bool = False,
-             images: Optional[torch.Tensor] = None) -> SceneFeed:
+             images: Optional[torch.Tensor] = None, size=None, resample: str = "bilinear") -> SceneFeed:
         """The training batch of the composites `out` of the last ``run``, left
         on the device (include/ipp.h: ipp_scene_feed_images, _targets,
         _index_map): a ``SceneFeed`` of
@@ -844,14 +846,64 @@ class SceneRunner(_Runner):
         nothing synchronises; the table and the class ids are uploaded once per
         distinct argument and kept on the runner.  ``images`` supplies the
         output (contiguous, on the device, of the table's dtype and the shape
-        above; every element is written)."""
+        above; every element is written).
+
+        ``size`` = (out_h, out_w), or one int for a square, gives the batch at
+        the network's input size (include/ipp.h: ipp_scene_feed_resize,
+        ipp_scene_feed_index_map_sampled): every composite is resized on the
+        device exactly as Pillow's ``Image.resize((out_w, out_h), F)`` resizes
+        it, F = ``resample``, one of ``FEED_RESAMPLE`` (box, bilinear, hamming,
+        bicubic, lanczos) — the horizontal pass first, rounded and clipped to
+        uint8, then the vertical one — and the table is applied to the result;
+        ``images`` is (S, 3, out_h, out_w).  A plain stretch leaves normalised
+        boxes as they are: targets, count and slot are those of ``size=None``
+        bit for bit.  ``index_map`` is (S, out_h, out_w), Pillow's NEAREST
+        resize of the full-size one.  The taps are built and uploaded once per
+        (size, resample), the NEAREST tables once per size and only when an
+        ``index_map`` is asked for; both stay on the runner for its lifetime
+        (a few tens of KB per distinct size, never evicted: a loop that draws
+        a new size per batch keeps one entry per size it has seen).  A
+        filter window above ``IPP_FEED_RESIZE_MAX_KSIZE`` source pixels (a
+        reduction beyond 21x for lanczos, 63x for bilinear) is a ValueError."""
         if not self._hpass_done:
             raise ValueError("SceneRunner.feed: no run has filled the composites and the scratch on this runner")
         return self._feed_launch(*self._feed_args("feed", out, lut, mean, std, dtype, bgr, class_ids, alpha_min,
-                                                  cover_min, min_visible, index_map, images))
+                                                  cover_min, min_visible, index_map, images, size, resample))
+
+    def _feed_resize(self, who: str, size, resample, index_map: bool):
+        """(out_h, out_w, ksize_x, ksize_y, taps_x, taps_y, xtab, ytab) of ``feed(size=...)``: the device taps of
+        one (size, resample) and, with `index_map` only (None otherwise), the NEAREST tables of the size, each built
+        and uploaded once.  ValueError for what the entries would refuse."""
+        if isinstance(size, (int, np.integer)) and not isinstance(size, (bool, np.bool_)):
+            size = (size, size)
+        ok = isinstance(size, (tuple, list)) and len(size) == 2 and all(
+            isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)) and v >= 1 for v in size)
+        if not ok or int(size[0]) * int(size[1]) >= 1 << 28:
+            raise ValueError(f"{who}: size {size!r}: (out_h, out_w) or one int, each >= 1, out_h*out_w < 2^28")
+        if not isinstance(resample, str) or resample not in FEED_RESAMPLE:
+            raise ValueError(f"{who}: resample {resample!r}: one of {', '.join(FEED_RESAMPLE)}")
+        oh, ow = int(size[0]), int(size[1])
+        key, near = ("resize", oh, ow, resample), ("nearest", oh, ow)
+        p = self.plan.pipe
+        if key not in self._feed_cache:
+            if p.bg_w * p.bg_h >= 1 << 28:
+                raise ValueError(f"{who}: a {p.bg_w}x{p.bg_h} background: bg_w*bg_h must stay below 2^28")
+            axes = []
+            for n_in, n_out, name in ((p.bg_w, ow, "width"), (p.bg_h, oh, "height")):
+                k, taps = G.identity_taps(n_in) if n_in == n_out else G.resample_taps(resample, n_in, n_out)
+                if k > N.IPP_FEED_RESIZE_MAX_KSIZE:
+                    raise ValueError(f"{who}: {resample} {n_in}->{n_out} ({name}) takes windows of {k} source pixels, "
+                                     f"IPP_FEED_RESIZE_MAX_KSIZE is {N.IPP_FEED_RESIZE_MAX_KSIZE}")
+                axes.append((k, taps))
+            dev = [_to_dev(taps, self.device).view(torch.int32) for _, taps in axes]
+            self._feed_cache[key] = (oh, ow, axes[0][0], axes[1][0], *dev)
+        if index_map and near not in self._feed_cache:
+            self._feed_cache[near] = tuple(_to_dev(G.nearest_table(n_in, n_out), self.device).view(torch.int32)
+                                           for n_in, n_out in ((p.bg_w, ow), (p.bg_h, oh)))
+        return self._feed_cache[key] + (self._feed_cache[near] if index_map else (None, None))
 
     def _feed_args(self, caller: str, out, lut, mean, std, dtype, bgr, class_ids, alpha_min, cover_min, min_visible,
-                   index_map, images):
+                   index_map, images, size=None, resample="bilinear"):
         """Everything ``feed`` refuses with ValueError, before any launch, and the uploads: the arguments of
         ``_feed_launch``."""
         who = f"SceneRunner.{caller}"
@@ -879,17 +931,19 @@ class SceneRunner(_Runner):
             self._feed_cache = {}
         table = self._feed_lut(lut, mean, std, dtype)
         classes = self._feed_classes(class_ids)
-        shape = (S, 3, p.bg_h, p.bg_w)
+        resize = None if size is None else self._feed_resize(who, size, resample, bool(index_map))
+        shape = (S, 3, p.bg_h, p.bg_w) if resize is None else (S, 3, resize[0], resize[1])
         if images is None:
             images = torch.empty(shape, dtype=table.dtype, device=self.device)
         elif not on_device(images) or images.dtype != table.dtype or tuple(images.shape) != shape or \
                 not images.is_contiguous():
             raise ValueError(f"{who}: images must be a contiguous {table.dtype} tensor {shape} on {self.device}")
-        return caller, out, table, bool(bgr), classes, alpha_min, cover_min, min_q, bool(index_map), images
+        return caller, out, table, bool(bgr), classes, alpha_min, cover_min, min_q, bool(index_map), images, resize
 
     def _feed_launch(self, caller: str, out, table, bgr: bool, classes, alpha_min: int, cover_min: int, min_q: int,
-                     index_map: bool, images) -> SceneFeed:
-        """The launches of ``feed``: the box or the map launch, then the two or three feed entries."""
+                     index_map: bool, images, resize=None) -> SceneFeed:
+        """The launches of ``feed``: the box or the map launch, then the two or three feed entries (with `resize`,
+        ``_feed_resize``'s tables, the resizing ones)."""
         p, S, K = self.plan.pipe, self.plan.n_scenes, self.plan.per_scene
         st, lib = _stream(self.device), self.lib
         buf = None
@@ -897,8 +951,14 @@ class SceneRunner(_Runner):
             buf, rows = self._launch_map(caller, alpha_min, cover_min, True, None)
         else:
             rows = self._launch_boxes(alpha_min, cover_min)
-        N.check(lib.ipp_scene_feed_images(out.data_ptr(), images.data_ptr(), table.data_ptr(), S, p.bg_w, p.bg_h,
-                                          table.element_size(), int(bgr), st), "ipp_scene_feed_images")
+        if resize is None:
+            N.check(lib.ipp_scene_feed_images(out.data_ptr(), images.data_ptr(), table.data_ptr(), S, p.bg_w, p.bg_h,
+                                              table.element_size(), int(bgr), st), "ipp_scene_feed_images")
+        else:
+            oh, ow, kx, ky, taps_x, taps_y, xtab, ytab = resize
+            N.check(lib.ipp_scene_feed_resize(out.data_ptr(), images.data_ptr(), table.data_ptr(), taps_x.data_ptr(),
+                                              taps_y.data_ptr(), S, p.bg_w, p.bg_h, ow, oh, kx, ky,
+                                              table.element_size(), int(bgr), st), "ipp_scene_feed_resize")
         targets = torch.empty((S * K, 6), dtype=torch.float32, device=self.device)
         count = torch.empty(1, dtype=torch.int32, device=self.device)
         slot = torch.empty((S, K), dtype=torch.int32, device=self.device)
@@ -907,18 +967,25 @@ class SceneRunner(_Runner):
                                            p.bg_h, min_q, targets.data_ptr(), count.data_ptr(), slot.data_ptr(), st),
                 "ipp_scene_feed_targets")
         idx = None
-        if index_map:
+        if index_map and resize is None:
             ibuf = torch.empty_like(buf)
             N.check(lib.ipp_scene_feed_index_map(buf.data_ptr(), buf.shape[2], p.bg_w, p.bg_h, slot.data_ptr(), S, K,
                                                  ibuf.data_ptr(), st), "ipp_scene_feed_index_map")
             idx = ibuf[:, :, :p.bg_w]
+        elif index_map:
+            ibuf = torch.empty((S, oh, (ow + 15) // 16 * 16), dtype=torch.uint8, device=self.device)
+            N.check(lib.ipp_scene_feed_index_map_sampled(buf.data_ptr(), buf.shape[2], p.bg_w, p.bg_h, slot.data_ptr(),
+                                                         S, K, xtab.data_ptr(), ytab.data_ptr(), ow, oh,
+                                                         ibuf.data_ptr(), ibuf.shape[2], st),
+                    "ipp_scene_feed_index_map_sampled")
+            idx = ibuf[:, :, :ow]
         return SceneFeed(images, targets, count, slot, idx)
 
     def run_feed(self, src: torch.Tensor, bgs: torch.Tensor, out: torch.Tensor, lut: Optional[torch.Tensor] = None,
                  mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0), dtype: torch.dtype = torch.float16, bgr: bool = False,
                  class_ids=0, alpha_min: int = 1, cover_min: int = 128, min_visible: float = 0.0,
                  index_map: bool = False, images: Optional[torch.Tensor] = None, cull: bool = False,
-                 min_pixels: int = 1) -> SceneFeed:
+                 min_pixels: int = 1, size=None, resample: str = "bilinear") -> SceneFeed:
         """``run`` followed by ``feed`` (same arguments), all on the current
         stream and without a copy back.  With ``cull`` the run is
         ``run_culled``'s — the H launches, ipp_pipe_scene_cull with
@@ -933,7 +1000,7 @@ class SceneRunner(_Runner):
             min_q, min_pixels = self._check_cull("run_feed", min_visible, min_pixels)
         self._check("run_feed", src, bgs, out)
         args = self._feed_args("run_feed", out, lut, mean, std, dtype, bgr, class_ids, alpha_min, cover_min,
-                               min_visible, index_map, images)
+                               min_visible, index_map, images, size, resample)
         self._launch_h(src, bgs, out)
         if cull:
             self._launch_cull("run_feed", args[5], args[6], min_q, min_pixels)

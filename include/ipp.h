@@ -861,6 +861,82 @@ int ipp_scene_feed_targets(const int32_t* rows, const int32_t* scene_layer,
 int ipp_scene_feed_index_map(const uint8_t* map, int64_t map_pitch, int32_t bg_w, int32_t bg_h,
                              const int32_t* slot, int32_t n_scenes, int32_t per_scene, uint8_t* out,
                              void* stream);
+/* The same batch at the network's input size: the composites resized on the
+ * device exactly as Pillow's Image.resize((out_w, out_h), filter) resizes an
+ * RGB image (Resample.c, 8 bits per channel), then the table.
+ *
+ * ipp_scene_feed_resize: in, lut, elem_size, bgr as for ipp_scene_feed_images;
+ * out = n_scenes x 3 x out_h x out_w contiguous elements.  taps_x, taps_y:
+ * device int32 tables of ipp_plan_resample for (bg_w -> out_w) and (bg_h ->
+ * out_h) with ksize_x and ksize_y, or geometry.identity_taps (ksize 1) for an
+ * axis whose sizes are equal (Pillow skips that pass; the identity taps
+ * reproduce the input).  With (xmin, n) = the bounds of an output and k its taps:
+ *   H FIRST:  t[y][xo][c] = clip8((2^21 + sum_k in[s][y][xmin + k][c] * kx[xo][k]) >> 22),
+ *             stored as uint8: rounded and clipped BEFORE the vertical pass;
+ *   THEN V:   r[yo][xo][c] = clip8((2^21 + sum_k t[ymin + k][xo][c] * ky[yo][k]) >> 22);
+ *   THEN THE TABLE: out[s][c][yo][xo] = lut[c][ r[yo][xo][ch(c)] ], ch(c) = c, or
+ *             2 - c with bgr = 1; the table's words are copied as opaque words.
+ * clip8(v) = min(max(v, 0), 255) with an arithmetic shift; the sums are int32
+ * as in Pillow.  No float arithmetic runs on the device.
+ * One workgroup of 256 threads per (scene, tile of tw x th outputs).  The
+ * table, the tile's bounds and taps, the source span of the tile's windows
+ * (fetched in aligned dwords; a scene's slot and a row may start at any byte)
+ * and the uint8 intermediate live in LDS; a wave stores 64 consecutive
+ * elements of one plane row.  The LDS extents follow from (bg, out, ksize,
+ * elem_size) alone: a run of n outputs touches fewer than (n - 1)·in/out +
+ * ksize + 1 source positions.  The tile is 64 x 32, each side halved (the one
+ * whose halving leaves fewer bytes, the height on a tie) until the extents fit
+ * IPP_FEED_RESIZE_LDS_BYTES = 64 KiB, so that two workgroups share a CU's LDS.
+ * ipp_scene_feed_resize_lds returns those bytes and the tile (tile[0] = tw,
+ * tile[1] = th; tile may be NULL).  It is host code and needs no device: it
+ * exists for planning (what a geometry will cost before any launch) and for
+ * testing (the extents are dynamic LDS, which a kernel's metadata does not
+ * show; tests/test_feed_resize_cpu.py sweeps them through it); no launch needs
+ * a call to it.
+ * IPP_FEED_RESIZE_MAX_KSIZE = 128 is the largest ksize of either axis: up to it
+ * even the 1 x 1 tile of the most reducing filter fits the budget (a ksize_y x
+ * ksize_x span at 129 x 392 B, 57 KiB in all).  LANCZOS reaches it at a 21x
+ * reduction, BILINEAR at 63x.  A larger ksize is refused, never truncated.
+ * Every window is clamped to its axis and to the staged span, so whatever the
+ * tables hold no byte outside the n_scenes·bg_h·bg_w·3 of `in` is read and none
+ * outside `out` written (tables that are not ipp_plan_resample's give pixels
+ * this rule does not state).
+ * IPP_E_ARG, before any launch: a NULL pointer; n_scenes, bg_w, bg_h, out_w or
+ * out_h < 1; elem_size other than 2 or 4; bgr other than 0 or 1; out or lut not
+ * aligned to elem_size, taps_x or taps_y not 4-B aligned; ksize_x or ksize_y
+ * outside 1..IPP_FEED_RESIZE_MAX_KSIZE; bg_w·bg_h or out_w·out_h >= 2^28;
+ * n_scenes·tiles >= 2^31 - 1 (the grid).  ipp_scene_feed_resize_lds returns
+ * IPP_E_ARG for the same sizes.
+ *
+ * ipp_scene_feed_index_map_sampled: ipp_scene_feed_index_map at the output
+ * size, as Pillow's NEAREST resize of the full-size index map (Geometry.c
+ * ImagingScaleAffine): xtab = device int32[out_w] with xtab[x] = int(o), o
+ * starting at 0.5·(bg_w / out_w) and advanced by REPEATED ADDITION of bg_w /
+ * out_w in double; ytab alike (geometry.nearest_table).  With f the per-scene
+ * rule of ipp_scene_feed_index_map:
+ *   out[s][y][x] = f(map[s][ytab[y]][xtab[x]])   for x < out_w,
+ * in n_scenes slots of out_h rows of out_pitch bytes; columns [out_w,
+ * out_pitch) are 0 and every byte of all slots is written.  The map is read at
+ * the sampled positions only (coordinates are clamped into it).
+ * IPP_E_ARG, before any launch: a NULL pointer; out not 16-B, slot, xtab or
+ * ytab not 4-B aligned; n_scenes, bg_w, bg_h, out_w or out_h < 1; per_scene
+ * outside 1..IPP_SCENE_MAP_MAX_LAYERS; map_pitch < bg_w or >= 2^31; out_pitch <
+ * out_w, not a multiple of 16 or >= 2^31; bg_h·map_pitch >= 2^32; out_h·
+ * out_pitch >= 2^32; n_scenes·⌈out_h·out_pitch / 16384⌉ >= 2^31 - 1. */
+#define IPP_FEED_RESIZE_MAX_KSIZE 128
+#define IPP_FEED_RESIZE_LDS_BYTES 65536
+int ipp_scene_feed_resize(const uint8_t* in, void* out, const void* lut, const int32_t* taps_x,
+                          const int32_t* taps_y, int32_t n_scenes, int32_t bg_w, int32_t bg_h,
+                          int32_t out_w, int32_t out_h, int32_t ksize_x, int32_t ksize_y,
+                          int32_t elem_size, int32_t bgr, void* stream);
+int64_t ipp_scene_feed_resize_lds(int32_t bg_w, int32_t bg_h, int32_t out_w, int32_t out_h,
+                                  int32_t ksize_x, int32_t ksize_y, int32_t elem_size,
+                                  int32_t* tile /* may be NULL */);
+int ipp_scene_feed_index_map_sampled(const uint8_t* map, int64_t map_pitch, int32_t bg_w,
+                                     int32_t bg_h, const int32_t* slot, int32_t n_scenes,
+                                     int32_t per_scene, const int32_t* xtab, const int32_t* ytab,
+                                     int32_t out_w, int32_t out_h, uint8_t* out, int64_t out_pitch,
+                                     void* stream);
 
 /* ------------------------------------------------------------------------ */
 /* K10-K13: pixels_isolés.keep_largest_component                             */
@@ -933,6 +1009,24 @@ int ipp_alpha_bbox_min(const uint8_t* img, const ipp_image_desc* descs, int32_t 
  * int32 count when out == NULL (as -count), or IPP_E_ARG. */
 int64_t ipp_plan_lanczos(int32_t in_size, double in0, double in1, int32_t out_size,
                          int32_t* out, int64_t out_capacity);
+/* The same for any of Pillow's five convolution filters (Resample.c's filter
+ * functions and supports): `filter` is an IPP_RESAMPLE_* code, the layout and
+ * the return convention are ipp_plan_lanczos', and ksize = 2·⌈support·max((in1
+ * - in0) / out_size, 1)⌉ + 1.  IPP_RESAMPLE_LANCZOS returns exactly what
+ * ipp_plan_lanczos returns.  An unknown filter is IPP_E_ARG.
+ *   BOX       1 on (-0.5, 0.5], support 0.5
+ *   BILINEAR  1 - |x|, support 1
+ *   HAMMING   sinc(x)·(0.54 + 0.46·cos(pi·x)), support 1 (the two constants are
+ *             float literals in Resample.c and are widened from float here too)
+ *   BICUBIC   a = -0.5, support 2
+ *   LANCZOS   sinc(x)·sinc(x / 3), support 3 */
+#define IPP_RESAMPLE_BOX 0
+#define IPP_RESAMPLE_BILINEAR 1
+#define IPP_RESAMPLE_HAMMING 2
+#define IPP_RESAMPLE_BICUBIC 3
+#define IPP_RESAMPLE_LANCZOS 4
+int64_t ipp_plan_resample(int32_t filter, int32_t in_size, double in0, double in1,
+                          int32_t out_size, int32_t* out, int64_t out_capacity);
 /* Batch form: n axes (in_sizes[i] → out_sizes[i], box = full axis), each
  * written at int32 offset offsets[i] of `out`; n_threads ≤ 0 = all cores. */
 int ipp_plan_lanczos_batch(int32_t n, const int32_t* in_sizes, const int32_t* out_sizes,
