@@ -277,7 +277,19 @@ typedef struct ipp_pipe_desc {
  * steps; ipp_plan_mfma_nk_bound(in, out, ksize) ≤ 8, i.e. LANCZOS downscales
  * of at most ≈ 23×; fused.plan_pipe refuses plans beyond it).  A violating
  * tile sets bit 0 of the sticky status read by ipp_pipe_status; its T columns
- * are then wrong. */
+ * are then wrong.
+ * What ipp_pipe_vblend_bands (and _bands_trim, ipp_pipe_vblend_over) reads of
+ * an ipp_pipe_desc: v.src_off and v.src_pitch (the item's T in tmp, 16-B
+ * aligned, pitch a multiple of 16 and ≥ 16·p.ov_w), v.out_len and v.coef_off
+ * (its V tap tiles, phase p.y mod 16), h.lines (the item's T rows: loaded by
+ * every launch, used with a trim table only, so the descriptor's h part must
+ * be mapped) and all of p (ov_off and ov_pitch unused); nothing of g, nothing
+ * else of h and v.  The bg_w / bg_h arguments bound the launch (max_ov_w ≤
+ * bg_w, bands per item); each item's own p.bg_w / p.bg_h size its composite.
+ * T is allocated for t_groups(rows, nkb) row groups per item
+ * (csrc/ipp_pipe_layout.h): its rows past h.lines may hold anything (they
+ * are read, but every tap there is zero), and so may the padding of its pitch
+ * (never read).  tests/test_gpu_vblend_direct.py relies on exactly this. */
 int ipp_pipe_hpass_bgcopy(const uint8_t* src, uint8_t* tmp, const int32_t* coefs,
                           const ipp_pipe_desc* descs, int32_t n_images,
                           int32_t max_out_w, int32_t max_rows, int32_t src_cn,
