@@ -186,12 +186,9 @@ SIGNATURES = {
     "ipp_plan_lanczos": (_L, [_I, _D, _D, _I, _P, _L]),
     "ipp_plan_resample": (_L, [_I, _I, _D, _D, _I, _P, _L]),
     "ipp_plan_lanczos_ksize": (_I, [_D, _D, _I]),
-    "ipp_plan_lanczos_batch": (_I, [_I, _P, _P, _P, _P, _L, _I]),
     "ipp_plan_opaque_bbox": (_I, [_I, _I, _P, _I, _I, _P]),
     "ipp_plan_mfma_size": (_L, [_I, _I, _I]),
-    "ipp_plan_mfma_from_taps": (_I, [_I, _I, _I, _P, _I, _I, _P]),
     "ipp_plan_mfma_nk_bound": (_I, [_I, _I, _I]),
-    "ipp_plan_pipe_axes": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _I]),
     "ipp_stream_copy": (_I, [_P, _P, _L, _P]),
     "ipp_enhance_lsum": (_I, [_P, _P, _I, _L, _P, _P]),
     "ipp_enhance_color": (_I, [_P, _P, _P, _I, _L, _P, _P, _P]),

@@ -38,8 +38,8 @@
 //   2^21 + Σ p·k = bias + Σ_p 2^(8p) acc_p   exactly.
 // Layout per axis (int32 units from coef_off): hdr[4T], bias[16T], blocks (4
 // int32 each); dense block (s, p) of a tile is block boff + (3s + p)·64 + lane.
-// ipp_plan_mfma_from_taps packs the tiles (boff running); the device planner
-// and ipp_plan_mfma_tile give every tile nkb K-step slots: boff = t·nkb·192.
+// Both writers, the device planner and the host's ipp_plan_mfma_tile, give
+// every tile nkb K-step slots: boff = t·nkb·192.
 //
 // Compact tile (hdr.w = 1; axis->compact, nK >= 2 and at most 64 nonzero
 // 16-column groups over the tile's 16 outputs): the tile's first 4 blocks

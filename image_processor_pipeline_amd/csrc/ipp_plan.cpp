@@ -30,6 +30,7 @@
 
 #include "ipp.h"
 #include "ipp_pipe_layout.h"
+#include "ipp_resample_plan.h"
 
 using namespace pipe_layout;
 
@@ -393,25 +394,6 @@ int overlay_size(int32_t ov_w, int32_t ov_h, int32_t bg_w, int32_t bg_h, double 
     return E_OK;
 }
 
-// Pillow Resample.c bounds of output xx (precompute_coeffs, in0 = 0).
-struct AxisBounds {
-    double scale, support;
-    int32_t in;
-    AxisBounds(int32_t in_, int32_t out) : in(in_) {
-        scale = (double)((float)in_) / out;
-        const double fs = scale < 1.0 ? 1.0 : scale;
-        support = 3.0 * fs;
-    }
-    void at(int xx, int& xmin, int& cnt) const {
-        const double center = 0.0 + (xx + 0.5) * scale;
-        xmin = (int)(center - support + 0.5);
-        if (xmin < 0) xmin = 0;
-        int xmax = (int)(center + support + 0.5);
-        if (xmax > in) xmax = in;
-        cnt = xmax - xmin;
-    }
-};
-
 }  // namespace
 
 extern "C" int ipp_plan_pipe_batch(const ipp_pipe_plan_cfg* cfg, ipp_pipe_item* items, ipp_pipe_desc* descs,
@@ -549,16 +531,17 @@ extern "C" int ipp_plan_pipe_batch(const ipp_pipe_plan_cfg* cfg, ipp_pipe_item* 
         const bool id_h = same || nw_ == rw, id_v = same || nh_ == rh;
         ipp_tap_axis& ah = axes[2 * i];
         ipp_tap_axis& av = axes[2 * i + 1];
-        const int32_t ks_h = id_h ? 1 : ipp_plan_lanczos_ksize(0.0, (double)rw, nw_);
-        const int32_t ks_v = id_v ? 1 : ipp_plan_lanczos_ksize(0.0, (double)rh, nh_);
+        const resample_plan::Axis lh(IPP_RESAMPLE_LANCZOS, rw, 0.0, (double)rw, nw_);
+        const resample_plan::Axis lv(IPP_RESAMPLE_LANCZOS, rh, 0.0, (double)rh, nh_);
+        const int32_t ks_h = id_h ? 1 : lh.ksize;
+        const int32_t ks_v = id_v ? 1 : lv.ksize;
         // V rows: Pillow's ybox_first/last when the H pass runs first
         int32_t y0 = 0, y1 = rh;
         if (!id_h && !id_v) {
-            AxisBounds b(rh, nh_);
             int xm, cn;
-            b.at(0, xm, cn);
+            lv.bounds(0, xm, cn);
             y0 = xm;
-            b.at(nh_ - 1, xm, cn);
+            lv.bounds(nh_ - 1, xm, cn);
             y1 = xm + cn;
         }
         const int32_t rows = y1 - y0;

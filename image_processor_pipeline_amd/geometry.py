@@ -218,14 +218,21 @@ REFERENCE_HSV_RANGES = [
 
 def lanczos_taps(in_size: int, out_size: int) -> Tuple[int, np.ndarray]:
     """(ksize, int32[2*out + out*ksize]) via the C planner (Resample.c)."""
+    return resample_taps("lanczos", in_size, out_size)
+
+
+def mfma_tiles(axis) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Every tap tile of a ``TAP_AXIS`` record, built on the host by
+    ipp_plan_mfma_tile: (hdr (T, 4) int32, bias (T, 16) int32, blocks
+    (T, nkb·3072) uint8; tile t's first hdr[t, 1]·3072 bytes are written)."""
     lib = N.load()
-    need = -lib.ipp_plan_lanczos(in_size, 0.0, float(in_size), out_size, None, 0)
-    if need <= 0:
-        raise ValueError(f"invalid resize {in_size}->{out_size}")
-    buf = np.empty(need, np.int32)
-    k = lib.ipp_plan_lanczos(in_size, 0.0, float(in_size), out_size, N.np_ptr(buf), need)
-    N.check(0 if k > 0 else int(k), "ipp_plan_lanczos")
-    return int(k), buf
+    ax = np.array(axis, dtype=N.TAP_AXIS).reshape(1)
+    T, cap = int(ax["n_tiles"][0]), max(1, int(ax["nkb"][0])) * 3072
+    hdr, bias, blocks = np.zeros((T, 4), np.int32), np.zeros((T, 16), np.int32), np.zeros((T, cap), np.uint8)
+    for t in range(T):
+        N.check(lib.ipp_plan_mfma_tile(N.np_ptr(ax), t, N.np_ptr(hdr[t]), N.np_ptr(bias[t]), N.np_ptr(blocks[t]), cap),
+                "ipp_plan_mfma_tile")
+    return hdr, bias, blocks
 
 
 def resample_taps(resample: str, in_size: int, out_size: int) -> Tuple[int, np.ndarray]:

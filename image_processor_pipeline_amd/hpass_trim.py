@@ -18,7 +18,7 @@ from typing import List, Tuple
 
 import numpy as np
 
-from . import _native as N
+from .geometry import mfma_tiles
 
 HP_ROWS = 16          # ipp_pipe.hip HR: M rows per band
 TRIM_MAX_TILES = 64   # one header per lane: wider items are not trimmed
@@ -66,19 +66,7 @@ def tile_windows(axis) -> np.ndarray:
     """(n_tiles, 2) int array of (hdr.x, hdr.y) = (first input column, 64-column
     K steps) of every tile of a tap axis (ipp_plan_mfma_tile, the host
     restatement of the device tap planner)."""
-    lib = N.load()
-    ax = np.array(axis, dtype=N.TAP_AXIS)
-    nt = int(ax["n_tiles"])
-    out = np.zeros((nt, 2), np.int64)
-    hdr = np.zeros(4, np.int32)
-    bias = np.zeros(16, np.int32)
-    cap = max(1, int(ax["nkb"])) * 3072
-    blocks = np.zeros(cap, np.uint8)
-    for t in range(nt):
-        N.check(lib.ipp_plan_mfma_tile(N.np_ptr(ax), t, N.np_ptr(hdr), N.np_ptr(bias), N.np_ptr(blocks), cap),
-                "ipp_plan_mfma_tile")
-        out[t] = hdr[0], hdr[1]
-    return out
+    return mfma_tiles(axis)[0][:, :2].astype(np.int64)
 
 
 def sweep_bounds(windows: np.ndarray, xlo: int, xhi: int) -> Tuple[int, int]:

@@ -238,7 +238,7 @@ typedef struct ipp_pipe_desc {
     ipp_paste_desc p;       /* paste: ov = V-pass result (never stored)        */
 } ipp_pipe_desc;
 
-/* Tap format of the pipe kernels (ipp_plan_pipe_axes format = 2 + phase).
+/* Tap format of the pipe kernels (the tiles of ipp_pipe_plan_taps).
  * The pipe kernels take IPP_TAPS_MFMA only; any other value returns
  * IPP_E_ARG. */
 #define IPP_TAPS_MFMA 1   /* 16-output tiles, v_mfma_i32_16x16x64_i8          */
@@ -1039,29 +1039,12 @@ int64_t ipp_plan_lanczos(int32_t in_size, double in0, double in1, int32_t out_si
 #define IPP_RESAMPLE_LANCZOS 4
 int64_t ipp_plan_resample(int32_t filter, int32_t in_size, double in0, double in1,
                           int32_t out_size, int32_t* out, int64_t out_capacity);
-/* Batch form: n axes (in_sizes[i] → out_sizes[i], box = full axis), each
- * written at int32 offset offsets[i] of `out`; n_threads ≤ 0 = all cores. */
-int ipp_plan_lanczos_batch(int32_t n, const int32_t* in_sizes, const int32_t* out_sizes,
-                           const int64_t* offsets, int32_t* out, int64_t out_capacity,
-                           int32_t n_threads);
-/* Plan every axis of a pipe batch in the MFMA tile format (threaded);
- * identity[i] = no pass on that axis; shift_first[i] = shift bounds to
- * ybox_first; transposed[i] = 2 + tile phase (other values: IPP_E_ARG);
- * first_last receives (ybox_first, ybox_last). */
-int ipp_plan_pipe_axes(int32_t n, const int32_t* in_sizes, const int32_t* out_sizes,
-                       const int32_t* identity, const int32_t* shift_first,
-                       const int32_t* transposed, const int64_t* offsets, int32_t* out,
-                       int32_t* first_last, int32_t n_threads);
 /* MFMA tile format of a pipe axis (v_mfma_i32_16x16x64_i8; stated in
- * csrc/ipp_pipe_layout.h):
- * size bound in int32 for (in, out, ksize), bound on K steps per tile, and the
- * conversion from standard Pillow taps (input indices minus `shift`, tiles
- * offset by `phase` outputs).  ipp_plan_pipe_axes writes this format for axes
- * with transposed[i] = 2 + phase. */
+ * csrc/ipp_pipe_layout.h): size bound in int32 for (in, out, ksize) and bound
+ * on K steps per tile.  ipp_plan_mfma_tile (below) is the one host function
+ * that writes the format. */
 int64_t ipp_plan_mfma_size(int32_t in_size, int32_t out_size, int32_t ksize);
 int32_t ipp_plan_mfma_nk_bound(int32_t in_size, int32_t out_size, int32_t ksize);
-int ipp_plan_mfma_from_taps(int32_t in_size, int32_t out_size, int32_t ksize,
-                            const int32_t* std_taps, int32_t shift, int32_t phase, int32_t* out);
 /* ksize for (in_size, out_size) without computing taps. */
 int32_t ipp_plan_lanczos_ksize(double in0, double in1, int32_t out_size);
 
@@ -1153,7 +1136,7 @@ int ipp_plan_pipe_batch(const ipp_pipe_plan_cfg* cfg, ipp_pipe_item* items, ipp_
                         ipp_tap_axis* axes, int64_t* totals);
 
 /* Device tap planner (ipp_taps.hip): builds the MFMA tile format of every
- * axis (what ipp_plan_mfma_from_taps writes from Pillow's taps: hdr, bias,
+ * axis (what ipp_plan_mfma_tile writes from Pillow's taps: hdr, bias,
  * blocks; tile t's blocks at uint4 offset t·nkb·192 of the axis's block area)
  * directly in `coefs` (device, IPP_PT_COEF_WORDS int32).  The taps are
  * computed in fp64 on the device; any tile holding a tap whose rounding point

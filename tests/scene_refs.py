@@ -75,15 +75,5 @@ def scene_noise_batch(fused, S, K, H, W, n_bg, bh, bw, cfg, seed):
 def host_v_ksteps(plan):
     """K steps of every V tap tile of the plan, from the host restatement of
     the device tap tiles (ipp_plan_mfma_tile; hdr[1] = K steps)."""
-    from image_processor_pipeline_amd import _native as N
-    lib = N.load()
-    ks = set()
-    hdr, bias = np.zeros(4, np.int32), np.zeros(16, np.int32)
-    for ax in plan.axes[1::2]:
-        blocks = np.zeros(max(int(ax["nkb"]), 1) * 3072, np.uint8)
-        one = np.array([ax])
-        for t in range(int(ax["n_tiles"])):
-            N.check(lib.ipp_plan_mfma_tile(N.np_ptr(one), t, N.np_ptr(hdr), N.np_ptr(bias), N.np_ptr(blocks),
-                                           blocks.nbytes), "ipp_plan_mfma_tile")
-            ks.add(int(hdr[1]))
-    return ks
+    from image_processor_pipeline_amd.geometry import mfma_tiles
+    return {int(nk) for ax in plan.axes[1::2] for nk in mfma_tiles(ax)[0][:, 1]}

@@ -2,8 +2,9 @@
 restatement of Pillow's taps (ipp_plan_mfma_tile: Resample.c
 precompute_coeffs + normalize_coeffs_8bpc with libm sin, reference call site
 overlays.py:129), tile by tile: header, biases and every byte of the i8
-blocks, bit-exact.  The host builder itself is pinned to the axis planner
-(tests/test_plan_batch.py) and that to the oracle (tests/test_host_plan.py).
+blocks, bit-exact.  The host builder itself is pinned to the oracle's taps:
+its tiles are decoded tap by tap (tests/test_plan_batch.py) and run through an
+emulated MFMA (tests/test_host_plan.py), dense and compact.
 """
 import numpy as np
 import pytest
@@ -12,25 +13,22 @@ torch = pytest.importorskip("torch")
 
 from image_processor_pipeline_amd import _native as N
 from image_processor_pipeline_amd import fused as F
+from image_processor_pipeline_amd import geometry as G
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
 
 def _check_axes(plan, coefs, axes_idx):
-    lib = N.load()
     c = coefs.cpu().numpy()
     bad = []
     for j in axes_idx:
         a = plan.axes[j:j + 1]
-        T, off, nkb = int(a["n_tiles"][0]), int(a["coef_off"][0]), int(a["nkb"][0])
+        T, off = int(a["n_tiles"][0]), int(a["coef_off"][0])
         hdr = c[off:off + 4 * T].reshape(T, 4)
         bias = c[off + 4 * T:off + 20 * T]
         blocks = c[off + 20 * T:].view(np.uint8)
-        for t in range(T):
-            h4, b16 = np.zeros(4, np.int32), np.zeros(16, np.int32)
-            blk = np.zeros(nkb * 3072, np.uint8)
-            assert lib.ipp_plan_mfma_tile(N.np_ptr(a), t, N.np_ptr(h4), N.np_ptr(b16), N.np_ptr(blk), blk.size) == 0
+        for t, (h4, b16, blk) in enumerate(zip(*G.mfma_tiles(a))):
             nk = int(h4[1])
             ok = (np.array_equal(hdr[t], h4) and np.array_equal(bias[16 * t:16 * t + 16], b16)
                   and np.array_equal(blocks[h4[2] * 16:h4[2] * 16 + nk * 3072], blk[:nk * 3072]))

@@ -1,5 +1,6 @@
 """Host-side planning (CPU): the C planner and the Python geometry reproduce
 the library host arithmetic exactly (checked against the oracle)."""
+import functools
 import math
 import random
 
@@ -9,6 +10,7 @@ import pytest
 from image_processor_pipeline_amd import _native as N
 from image_processor_pipeline_amd import geometry as G
 from oracle import ops
+from tests import tap_tile_refs as TT
 
 
 @pytest.mark.parametrize("io", [(1024, 200), (1268, 307), (57, 20), (30, 45), (9, 3), (1, 1), (5, 9),
@@ -73,51 +75,81 @@ def test_overlay_size_and_hsv_params():
         G.hsv_params([])
 
 
-@pytest.mark.parametrize("io,shift,phase", [((1100, 230), 0, 0), ((1268, 150), 0, 7), ((896, 896), 0, 0),
-                                            ((40, 13), 0, 3), ((1, 1), 0, 0), ((300, 299), 0, 15), ((57, 20), 0, 0),
-                                            ((1150, 240), 9, 5)])
-def test_mfma_tile_format_is_exact(io, shift, phase):
-    """Emulate v_mfma_i32_16x16x64_i8 on the planned B blocks: for every
-    output, bias + Σ_p 2^(8p) Σ_s Σ_k (pix[K0+64s+k] ^ 0x80) · B_p[k][col]
-    == 2^21 + Σ p·k (the identity the MFMA H pass relies on)."""
-    lib = N.load()
-    i, o = io
-    k, std = G.lanczos_taps(i, o)
-    if shift:
-        std[0:2 * o:2] += shift   # pretend the axis starts `shift` rows later
-    size = lib.ipp_plan_mfma_size(i, o, k)
-    out = np.zeros(size, np.int32)
-    assert lib.ipp_plan_mfma_from_taps(i, o, k, N.np_ptr(std), shift, phase, N.np_ptr(out)) == 0
-    T = (o + phase + 15) // 16
-    hdr = out[:4 * T].reshape(T, 4)
-    bias = out[4 * T:20 * T]
-    nblk = int(max(hdr[:, 2] // 64 + hdr[:, 1] * 3))
-    blocks = out[20 * T:20 * T + nblk * 256].view(np.uint8).view(np.int8).reshape(-1, 64, 16)
-    rng = np.random.default_rng(5)
-    pix = rng.integers(0, 256, i + 256, np.uint8)
+MFMA_CASES = [((1100, 230), 0), ((1268, 150), 7), ((896, 896), 0), ((40, 13), 3), ((1, 1), 0), ((300, 299), 15),
+              ((57, 20), 0), ((1150, 240), 5)]
+
+
+def _mfma_identity(a, t, h4, b16, blk, std, k):
+    """The identity on tile t of axis record a: emulate v_mfma_i32_16x16x64_i8 on the tile's B operand."""
+    i, o, phase, shift = (int(a[f][0]) for f in ("in_size", "out_size", "phase", "shift"))
+    pix = np.random.default_rng(5).integers(0, 256, i + 64 * int(a["nkb"][0]) + 16, np.uint8)
     sp = (pix ^ 0x80).view(np.int8).astype(np.int64)
-    for t in range(T):
-        K0, nK, boff = int(hdr[t, 0]), int(hdr[t, 1]), int(hdr[t, 2])
-        assert K0 % 16 == 0 and boff % 64 == 0
-        acc = np.zeros((3, 16), np.int64)
-        for s in range(nK):
-            for p in range(3):
-                blk = blocks[boff // 64 + s * 3 + p].astype(np.int64)  # [lane][j]
-                Bm = np.zeros((64, 16), np.int64)                     # B[k][col]
-                for lane in range(64):
-                    Bm[16 * (lane >> 4):16 * (lane >> 4) + 16, lane & 15] = blk[lane]
-                a = sp[K0 + 64 * s:K0 + 64 * s + 64]
-                a = np.pad(a, (0, 64 - len(a)))
-                acc[p] += a @ Bm
-        for col in range(16):
-            oo = 16 * t - phase + col
-            if oo < 0 or oo >= o:
-                assert bias[16 * t + col] == 0
-                continue
-            xmin, cnt = std[2 * oo] - shift, std[2 * oo + 1]
-            ref = (1 << 21) + int((pix[xmin:xmin + cnt].astype(np.int64) * std[2 * o + oo * k:2 * o + oo * k + cnt]).sum())
-            got = int(bias[16 * t + col]) + int(acc[0, col]) + (int(acc[1, col]) << 8) + (int(acc[2, col]) << 16)
-            assert got == ref, (t, col)
+    K0, nK = int(h4[0]), int(h4[1])
+    assert K0 % 16 == 0 and h4[2] == t * int(a["nkb"][0]) * 192
+    B = TT.tile_operand(h4, blk)                         # [plane][K step][k][col]
+    acc = np.zeros((3, 16), np.int64)
+    for s in range(nK):
+        for p in range(3):
+            acc[p] += sp[K0 + 64 * s:K0 + 64 * s + 64] @ B[p, s]
+    for col in range(16):
+        oo = 16 * t - phase + col
+        if oo < 0 or oo >= o:
+            assert b16[col] == 0
+            continue
+        xmin, cnt = std[2 * oo] - shift, std[2 * oo + 1]
+        ref = (1 << 21) + int((pix[xmin:xmin + cnt].astype(np.int64) * std[2 * o + oo * k:2 * o + oo * k + cnt]).sum())
+        got = int(b16[col]) + int(acc[0, col]) + (int(acc[1, col]) << 8) + (int(acc[2, col]) << 16)
+        assert got == ref, (t, col)
+
+
+@functools.lru_cache(maxsize=None)
+def _mfma_tiles(io, phase, compact):
+    a = TT.tap_axis(*io, phase=phase, compact=compact)
+    return (a,) + G.mfma_tiles(a)
+
+
+@pytest.mark.parametrize("compact", [0, 1])
+@pytest.mark.parametrize("io,phase", MFMA_CASES)
+def test_mfma_tile_format_is_exact(io, phase, compact):
+    """Emulate v_mfma_i32_16x16x64_i8 on the B operand of the host builder's
+    tiles (ipp_plan_mfma_tile, dense and compact; the compact tiles read by
+    tap_tile_refs' numpy decoder): for every output,
+    bias + Σ_p 2^(8p) Σ_s Σ_k (pix[K0+64s+k] ^ 0x80) · B_p[k][col]
+    == 2^21 + Σ p·k (the identity the MFMA H pass relies on).  Over the whole
+    parametrisation some tile is compact (hdr[3] = 1, nK >= 2) and some dense
+    tile has nK >= 2."""
+    k, std = G.lanczos_taps(*io)
+    a, hdr, bias, blocks = _mfma_tiles(io, phase, compact)
+    assert compact or not hdr[:, 3].any()
+    for t, (h4, b16, blk) in enumerate(zip(hdr, bias, blocks)):
+        _mfma_identity(a, t, h4, b16, blk, std, k)
+    every = np.concatenate([_mfma_tiles(c_io, c_phase, c)[1] for c_io, c_phase in MFMA_CASES for c in (0, 1)])
+    assert ((every[:, 3] == 1) & (every[:, 1] >= 2)).any() and ((every[:, 3] == 0) & (every[:, 1] >= 2)).any()
+
+
+def test_mfma_tile_shift():
+    """axis.shift is subtracted from Pillow's bounds, and a first window left
+    of 0 is IPP_E_RANGE: shift = 1 on an axis whose first xmin is 0.
+
+    No shift > 0 is checked on a planned axis, because the planner emits none:
+    it sets a V axis's shift to its first xmin, and with in0 = 0 that is
+    max(0, int(scale/2 - 3·max(scale, 1) + 0.5)) = 0 for every scale (the
+    argument is below -2).  The plan below shows it; the later tiles of the
+    shifted axis, whose windows start at xmin - 1, are checked instead."""
+    from image_processor_pipeline_amd import fused
+    k, std = G.lanczos_taps(1100, 230)
+    a = TT.tap_axis(1100, 230, shift=1)
+    lib = N.load()
+    h4, b16, blk = np.zeros(4, np.int32), np.zeros(16, np.int32), np.zeros(int(a["nkb"][0]) * 3072, np.uint8)
+    for t in (0, 1, 7, 14):
+        rc = lib.ipp_plan_mfma_tile(N.np_ptr(a), t, N.np_ptr(h4), N.np_ptr(b16), N.np_ptr(blk), blk.size)
+        assert rc == (N.IPP_E_RANGE if t == 0 else 0) and std[0] == 0
+        if t:
+            assert h4[0] == (std[2 * 16 * t] - 1) & ~15
+            _mfma_identity(a, t, h4, b16, blk, std, k)
+    cfg = fused.PipeConfig(margins=(0, 0, 0, 0), scale_min=0.5, scale_max=0.9)
+    plan = fused.plan_pipe((200, 160), 30, (1024, 1024), 2, cfg, seed=11)
+    assert not plan.axes["shift"].any() and not plan.axes[1::2]["identity"].all()
 
 
 def test_pipe_plan_rejects_windows_wider_than_the_ring():

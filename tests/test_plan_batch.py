@@ -12,7 +12,7 @@ and tests/test_host_plan.py to the oracle).
 * Per-item parameters, geometry and every descriptor field, for plans with
   and without item ranges, given parameters, non-square sizes.
 * The per-tile host tap builder (ipp_plan_mfma_tile, the fix-up path of the
-  device tap planner) against ipp_plan_mfma_from_taps.
+  device tap planner): its tiles, decoded tap by tap, against Pillow's taps.
 """
 import ctypes
 import math
@@ -25,6 +25,7 @@ from image_processor_pipeline_amd import _native as N
 from image_processor_pipeline_amd import fused as F
 from image_processor_pipeline_amd import geometry as G
 from image_processor_pipeline_amd.device import SYM_FLIP
+from tests import tap_tile_refs as TT
 
 
 @pytest.mark.parametrize("seed", [0, 1, 7919, 123456789, 2 ** 32 + 5, 2 ** 63 + 11, 2 ** 64 - 1])
@@ -190,40 +191,35 @@ def test_batch_plan_given_params_and_errors():
         assert [q.angle for q in p.params] == angles and [q.x for q in p.params] == [e[1] for e in per]
 
 
-@pytest.mark.parametrize("io,shift,phase,ident", [((1100, 230), 0, 0, 0), ((1268, 150), 0, 7, 0),
-                                                  ((896, 896), 0, 0, 1), ((40, 13), 0, 3, 0), ((1, 1), 0, 0, 1),
-                                                  ((300, 299), 0, 15, 0), ((1150, 240), 9, 5, 0),
-                                                  ((2000, 90), 3, 11, 0)])
-def test_mfma_tile_matches_axis_planner(io, shift, phase, ident):
-    lib = N.load()
+@pytest.mark.parametrize("compact", [0, 1])
+@pytest.mark.parametrize("io,phase,ident", [((1100, 230), 0, 0), ((1268, 150), 7, 0), ((896, 896), 0, 1),
+                                            ((40, 13), 3, 0), ((1, 1), 0, 1), ((300, 299), 15, 0),
+                                            ((1150, 240), 5, 0), ((2000, 90), 11, 0)])
+def test_mfma_tile_decodes_to_pillow_taps(io, phase, ident, compact):
+    """Every tile of ipp_plan_mfma_tile, dense and compact, read back tap by
+    tap with the numpy decoder of tests/tap_tile_refs.py: the tap at input
+    K0 + 64s + kin of each output is Pillow's (zero outside its window), the
+    bias is 2^21 + 128·Σk, and tile t's blocks sit at t·nkb·192."""
     i, o = io
-    if ident:
-        k, std = G.identity_taps(o)
-    else:
-        k, std = G.lanczos_taps(i, o)
-    if shift:
-        std[0:2 * o:2] += shift
-    out = np.zeros(lib.ipp_plan_mfma_size(i, o, k), np.int32)
-    assert lib.ipp_plan_mfma_from_taps(i, o, k, N.np_ptr(std), shift, phase, N.np_ptr(out)) == 0
-    T = (o + phase + 15) // 16
-    ax = np.zeros(1, N.TAP_AXIS)
-    ax["in_size"], ax["out_size"], ax["identity"], ax["shift"], ax["phase"] = i, o, ident, shift, phase
-    ax["nkb"], ax["n_tiles"] = lib.ipp_plan_mfma_nk_bound(i, o, k), T
-    hdr = out[:4 * T].reshape(T, 4)
-    blocks = out[20 * T:].view(np.uint8)
-    for t in range(T):
-        h4, b16 = np.zeros(4, np.int32), np.zeros(16, np.int32)
-        blk = np.zeros(int(ax["nkb"][0]) * 3072, np.uint8)
-        # the axis planner got Pillow's bounds moved by +shift and subtracts
-        # shift again: the tile builder sees the plain axis
-        ax2 = ax.copy()
-        ax2["shift"] = 0
-        assert lib.ipp_plan_mfma_tile(N.np_ptr(ax2), t, N.np_ptr(h4), N.np_ptr(b16), N.np_ptr(blk), blk.size) == 0
-        assert (h4[0], h4[1]) == (hdr[t, 0], hdr[t, 1]), t
-        assert np.array_equal(b16, out[4 * T + 16 * t:4 * T + 16 * t + 16]), t
-        nk = int(h4[1])
-        assert np.array_equal(blk[:nk * 3072], blocks[hdr[t, 2] * 16:hdr[t, 2] * 16 + nk * 3072]), t
-        assert h4[2] == t * int(ax["nkb"][0]) * 192
+    k, std = G.identity_taps(o) if ident else G.lanczos_taps(i, o)
+    a = TT.tap_axis(i, o, identity=ident, phase=phase, compact=compact)
+    for t, (h4, b16, blk) in enumerate(zip(*G.mfma_tiles(a))):
+        K0, nK = int(h4[0]), int(h4[1])
+        o0 = 16 * t - phase
+        oa, o1 = max(o0, 0), min(o0 + 16, o)
+        assert K0 == std[2 * oa] & ~15
+        assert nK == (max(std[2 * oo] + std[2 * oo + 1] for oo in range(oa, o1)) - K0 + 63) // 64
+        assert h4[2] == t * int(a["nkb"][0]) * 192
+        assert h4[3] in ((0, 1) if compact and not ident else (0,))
+        exp = np.zeros((64 * nK, 16), np.int64)
+        exp_bias = np.zeros(16, np.int64)
+        for oo in range(oa, o1):
+            xmin, cnt = std[2 * oo], std[2 * oo + 1]
+            kk = std[2 * o + oo * k:2 * o + oo * k + cnt].astype(np.int64)
+            exp[xmin - K0:xmin - K0 + cnt, oo - o0] = kk
+            exp_bias[oo - o0] = (1 << 21) + 128 * int(kk.sum())
+        assert np.array_equal(TT.tile_taps(h4, blk), exp), t
+        assert np.array_equal(b16, exp_bias), t
 
 
 def test_plan_rejects_overlays_wider_than_the_v_launch():

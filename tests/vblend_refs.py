@@ -23,6 +23,7 @@ from collections import namedtuple
 import numpy as np
 
 from image_processor_pipeline_amd import _native as N
+from image_processor_pipeline_amd.geometry import mfma_tiles
 from oracle import ops
 
 BAND = 16                     # kBandRows
@@ -86,20 +87,12 @@ def v_axis(in_len, out_len, phase, identity=0):
     T = tap_ntiles(out_len, phase)
     a["in_size"], a["out_size"], a["identity"], a["shift"], a["phase"] = in_len, out_len, identity, 0, phase
     a["nkb"], a["compact"], a["n_tiles"], a["coef_off"] = nkb, 0, T, 0
-    words = np.zeros(20 * T + T * nkb * 768, np.int32)
-    hdr, bias = words[:4 * T].reshape(T, 4), words[4 * T:20 * T].reshape(T, 16)
-    blocks = words[20 * T:].view(np.uint8)
-    nks = []
-    for t in range(T):
-        h4, b16 = np.zeros(4, np.int32), np.zeros(16, np.int32)
-        blk = np.zeros(nkb * 3072, np.uint8)
-        rc = lib.ipp_plan_mfma_tile(N.np_ptr(a), t, N.np_ptr(h4), N.np_ptr(b16), N.np_ptr(blk), blk.size)
-        assert rc == 0, (in_len, out_len, phase, t, rc)
+    hdr, bias, blocks = mfma_tiles(a)
+    for t, h4 in enumerate(hdr):
         assert h4[2] == t * nkb * 192 and h4[3] == 0
-        hdr[t], bias[t] = h4, b16
-        blocks[16 * int(h4[2]):16 * int(h4[2]) + blk.size] = blk
-        nks.append(int(h4[1]))
-    return a, words, nks
+    # tile t's blocks at uint4 h4[2] = t·nkb·192 of the block area: the tiles back to back
+    words = np.concatenate([hdr.reshape(-1), bias.reshape(-1), blocks.reshape(-1).view(np.int32)])
+    return a, words, [int(nk) for nk in hdr[:, 1]]
 
 
 # --------------------------------------------------------------------------- descriptors
