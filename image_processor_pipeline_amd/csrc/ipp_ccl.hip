@@ -52,8 +52,9 @@
 //                    deterministic labelling as K1, so the same ids) and looks
 //                    up each component's final root.  Then α := 0 outside the
 //                    component in place (plugin path), or (fused chain) the
-//                    words are stored and k_ccl_crop_stream writes the crop-fit
-//                    as BGRA from the BGR frame in output-row order.
+//                    words are stored and k_ccl_crop_rows writes the crop-fit
+//                    as BGRA from the BGR frame, a wave per crop row at a
+//                    time, for any frame width and h·pitch + 18 < 2^32.
 // Pixels are read once in K1 and once in K6 (within the crop for the fused
 // chain); everything else is per run, per component or per edge pixel.
 #include <algorithm>
@@ -82,6 +83,24 @@ __device__ __forceinline__ Frame frame_of(const ipp_image_desc& d) {
     f.tiles_x = (d.w + TW - 1) / TW;
     f.tiles_y = (d.h + TH - 1) / TH;
     return f;
+}
+
+// A block of the group grid (plan_launch) is WAVES tiles side by side, one
+// wave each, groups_x blocks per tile row: its image, tile, wave and lane.
+struct TileWave {
+    int im, tx, ty, wave, lane;
+};
+
+__device__ __forceinline__ TileWave tile_wave(int groups_per_img, int groups_x) {
+    const uint32_t b = xcd_remap(blockIdx.x, gridDim.x);
+    TileWave t;
+    t.im = b / groups_per_img;
+    const int g = b - t.im * groups_per_img;
+    t.ty = g / groups_x;
+    t.wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    t.lane = threadIdx.x & 63;
+    t.tx = (g - t.ty * groups_x) * WAVES + t.wave;
+    return t;
 }
 
 // Run-start slot inside a tile; orders slots as G orders run starts.
@@ -152,32 +171,28 @@ __device__ __forceinline__ void gunite(int32_t* P, int32_t a, int32_t b) {
 // NJ + component id < NJ + CMAX after label_tile): 4 KB per wave.  A union's
 // atomicMin is a 32-bit compare-and-swap on the word holding the entry (LDS
 // has no 16-bit atomics); plain 16-bit loads and stores elsewhere.
+// Slot j's dword (rows 2k and 2k+1 of one column pair) sits on bank (column
+// pair) mod 32, so the runs of many rows that start in one column — a blob
+// crossing the tile's left edge — hit one bank: k_ccl_label's LDS bank
+// conflicts (2.2e8 of 5.9e8 LDS cycles; profiles/r05/ccl/).  Rotating the bank
+// by the row pair cut them to 5.8e7 but its VALU on every access ran config 5
+// 0.3-5 % slower (round 5, two forms measured): slots stay in place.
 typedef uint16_t Par;
 
 __device__ __forceinline__ int lld(const Par* p) { return *reinterpret_cast<const volatile Par*>(p); }
 
-// Physical position of run slot j in the union-find array.  Slot j's dword
-// (two 16-bit entries: rows 2k and 2k+1 of one column pair) sits on bank
-// (column pair) mod 32, so the runs of many rows that start in one column — a
-// blob crossing the tile's left edge — hit one bank: that is where
-// k_ccl_label's LDS bank conflicts come from (2.2e8 of 5.9e8 LDS cycles;
-// profiles/r05/ccl/).  Rotating the bank by the row pair cut them to 5.8e7 but
-// cost VALU on every union-find access: config 5 0.3-5 % slower (round 5, two
-// forms measured), so slots stay in place.
-__device__ __forceinline__ int pswz(int j) { return j; }
-
 __device__ __forceinline__ int lfind(const Par* par, int x) {
-    int p = lld(par + pswz(x));
+    int p = lld(par + x);
     while (p != x) {
         x = p;
-        p = lld(par + pswz(x));
+        p = lld(par + x);
     }
     return x;
 }
 
 // par[b] = min(par[b], a); returns the previous par[b].
 __device__ __forceinline__ int lmin16(Par* par, int b, int a) {
-    uint32_t* w = reinterpret_cast<uint32_t*>(par + (pswz(b) & ~1));
+    uint32_t* w = reinterpret_cast<uint32_t*>(par + (b & ~1));
     const int sh = (b & 1) * 16;
     uint32_t cur = *reinterpret_cast<volatile uint32_t*>(w);
     for (;;) {
@@ -239,11 +254,11 @@ __device__ __forceinline__ int label_tile(Par* par, int r, int lane, u64 m, u64 
         // every run is a root, and the ids follow (row, run) order as below.
         int n;
         int cid = wave_scan_excl(__popcll(m & ~(m << 1)), lane, n);
-        for_runs(m, [&](int a, int) { par[pswz(slot(r, a))] = NJ + cid++; });
+        for_runs(m, [&](int a, int) { par[slot(r, a)] = NJ + cid++; });
         wave_sync();
         return n;
     }
-    for_runs(m, [&](int a, int) { par[pswz(slot(r, a))] = slot(r, a); });
+    for_runs(m, [&](int a, int) { par[slot(r, a)] = slot(r, a); });
     wave_sync();
     if (p) {
         const u64 ps = p & ~(p << 1);
@@ -273,10 +288,10 @@ __device__ __forceinline__ int label_tile(Par* par, int r, int lane, u64 m, u64 
         bool moved = false;
         for_runs(m, [&](int a, int) {
             const int j = slot(r, a);
-            const int pj = par[pswz(j)];
-            const int pp = par[pswz(pj)];
+            const int pj = par[j];
+            const int pp = par[pj];
             if (pp != pj) {
-                par[pswz(j)] = pp;
+                par[j] = pp;
                 moved = true;
             }
         });
@@ -288,26 +303,26 @@ __device__ __forceinline__ int label_tile(Par* par, int r, int lane, u64 m, u64 
         const int j = slot(r, a);
         const int root = lfind(par, j);
         nroot += root == j;
-        if (root != j) par[pswz(j)] = root;
+        if (root != j) par[j] = root;
     });
     wave_sync();
     int n;
     int cid = wave_scan_excl(nroot, lane, n);
     for_runs(m, [&](int a, int) {
         const int j = slot(r, a);
-        if (par[pswz(j)] == j) par[pswz(j)] = NJ + cid++;
+        if (par[j] == j) par[j] = NJ + cid++;
     });
     wave_sync();
     return n;
 }
 
 __device__ __forceinline__ int run_root(const Par* par, int j) {
-    const int v = par[pswz(j)];
+    const int v = par[j];
     return v >= NJ ? j : v;
 }
 __device__ __forceinline__ int run_cid(const Par* par, int j) {
-    const int v = par[pswz(j)];
-    return (v >= NJ ? v : par[pswz(v)]) - NJ;
+    const int v = par[j];
+    return (v >= NJ ? v : par[v]) - NJ;
 }
 
 // Scratch layout per image (offsets in the ipp_ccl_work descriptor).
@@ -560,13 +575,7 @@ k_ccl_label(const uint8_t* __restrict__ img, const ipp_image_desc* __restrict__ 
     __shared__ int st_root[WAVES][MAXC];
     struct NoTables {};
     __shared__ typename std::conditional<SRC == SRC_HSV, HsvTables<NR>, NoTables>::type T;
-    const uint32_t b = xcd_remap(blockIdx.x, gridDim.x);
-    const int im = b / groups_per_img;
-    const int g = b - im * groups_per_img;
-    const int ty = g / groups_x;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    const int tx = (g - ty * groups_x) * WAVES + wave;
+    const auto [im, tx, ty, wave, lane] = tile_wave(groups_per_img, groups_x);
     const ipp_image_desc d = descs[im];
     const Frame f = frame_of(d);
     Ranges<NR> R;  // zones only (the test itself is table-driven)
@@ -623,8 +632,8 @@ k_ccl_label(const uint8_t* __restrict__ img, const ipp_image_desc* __restrict__ 
         wave_sync();
         for_runs(m, [&](int a, int len) {
             const int j = slot(r, a);
-            const int v = par[pswz(j)];
-            const int c = (v >= NJ ? v : par[pswz(v)]) - NJ - c0;
+            const int v = par[j];
+            const int c = (v >= NJ ? v : par[v]) - NJ - c0;
             if ((unsigned)c < (unsigned)MAXC) {
                 atomicAdd(&area[c], (uint32_t)len);
                 atomicOr(&rows[c], 1ull << r);
@@ -903,8 +912,17 @@ k_ccl_bbox(const ipp_image_desc* __restrict__ descs, const ipp_ccl_work* __restr
 // kept component (lane r: row r).  A tile with one component takes its mask
 // words or nothing; a tile with several relabels its words (same ids as K1)
 // and looks up each component's final root.
+struct InWordLds {               // per wave
+    Par par[NJ];                 // label_tile's union-find
+    uint8_t cflag[CMAX];         // per component: it is the kept one
+    uint32_t cedge[CMAX / 32];   // per component: it touches a tile edge (bit)
+};
+
 __device__ __forceinline__ u64 tile_in_word(const Frame& f, const Work& k, int tile, int32_t broot, int lane,
-                                            Par* par, uint8_t* cflag, uint32_t* cedge, int tx, int ty) {
+                                            InWordLds& s, int tx, int ty) {
+    Par* par = s.par;
+    uint8_t* cflag = s.cflag;
+    uint32_t* cedge = s.cedge;
     const TileRec t = k.tile[tile];
     if (t.n == 0) return 0ull;
     const u64 m = k.mask[(int64_t)tile * TH + lane];
@@ -925,7 +943,7 @@ __device__ __forceinline__ u64 tile_in_word(const Frame& f, const Work& k, int t
     const bool closed_ok = 2ll * f.wb * ((f.h + 1) >> 1) <= CLOSED_SLOTS;
     for_runs(m, [&](int a, int) {
         const int j = slot(lane, a);
-        const int v = par[pswz(j)];
+        const int v = par[j];
         if (v >= NJ) {
             const int c = v - NJ;
             const int32_t G = slot_gidx(f, tx, ty, j);
@@ -952,23 +970,15 @@ __device__ __forceinline__ u64 row_word(u64 w, int r) {
 __global__ void __launch_bounds__(64 * WAVES)
 k_ccl_apply(uint8_t* __restrict__ img, const ipp_image_desc* __restrict__ descs, const ipp_ccl_work* __restrict__ works,
             uint8_t* __restrict__ scratch, int groups_per_img, int groups_x) {
-    __shared__ Par par_s[WAVES][NJ];
-    __shared__ uint8_t flag_s[WAVES][CMAX];
-    __shared__ uint32_t cedge_s[WAVES][CMAX / 32];
-    const uint32_t b = xcd_remap(blockIdx.x, gridDim.x);
-    const int im = b / groups_per_img;
-    const int g = b - im * groups_per_img;
-    const int ty = g / groups_x;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    const int tx = (g - ty * groups_x) * WAVES + wave;
+    __shared__ InWordLds lds[WAVES];
+    const auto [im, tx, ty, wave, lane] = tile_wave(groups_per_img, groups_x);
     const ipp_image_desc d = descs[im];
     const Frame f = frame_of(d);
     if (tx >= f.tiles_x || ty >= f.tiles_y) return;
     const Work k = work_of(scratch, works[im]);
     const int32_t broot = k.rec->root;
     if (broot < 0) return;
-    const u64 w = tile_in_word(f, k, ty * f.tiles_x + tx, broot, lane, par_s[wave], flag_s[wave], cedge_s[wave], tx, ty);
+    const u64 w = tile_in_word(f, k, ty * f.tiles_x + tx, broot, lane, lds[wave], tx, ty);
     const int x = tx * TW + lane;
     const int nr = min(TH, d.h - ty * TH);
     for (int r = 0; r < nr; ++r) {
@@ -980,36 +990,18 @@ k_ccl_apply(uint8_t* __restrict__ img, const ipp_image_desc* __restrict__ descs,
     }
 }
 
-#ifndef IPP_CCL_CROP_ROWS
-#define IPP_CCL_CROP_ROWS 1  // the crop-fit by row waves (k_ccl_crop_rows); 0: the item stream (A/B)
-#endif
-
 // K6, fused chain, in two passes.
 // (a) k_ccl_inwords: one wave per tile that meets the kept component's bbox
 //     overwrites the tile's mask words with its words restricted to the
 //     component (tile_in_word; zeros for tiles without foreground).
-// (b) k_ccl_crop_stream: the crop-fit of the BGR frame written as BGRA (α =
-//     255 inside the component, 0 elsewhere) into the image's output slot,
-//     row by row in output order: 4 pixels per thread (three dword loads, one
-//     16-byte store), so output lines are written whole whatever the bbox's
-//     alignment to the 64-pixel tiles.  Any frame width.  Live code: frames
-//     of more than CROP_ROWS_MAX_TILES_X tile columns (wider than 4096 px)
-//     take it instead of (b') k_ccl_crop_rows, and
-//     tests/test_gpu_parity.py test_video_chain_wide_frames_vs_oracle is its
-//     only coverage (narrower frames never launch it in the default build).
+// (b) k_ccl_crop_rows: the crop-fit of the BGR frame written as BGRA (α = 255
+//     inside the component, 0 elsewhere) into the image's output slot, one
+//     wave per crop row at a time, any frame width.
 __global__ void __launch_bounds__(64 * WAVES)
 k_ccl_inwords(const ipp_image_desc* __restrict__ descs, const ipp_ccl_work* __restrict__ works,
               uint8_t* __restrict__ scratch, const int32_t* __restrict__ bbox, int groups_per_img, int groups_x) {
-    __shared__ Par par_s[WAVES][NJ];
-    __shared__ uint8_t flag_s[WAVES][CMAX];
-    __shared__ uint32_t cedge_s[WAVES][CMAX / 32];
-    const uint32_t b = xcd_remap(blockIdx.x, gridDim.x);
-    const int im = b / groups_per_img;
-    const int g = b - im * groups_per_img;
-    const int ty = g / groups_x;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    const int tx = (g - ty * groups_x) * WAVES + wave;
+    __shared__ InWordLds lds[WAVES];
+    const auto [im, tx, ty, wave, lane] = tile_wave(groups_per_img, groups_x);
     // the bbox alone decides most waves (no kept component: an empty bbox)
     const int bx0 = bbox[4 * im + 0], by0 = bbox[4 * im + 1], bx1 = bbox[4 * im + 2], by1 = bbox[4 * im + 3];
     const int X0 = tx * TW, Y0 = ty * TH;
@@ -1019,99 +1011,28 @@ k_ccl_inwords(const ipp_image_desc* __restrict__ descs, const ipp_ccl_work* __re
     if (tx >= f.tiles_x || ty >= f.tiles_y) return;
     const Work k = work_of(scratch, works[im]);
     const int tile = ty * f.tiles_x + tx;
-    const u64 w = tile_in_word(f, k, tile, k.rec->root, lane, par_s[wave], flag_s[wave], cedge_s[wave], tx, ty);
+    const u64 w = tile_in_word(f, k, tile, k.rec->root, lane, lds[wave], tx, ty);
     k.mask[(int64_t)tile * TH + lane] = w;
 }
 
-constexpr int CROP_BLOCKS = 256;  // blocks per image striding over the crop
-
-__global__ void __launch_bounds__(256)
-k_ccl_crop_stream(const uint8_t* __restrict__ img, const ipp_image_desc* __restrict__ descs,
-                  const ipp_ccl_work* __restrict__ works, uint8_t* __restrict__ scratch,
-                  int32_t* __restrict__ bbox, uint8_t* __restrict__ out,
-                  const ipp_image_desc* __restrict__ out_descs) {
-    const uint32_t b = xcd_remap(blockIdx.x, gridDim.x);
-    const int im = b / CROP_BLOCKS;
-    const int rb = b - im * CROP_BLOCKS;
-    const int bx0 = bbox[4 * im + 0], by0 = bbox[4 * im + 1], bx1 = bbox[4 * im + 2], by1 = bbox[4 * im + 3];
-    if (bx1 <= bx0 || by1 <= by0) {  // no kept component
-        // (k_ccl_finish folded in: the image's first block reports the empty
-        // bbox as -1s; the other blocks read either form as empty)
-        if (rb == 0 && threadIdx.x < 4) bbox[4 * im + threadIdx.x] = -1;
-        return;
-    }
-    const ipp_image_desc d = descs[im];
-    const ipp_image_desc od = out_descs[im];
-    const Frame f = frame_of(d);
-    const Work k = work_of(scratch, works[im]);
-    const int cw = bx1 - bx0;
-    // all (row, 4-pixel chunk) items of the crop, 256 threads × CROP_BLOCKS
-    // blocks striding over them, two items per step for more loads in flight
-    const int cpr = (cw + 3) >> 2;  // chunks per row
-    const int64_t items = (int64_t)cpr * (by1 - by0);
-    const int64_t stride = (int64_t)CROP_BLOCKS * 256;
-    auto item = [&](int64_t it, uint32_t (&o)[4], int& n, uint32_t*& q) {
-        const int oy = (int)(it / cpr), ox = 4 * (int)(it - (int64_t)oy * cpr);
-        const int y = by0 + oy, x = bx0 + ox;
-        n = min(4, cw - ox);
-        const uint8_t* srow = img + d.off + (int64_t)y * d.pitch;
-        const u64* wrow = k.mask + (int64_t)(y / TH) * f.tiles_x * TH + (y & (TH - 1));
-        const u64 w0 = wrow[(int64_t)(x >> 6) * TH];
-        const u64 w1 = ((x + n - 1) >> 6) != (x >> 6) ? wrow[(int64_t)((x + n - 1) >> 6) * TH] : w0;
-        uint32_t px[4];
-        if (n == 4) {
-            const uint8_t* p = srow + 3 * x;
-            const uint32_t d0 = ld_u32_unaligned(p), d1 = ld_u32_unaligned(p + 4), d2 = ld_u32_unaligned(p + 8);
-            px[0] = d0;
-            px[1] = (d0 >> 24) | (d1 << 8);
-            px[2] = (d1 >> 16) | (d2 << 16);
-            px[3] = d2 >> 8;
-        } else {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const uint8_t* p = srow + 3 * (x + i);
-                px[i] = i < n ? (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) : 0u;
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int xi = x + i;
-            const u64 w = (xi >> 6) == (x >> 6) ? w0 : w1;
-            o[i] = (px[i] & 0x00FFFFFFu) | (((w >> (xi & 63)) & 1ull) ? 0xFF000000u : 0u);
-        }
-        q = reinterpret_cast<uint32_t*>(out + od.off + (int64_t)oy * od.pitch) + ox;
-    };
-    auto put = [&](const uint32_t (&o)[4], int n, uint32_t* q) {
-        if (n == 4 && ((reinterpret_cast<uintptr_t>(q) & 15u) == 0u)) {
-            typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-            // streaming store (-0.7 % against a plain one)
-            __builtin_nontemporal_store(u32x4{o[0], o[1], o[2], o[3]}, reinterpret_cast<u32x4*>(q));
-        } else {
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                if (i < n) q[i] = o[i];
-        }
-    };
-    for (int64_t it = (int64_t)rb * 256 + threadIdx.x; it < items; it += 2 * stride) {
-        uint32_t oa[4], ob[4];
-        int na, nb = 0;
-        uint32_t *qa, *qb = nullptr;
-        item(it, oa, na, qa);
-        if (it + stride < items) item(it + stride, ob, nb, qb);
-        put(oa, na, qa);
-        if (nb) put(ob, nb, qb);
-    }
-}
-
-// (b') k_ccl_crop_rows: the same crop-fit, one wave per crop row at a time.
-//     The stream above is texture-path bound (TA busy 96 % of the launch,
-//     profiles/r05/r05s9/prof_video4k): three unaligned dword loads plus the
-//     mask-word loads per 4 pixels.  Here a wave loads its row's source span
-//     with aligned 16-byte buffer loads (1 KB per instruction), stages it in
-//     LDS, and every lane assembles its 4 pixels from there (two LDS reads and
-//     v_alignbyte; the row's alignment is uniform), with the row's mask words
-//     read once into LDS too: per 4 pixels 0.75 load and 1 store instruction
-//     instead of ≈ 4.5 loads and 1 store.
+// k_ccl_crop_rows.  A wave loads its row's source span with aligned 16-byte
+// buffer loads (1 KB per instruction), stages it in LDS, and every lane assembles its 4 pixels
+// from there (two LDS reads and v_alignbyte; the row's alignment is uniform),
+// with the row's mask words read into LDS too: per 4 pixels 0.75 load and 1
+// store instruction.  (The per-item stream it replaced, three unaligned dword
+// loads plus the mask-word loads per 4 pixels, was texture-path bound: TA busy
+// 96 % of the launch, profiles/r05/r05s9/prof_video4k.)
+// Width: the mask words in LDS are a window of CROP_WIN output pixels over the
+// row's tile columns, one lane per word, reloaded every CROP_WIN / CROP_SEG
+// segments and re-based at the window's first tile column.  A window that
+// starts off a tile boundary meets TW + 1 tile columns: the last word is
+// fetched beside the lanes' words, only when the row has that many columns
+// left (never for a frame of at most CROP_WIN px, whose rows load their words
+// once, on the first segment).
+// Size: the frame is addressed through one buffer resource with 32-bit
+// offsets, from up to 15 bytes below the frame to the dword holding its last
+// byte: h·pitch + 18 < 2^32 (include/ipp.h; the descriptors are in device
+// memory, so the entry point cannot check it — VideoChain does).
 #ifndef IPP_CCL_CROP_ROW_BLOCKS
 #define IPP_CCL_CROP_ROW_BLOCKS 256
 #endif
@@ -1121,11 +1042,12 @@ constexpr int CROP_ROW_BLOCKS = IPP_CCL_CROP_ROW_BLOCKS;  // blocks per image (4
 #endif
 constexpr int CROP_SEG = 4 * 256;            // output pixels per wave iteration (4 × 64 lanes × 4)
 constexpr int CROP_CHUNKS = 3 * CROP_SEG / 16 + 1;  // 16-B source chunks one iteration may touch
-constexpr int CROP_ROWS_MAX_TILES_X = TW;    // widest frame, in tile columns: a lane per mask word of a row
+constexpr int CROP_WIN = TW * TW;            // output pixels per mask-word window: a lane per word (4 segments)
+static_assert(CROP_WIN % CROP_SEG == 0, "a window is whole segments");
 
 struct CropRowsLds {
     uint32_t stage[WAVES][CROP_CHUNKS * 4];  // source span of the wave's iteration
-    u64 words[WAVES][TW + 2];               // the row's mask words (tile columns tc0 ..), zero-padded
+    u64 words[WAVES][TW + 2];               // the window's mask words (TW lanes, the TW + 1st), zero-padded
 };
 
 __global__ void __launch_bounds__(256)
@@ -1138,7 +1060,9 @@ k_ccl_crop_rows(const uint8_t* __restrict__ img, const ipp_image_desc* __restric
     const int im = b / CROP_ROW_BLOCKS;
     const int rb = b - im * CROP_ROW_BLOCKS;
     const int bx0 = bbox[4 * im + 0], by0 = bbox[4 * im + 1], bx1 = bbox[4 * im + 2], by1 = bbox[4 * im + 3];
-    if (bx1 <= bx0 || by1 <= by0) {  // no kept component (k_ccl_finish folded in, as in k_ccl_crop_stream)
+    if (bx1 <= bx0 || by1 <= by0) {  // no kept component
+        // (k_ccl_finish folded in: the image's first block reports the empty
+        // bbox as -1s; the other blocks read either form as empty)
         if (rb == 0 && threadIdx.x < 4) bbox[4 * im + threadIdx.x] = -1;
         return;
     }
@@ -1149,12 +1073,7 @@ k_ccl_crop_rows(const uint8_t* __restrict__ img, const ipp_image_desc* __restric
     const Frame f = frame_of(d);
     const Work k = work_of(scratch, works[im]);
     const int cw = bx1 - bx0;
-    // ntc ≤ CROP_ROWS_MAX_TILES_X = 64, one mask word per lane and words[] of
-    // TW + 2: ipp_video_keep_largest launches this kernel only for frames of
-    // at most that many tile columns (≤ 4096 px) and k_ccl_crop_stream for
-    // wider ones (tests/test_gpu_parity.py
-    // test_video_chain_wide_frames_vs_oracle: 65, 69 and 120 tile columns).
-    const int tc0 = bx0 >> 6, ntc = ((bx1 - 1) >> 6) - tc0 + 1;
+    const int tc0 = bx0 >> 6, ntc = ((bx1 - 1) >> 6) - tc0 + 1;  // the crop's tile columns
     // The buffer starts at the 16-B aligned address at or below the frame
     // (fmis bytes before it, in the same aligned chunk) and ends with the
     // 4-aligned dword holding the frame's last byte: the range check works per
@@ -1172,7 +1091,7 @@ k_ccl_crop_rows(const uint8_t* __restrict__ img, const ipp_image_desc* __restric
     u64* words = L.words[wave];
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
     // The wave's (row, segment) units in order; each unit's chunk loads (and,
-    // on a row's first segment, its mask words) are issued before the
+    // on a window's first segment, its mask words) are issued before the
     // previous unit is assembled and stored (IPP_CCL_CROP_PF), so their
     // latency overlaps that work instead of stalling the wave.
     struct Unit {
@@ -1193,33 +1112,40 @@ k_ccl_crop_rows(const uint8_t* __restrict__ img, const ipp_image_desc* __restric
         return u;
     };
     auto next = [&](const Unit& u) { return u.seg + CROP_SEG < cw ? unit_at(u.y, u.seg + CROP_SEG) : unit_at(u.y + ystep, 0); };
-    auto load = [&](const Unit& u, u32x4 (&v)[4], u64& wd) {
+    auto new_window = [](const Unit& u) { return u.seg % CROP_WIN == 0; };
+    auto load = [&](const Unit& u, u32x4 (&v)[4], u64& wd, u64& wx) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int c = u.c0 + lane + 64 * i;
             if (c < u.c1)
                 v[i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, u.R - u.sh0 + 16u * (uint32_t)c, 0, 0));
         }
-        // the row's kept-component words, restricted by k_ccl_inwords (lanes
-        // past the row's tiles: zero), on its first segment
-        if (u.seg == 0)
-            wd = lane < ntc ? k.mask[((int64_t)(u.y >> 6) * f.tiles_x + tc0 + lane) * TH + (u.y & (TH - 1))] : 0ull;
+        // the window's kept-component words, restricted by k_ccl_inwords: lane
+        // l the word of the window's tile column l (past the row's: zero), wx
+        // the TW + 1st where the row has one (wave-uniform)
+        if (new_window(u)) {
+            const int wt = u.seg >> 6, nw = ntc - wt;  // the window's first tile column (from tc0); columns left
+            const u64* mrow = k.mask + ((int64_t)(u.y >> 6) * f.tiles_x + tc0 + wt) * TH + (u.y & (TH - 1));
+            wd = lane < nw ? mrow[lane * TH] : 0ull;
+            wx = 0ull;
+            if (nw > TW) wx = mrow[TW * TH];
+        }
     };
     Unit cur = unit_at(by0 + rb * WAVES + wave, 0);
     if (cur.y >= by1) return;
     u32x4 vc[4];
-    u64 wc = 0ull;
-    load(cur, vc, wc);
+    u64 wc = 0ull, xc = 0ull;
+    load(cur, vc, wc, xc);
     for (;;) {
         const Unit nx = next(cur);
         const bool more = nx.y < by1;
         u32x4 vn[4];
-        u64 wn = 0ull;
-        if (IPP_CCL_CROP_PF && more) load(nx, vn, wn);
+        u64 wn = 0ull, xn = 0ull;
+        if (IPP_CCL_CROP_PF && more) load(nx, vn, wn, xn);
         wave_sync();  // (the previous unit's stage and word reads done)
-        if (cur.seg == 0) {
+        if (new_window(cur)) {
             words[lane] = wc;
-            if (lane < 2) words[TW + lane] = 0ull;
+            if (lane < 2) words[TW + lane] = lane ? 0ull : xc;
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -1242,8 +1168,8 @@ k_ccl_crop_rows(const uint8_t* __restrict__ img, const ipp_image_desc* __restric
                            w2 = __builtin_amdgcn_alignbyte(d3, d2, sh);
             const uint32_t px[4] = {w0, __builtin_amdgcn_alignbyte(w1, w0, 3), __builtin_amdgcn_alignbyte(w2, w1, 2),
                                     w2 >> 8};
-            // the 4 pixels' bits: columns x .. x + 3 of the row's words
-            const int x = bx0 + ox, t = (x >> 6) - tc0, bb = x & 63;
+            // the 4 pixels' bits: columns x .. x + 3 of the window's words
+            const int x = bx0 + ox, t = (x >> 6) - tc0 - cur.seg / CROP_WIN * TW, bb = x & 63;
             const u64 lo = words[t] >> bb, hi = bb ? words[t + 1] << (64 - bb) : 0ull;
             const uint32_t fb = (uint32_t)(lo | hi);
             uint32_t o4[4];
@@ -1260,11 +1186,11 @@ k_ccl_crop_rows(const uint8_t* __restrict__ img, const ipp_image_desc* __restric
             }
         }
         if (!more) break;
-        if (!IPP_CCL_CROP_PF) load(nx, vn, wn);
+        if (!IPP_CCL_CROP_PF) load(nx, vn, wn, xn);
         cur = nx;
 #pragma unroll
         for (int i = 0; i < 4; ++i) vc[i] = vn[i];
-        if (cur.seg == 0) wc = wn;
+        if (new_window(cur)) wc = wn, xc = xn;
     }
 }
 
@@ -1410,14 +1336,8 @@ extern "C" int ipp_video_keep_largest(const uint8_t* frames, const ipp_image_des
     if (rc != IPP_OK) return rc;
     hipLaunchKernelGGL(k_ccl_inwords, L.group_grid, dim3(64 * WAVES), 0, s, descs, works, scratch, bbox,
                        L.groups_per_img, L.groups_x);
-    // k_ccl_crop_rows holds a row's mask words one per lane: frames wider than
-    // 64 tile columns take the item stream, which has no width limit
-    if (IPP_CCL_CROP_ROWS && L.tiles_x <= CROP_ROWS_MAX_TILES_X)
-        hipLaunchKernelGGL(k_ccl_crop_rows, dim3((uint32_t)((int64_t)CROP_ROW_BLOCKS * n_images)), dim3(256), 0, s,
-                           frames, descs, works, scratch, bbox, out, out_descs);
-    else
-        hipLaunchKernelGGL(k_ccl_crop_stream, dim3((uint32_t)((int64_t)CROP_BLOCKS * n_images)), dim3(256), 0, s,
-                           frames, descs, works, scratch, bbox, out, out_descs);
+    hipLaunchKernelGGL(k_ccl_crop_rows, dim3((uint32_t)((int64_t)CROP_ROW_BLOCKS * n_images)), dim3(256), 0, s,
+                       frames, descs, works, scratch, bbox, out, out_descs);
     IPP_CHECK_LAUNCH();
     return IPP_OK;
 }

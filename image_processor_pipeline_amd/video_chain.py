@@ -32,6 +32,11 @@ class VideoChain:
 
     def __init__(self, n: int, h: int, w: int, device, ranges: Optional[Sequence] = None, zones=None,
                  use_gimp_scale: bool = False):
+        # ipp_video_keep_largest's crop addresses a frame through one buffer
+        # resource with 32-bit offsets (include/ipp.h: h·pitch + 18 < 2^32),
+        # and cannot check it: its descriptors are in device memory
+        if 3 * w * h + 18 >= 1 << 32:
+            raise ValueError(f"frames of {w}x{h} BGR ({3 * w * h} bytes) are too large: a frame must stay below 4 GiB")
         self.n, self.h, self.w = n, h, w
         self.device = torch.device(device)
         self.lib = N.load()

@@ -990,7 +990,12 @@ int ipp_ccl_keep_largest(uint8_t* img, const ipp_image_desc* descs, int32_t n_im
  * components → keep the largest → crop-fit (pixels_isolés.py:29-81), written
  * as BGRA (α 255 inside the component, 0 elsewhere) at out_descs[i] (the
  * slot must hold the whole frame).  bbox as above; a frame with no kept pixel
- * gets bbox (-1,...) and no output (the reference raises there). */
+ * gets bbox (-1,...) and no output (the reference raises there).  Frames of
+ * any width; each frame's h·pitch + 18 must be below 2^32: the crop addresses
+ * a frame through one buffer resource (32-bit offsets from the 16-byte
+ * boundary below the frame to the dword holding its last byte).  NOT checked
+ * here, the descriptors being in device memory: a larger frame is cropped
+ * wrongly without an error. */
 int ipp_video_keep_largest(const uint8_t* frames, const ipp_image_desc* descs, int32_t n_images,
                            int32_t max_w, int32_t max_h, const ipp_hsv_params* hsv,
                            const ipp_ccl_work* works, uint8_t* scratch, int64_t max_ent,

@@ -168,7 +168,8 @@ def test_all_open_4097x4099(C):
 
 def test_all_open_fused_chain(C):
     """The same 4097×4099 content through the fused chain (HSV mask of two
-    flat colours): k_ccl_inwords and k_ccl_crop_stream in all-open mode."""
+    flat colours): k_ccl_inwords and k_ccl_crop_rows in all-open mode (65
+    tile columns, the crop inside the 32nd)."""
     from image_processor_pipeline_amd import geometry as G
     from image_processor_pipeline_amd.video_chain import VideoChain
     case = R.big_all_open()

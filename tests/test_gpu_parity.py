@@ -704,11 +704,12 @@ def _wide_frames(kind, h, w, rng):
 
 
 def test_video_chain_wide_frames_vs_oracle(D):
-    """Frames wider than 4096 px (more than 64 tile columns): the fused
-    chain's crop-fit is then k_ccl_crop_stream (k_ccl_crop_rows holds a row's
-    mask words one per lane, 64 at the most, and is launched only up to 4096
-    px; this test is the stream kernel's only coverage).  Widths 4100 (65 tile
-    columns), 4416 (69) and 7680 (8K, 120), two frames of 70 rows (two tile
+    """Frames wider than 4096 px (more than 64 tile columns): k_ccl_crop_rows
+    holds a row's mask words one per lane, 64 to a window, so these rows take
+    a second window (the crops here start on a tile boundary or, the noise,
+    at column 0 or next to it: test_video_chain_word_window_seams_vs_oracle
+    has those that start off one).  Widths 4100 (65 tile columns), 4416 (69)
+    and 7680 (8K, 120), two frames of 70 rows (two tile
     rows, more crop rows than one block's four waves), bit-exact against the
     oracle: dense noise whose kept set percolates (the crop spans more than
     0.9 of the width; reference-only shares 1.000, 1.000 and 1.000); a kept
@@ -746,6 +747,67 @@ def test_video_chain_wide_frames_vs_oracle(D):
                 chain.run_staged(frd)
                 staged = chain.results()
                 assert all(np.array_equal(a, b) for a, b in zip(staged, res))
+
+
+_CROP_WIN = 4096    # k_ccl_crop_rows' mask-word window (ipp_ccl.hip CROP_WIN), in output pixels
+
+
+def _seam_frames(h, w, c0, c1):
+    """Two h×w frames of test_video_chain_word_window_seams_vs_oracle: a kept
+    band of 5 rows over columns c0 .. c1 (rows 61-65 across the two tile rows
+    in frame 0, 40-44 in frame 1) and a smaller kept rectangle to be removed.
+    The band's row 0 holds single kept pixels only (returned: how many): at
+    c0 and c1 and at s - 1, s, s + 1 for every window seam s = c0 + k·4096
+    inside the band.  Rows 1 and 4 are whole; rows 2 and 3 have a 2-column
+    hole across every seam, across the multiples of 64 on either side of it
+    and across the band's last one, so a mask word of the wrong window or tile
+    column changes the α there."""
+    fr = np.empty((2, h, w, 3), np.uint8)
+    fr[:] = _DROP
+    seams = list(range(c0 + _CROP_WIN, c1 + 1, _CROP_WIN))
+    top = sorted({c0, c1} | {s + k for s in seams for k in (-1, 0, 1)})
+    holes = sorted({m for s in seams for m in (s, s // 64 * 64, s // 64 * 64 + 64)} | {c1 // 64 * 64})
+    for i, y0 in enumerate((61, 40)):
+        fr[i, y0 + 1:y0 + 5, c0:c1 + 1] = _KEEP
+        fr[i, y0, top] = _KEEP
+        for m in holes:
+            fr[i, y0 + 2:y0 + 4, m - 1:m + 1] = _DROP
+        fr[i, 10:30, 100:170] = _KEEP
+    return fr, len(top)
+
+
+def test_video_chain_word_window_seams_vs_oracle(D):
+    """k_ccl_crop_rows keeps a row's mask words in LDS as a window of 4096
+    output pixels, one lane per word, re-based at the window's first tile
+    column; a window that starts off a tile boundary meets 65 tile columns and
+    fetches the 65th word apart.  Frames of 70 rows, two per chain, bit-exact
+    against the oracle (_seam_frames): 4096 px with the band over all of it
+    (one window of 64 tile columns: the control); 4224 px, band 63 .. 4158 (one
+    window of 65 tile columns); 8320 px, band o .. 8318 for o = 0, 1 and 63
+    (three windows, seams at o + 4096 and o + 8192, the last one partial; off a
+    tile boundary for o = 1 and 63, where the first two meet 65 tile columns).
+    With the 65th word's fetch disabled in a scratch build, the o = 1 and o =
+    63 cases and the 4224-px one fail and the control passes."""
+    from image_processor_pipeline_amd import geometry as G
+    from image_processor_pipeline_amd.video_chain import VideoChain
+    n, h = 2, 70
+    for w, bands in ((4096, [(0, 4095)]), (4224, [(63, 4158)]), (8320, [(o, 8318) for o in (0, 1, 63)])):
+        chain = VideoChain(n, h, w, DEV)
+        for c0, c1 in bands:
+            fr, n_top = _seam_frames(h, w, c0, c1)
+            assert n_top == 2 + 3 * ((c1 - c0) // _CROP_WIN)
+            chain.out.fill_(7)
+            chain.run(_t(fr))
+            res = chain.results()
+            for i, y0 in enumerate((61, 40)):
+                exp = ops.keep_largest_component(ops.color_mask_bgra(fr[i], G.REFERENCE_HSV_RANGES))
+                # the reference's crop is the band: bx0 = c0 (off the tile
+                # grid as intended), its top row the single pixels alone
+                assert exp.shape[:2] == (5, c1 - c0 + 1) and np.array_equal(exp[..., :3], fr[i, y0:y0 + 5, c0:c1 + 1])
+                assert c0 % 64 in (0, 1, 63) and (c1 - c0) // 64 + 1 >= 64
+                assert int((exp[0, :, 3] != 0).sum()) == n_top and exp[1, :, 3].all() and exp[4, :, 3].all()
+                assert not exp[2:4, :, 3].all()
+                assert res[i] is not None and res[i].shape == exp.shape and np.array_equal(res[i], exp), (w, c0, i)
 
 
 def _tail_frames(n, h, w, rng):

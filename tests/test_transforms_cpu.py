@@ -135,6 +135,31 @@ def test_device_path_fails_loudly_without_gpu(tmp_path):
         recadrages.crop_from_border(q, [tmp_path], crop_margins=(1, 1, 1, 1))
 
 
+def test_video_chain_refuses_frames_of_4_gib(monkeypatch):
+    """ipp_video_keep_largest's crop addresses a frame with 32-bit offsets
+    (include/ipp.h: h·pitch + 18 < 2^32) and cannot check it; VideoChain
+    does, before it loads the library or allocates anything.  8K frames of
+    186 500 rows are refused, and so is the first size past the bound; the
+    largest below it (3·w·h = 2^32 - 19) gets as far as the library."""
+    from image_processor_pipeline_amd import video_chain
+
+    class Reached(Exception):
+        pass
+
+    def load():
+        raise Reached
+
+    monkeypatch.setattr(video_chain.N, "load", load)
+    with pytest.raises(ValueError, match="4 GiB"):
+        video_chain.VideoChain(1, 186_500, 7680, "cuda:0")
+    wh = (2 ** 32 - 19) // 3
+    assert 3 * wh + 18 == 2 ** 32 - 1
+    with pytest.raises(ValueError, match="4 GiB"):
+        video_chain.VideoChain(1, 1, wh + 1, "cuda:0")
+    with pytest.raises(Reached):
+        video_chain.VideoChain(1, 1, wh, "cuda:0")
+
+
 def test_change_label_class_reference_kat(tmp_path, capsys):
     """labels.py's own known-answer check (:67-128) with its intended call
     (cls_mapping=, output dir created); as written it passes
