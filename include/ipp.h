@@ -289,7 +289,29 @@ typedef struct ipp_pipe_desc {
  * T is allocated for t_groups(rows, nkb) row groups per item
  * (csrc/ipp_pipe_layout.h): its rows past h.lines may hold anything (they
  * are read, but every tap there is zero), and so may the padding of its pitch
- * (never read).  tests/test_gpu_vblend_direct.py relies on exactly this. */
+ * (never read).  tests/test_gpu_vblend_direct.py relies on exactly this.
+ * What the H launch (ipp_pipe_hpass, ipp_pipe_hpass_bgcopy and _trim) reads of
+ * an ipp_pipe_desc: of g, src_off, src_pitch, src_cn (= the src_cn argument),
+ * src_h (with in_x0 / in_y0 it bounds the loads: src must hold src_h·src_pitch
+ * bytes from src_off), the crop window in_x0, in_y0, in_w, in_h, the map a0..a5,
+ * out_w, out_h, off_x, off_y and flip; with prepared = 1, base_off, lim and
+ * b[6] stand in for src_off, the map, off_x, off_y and flip (the crop window
+ * and src_h still bound the loads, out_w and out_h still size the HSV zones); of h,
+ * dst_off and dst_pitch (the item's T in tmp, 16-B aligned, pitch a multiple of
+ * 16 and ≥ 16·out_len), out_len, lines, line0 and coef_off (its H tap tiles:
+ * phase 0, shift 0); with copy blocks all of p but ov_off and ov_pitch; nothing
+ * of v, and of g neither src_w nor the dst fields, of h neither in_len nor
+ * ksize.  The T bytes of an item fall in three classes:
+ *   1. T rows [0, lines) × columns [0, out_len) are written and specified: row
+ *      r, column x', channel c holds clip8((2^21 + Σ_j M[line0 + r][xmin + j][c]
+ *      ·k_j) >> 22) ^ 0x80 at dst_off + (r / 4)·dst_pitch + 16·x' + 4·c + r % 4
+ *      (with a trim table, the groups it marks constant are left unstored);
+ *   2. rows [lines, 16·⌈lines / 16⌉) of the same columns are written (a block
+ *      stores whole 16-B groups of its 16-row band) and may hold anything;
+ *   3. no other byte of tmp is written: not the padding of the pitch past
+ *      16·out_len, not the row groups from 4·⌈lines / 16⌉ on, nothing between
+ *      two items' T and nothing of a descriptor outside the launch's range.
+ * tests/test_gpu_hpass_direct.py relies on exactly this. */
 int ipp_pipe_hpass_bgcopy(const uint8_t* src, uint8_t* tmp, const int32_t* coefs,
                           const ipp_pipe_desc* descs, int32_t n_images,
                           int32_t max_out_w, int32_t max_rows, int32_t src_cn,
