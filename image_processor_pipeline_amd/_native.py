@@ -128,6 +128,11 @@ IPP_FEED_MAX_SIDE = 1 << 23      # largest background side of ipp_scene_feed_tar
 IPP_FEED_MAX_TARGETS = 1 << 20   # most overlays (and descriptors) of one ipp_scene_feed_targets call (ipp.h)
 IPP_FEED_RESIZE_MAX_KSIZE = 128  # largest ksize of either axis of ipp_scene_feed_resize (ipp.h)
 IPP_FEED_RESIZE_LDS_BYTES = 1 << 16   # LDS budget of one ipp_scene_feed_resize workgroup (ipp.h)
+IPP_JPEG_420, IPP_JPEG_444 = 0, 1   # ipp_jpeg_encode's samplings (ipp.h)
+IPP_JPEG_HDR = 2                    # int32 words {bytes, status} of one ipp_jpeg_encode header (ipp.h)
+IPP_JPEG_OVERFLOW = 1               # status: the data are longer than capacity, nothing of the slot was written (ipp.h)
+IPP_JPEG_MAX_SIDE = 16384
+IPP_JPEG_MAX_CAPACITY = (1 << 31) - 16
 IPP_RESAMPLE = dict(box=0, bilinear=1, hamming=2, bicubic=3, lanczos=4)   # ipp_plan_resample's filter codes (ipp.h)
 PT = dict(coef_words=0, tmp_bytes=1, max_out_w=2, max_rows=3, max_ov_w=4, max_ov_h=5, algo_h=6, algo_v=7,
           copy_bytes=8, max_tiles=9, err_item=10, err_code=11, copy_reads=12)
@@ -183,6 +188,9 @@ SIGNATURES = {
     "ipp_scene_feed_resize": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "ipp_scene_feed_resize_lds": (_L, [_I, _I, _I, _I, _I, _I, _I, _P]),
     "ipp_scene_feed_index_map_sampled": (_I, [_P, _L, _I, _I, _P, _I, _I, _P, _P, _I, _I, _P, _L, _P]),
+    "ipp_jpeg_scratch_bytes": (_L, [_I, _I, _I, _I, _L]),
+    "ipp_jpeg_encode": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _L, _P, _P]),
+    "ipp_jpeg_pack": (_I, [_P, _L, _P, _I, _P, _P, _P]),
     "ipp_plan_lanczos": (_L, [_I, _D, _D, _I, _P, _L]),
     "ipp_plan_resample": (_L, [_I, _I, _D, _D, _I, _P, _L]),
     "ipp_plan_lanczos_ksize": (_I, [_D, _D, _I]),

@@ -131,7 +131,8 @@ def keep_largest(imgs: Sequence[np.ndarray]) -> List[Optional[np.ndarray]]:
 
 
 def overlays(ovs: Sequence[np.ndarray], bgs: Sequence[np.ndarray], sizes: Sequence[Tuple[int, int]],
-             pos: Sequence[Tuple[int, int]], bbox_alpha_min: Optional[int] = None):
+             pos: Sequence[Tuple[int, int]], bbox_alpha_min: Optional[int] = None,
+             jpeg: Optional[Sequence[bool]] = None):
     """overlays.py:129-139 for a chunk: LANCZOS resize of each RGBA overlay
     to sizes[i] = (w, h) (RGBa round trip) and paste onto its RGB background
     at pos[i] — ipp_lanczos_h + ipp_lanczos_v + ipp_paste_blend, one launch
@@ -140,8 +141,13 @@ def overlays(ovs: Sequence[np.ndarray], bgs: Sequence[np.ndarray], sizes: Sequen
     ``bbox_alpha_min`` (1..255) it returns (composites, boxes): boxes[i] =
     the box (x0, y0, x1, y1), in overlay coordinates, of the resized overlay's
     pixels with alpha >= bbox_alpha_min, or None when there is none
-    (ipp_alpha_bbox_min, one more launch over the chunk's resized overlays)."""
+    (ipp_alpha_bbox_min, one more launch over the chunk's resized overlays).
+    ``jpeg[i]`` true: composite i comes back as the bytes of its JPEG file
+    (Pillow's ``save`` defaults: quality 75, 4:2:0), encoded on the device
+    (jpeg.encode_grouped) — its pixels are not copied back."""
     from .device import alpha_bbox_min, alpha_bbox_min_packed, check_alpha_min, paste_blend, resize_lanczos_rgba
+    from .jpeg import encode_grouped
+    as_jpeg = [bool(jpeg[i]) if jpeg is not None else False for i in range(len(ovs))]
     tight = bbox_alpha_min is not None
     if tight:
         bbox_alpha_min = check_alpha_min(bbox_alpha_min)
@@ -156,7 +162,8 @@ def overlays(ovs: Sequence[np.ndarray], bgs: Sequence[np.ndarray], sizes: Sequen
         rs = resize_lanczos_rgba(_rt.h2d(ovs[i]), *sizes[i])
         if tight:
             boxes[i] = alpha_bbox_min([rs], bbox_alpha_min)[0]
-        res[i] = _rt.d2h(paste_blend(_rt.h2d(bgs[i]), rs, *pos[i]))
+        comp = paste_blend(_rt.h2d(bgs[i]), rs, *pos[i])
+        res[i] = encode_grouped([comp])[0] if as_jpeg[i] else _rt.d2h(comp)
     if not both:
         return (res, boxes) if tight else res
     ov_buf, ooffs = _pack([ovs[i] for i in both])
@@ -222,6 +229,12 @@ def overlays(ovs: Sequence[np.ndarray], bgs: Sequence[np.ndarray], sizes: Sequen
     if tight:
         for i, b in zip(both, alpha_bbox_min_packed(rsb, roffs, rs_shapes, bbox_alpha_min)):
             boxes[i] = b
-    for i, c in zip(both, _unpack(out, coffs, out_shapes)):
-        res[i] = c
+    coded = [k for k, i in enumerate(both) if as_jpeg[i]]
+    views = [out[coffs[k]:coffs[k] + int(np.prod(out_shapes[k]))].view(out_shapes[k]) for k in coded]
+    for k, data in zip(coded, encode_grouped(views)):
+        res[both[k]] = data
+    if len(coded) < len(both):
+        for i, c in zip(both, _unpack(out, coffs, out_shapes)):
+            if not as_jpeg[i]:
+                res[i] = c
     return (res, boxes) if tight else res

@@ -4,8 +4,11 @@ The reference reads/writes files with ``cv2.imread``/``cv2.imwrite`` (BGR
 order; ``IMREAD_COLOR`` drops alpha, ``IMREAD_UNCHANGED`` keeps it) and with
 Pillow (RGB order).  OpenCV is not installed in this image, so the cv2-style
 helpers below are implemented on Pillow's codecs with the same channel
-conventions.  PNG is lossless, so pixel parity holds; JPEG payloads may differ
-in bytes from libjpeg-turbo as used by OpenCV (quality 95 is OpenCV's default).
+conventions.  PNG is lossless, so pixel parity holds; JPEG payloads written
+here may differ in bytes from libjpeg-turbo as used by OpenCV (quality 95 is
+OpenCV's default).  (The composites' JPEG files are another matter: jpeg.py
+encodes them on the device to exactly the bytes Pillow's ``save`` writes; these
+helpers are not routed through it.)
 Codec work is host CPU work and sits outside the device hot path.
 """
 from __future__ import annotations

@@ -24,6 +24,7 @@ from .. import _rt
 from .. import batch_ops as BO
 from .. import device as D
 from .. import geometry as G
+from ..jpeg import encode_grouped
 from ..labels_math import xyxy2xywhn
 from ..utils import utils
 
@@ -50,6 +51,21 @@ def _label_str(yolo_class_id: int, box: Optional[Tuple[int, int, int, int]], pos
     return f"{yolo_class_id} {cx:.6f} {cy:.6f} {w_norm:.6f} {h_norm:.6f}"
 
 
+def _is_jpeg(path: Path) -> bool:
+    return path.suffix.lower() in (".jpg", ".jpeg")
+
+
+def _save_composite(comp, path: Path) -> None:
+    """overlays.py:169 — or the bytes of the file, where the device encoded it."""
+    if isinstance(comp, bytes):
+        with open(path, "wb") as f:
+            f.write(comp)
+    elif isinstance(comp, Image.Image):
+        comp.save(path)
+    else:
+        Image.fromarray(comp, "RGB").save(path)
+
+
 @device_transform
 def paste_overlay_onto_background(
     overlay_path: Path,
@@ -60,9 +76,14 @@ def paste_overlay_onto_background(
     scale_max: float = 0.30,
     tight_bbox: bool = False,
     alpha_min: int = 1,
+    device_jpeg: bool = False,
     **options: Any,
 ) -> Optional[List[Path]]:
-    """``tight_bbox`` (not in the reference): the label's box is that of the
+    """``device_jpeg`` (not in the reference): where the output suffix is
+    ``.jpg`` / ``.jpeg`` the composite is encoded on the device (jpeg.py: the
+    same bytes ``save`` writes) and only the file's bytes are copied back; any
+    other suffix is saved on the host as before.
+    ``tight_bbox`` (not in the reference): the label's box is that of the
     resized overlay's pixels with alpha >= ``alpha_min`` (1..255) instead of
     its whole rectangle; an overlay without such a pixel gets an empty label
     file (the YOLO convention for an image without objects).  The draws, the
@@ -98,7 +119,10 @@ def paste_overlay_onto_background(
         pos_x = random.randint(0, bw - new_w)
         pos_y = random.randint(0, bh - new_h)
         comp = D.paste_blend(_rt.h2d(np.asarray(background)), resized, pos_x, pos_y)
-        composite_image = Image.fromarray(_rt.d2h(comp), "RGB")
+        if device_jpeg and _is_jpeg(background_path):
+            composite_image = encode_grouped([comp])[0]
+        else:
+            composite_image = Image.fromarray(_rt.d2h(comp), "RGB")
         tight = D.alpha_bbox_min([resized], alpha_min)[0] if tight_bbox else (0, 0, new_w, new_h)
         yolo_label_str = _label_str(yolo_class_id, tight, pos_x, pos_y, bw, bh)
     except ValueError as ve:
@@ -112,7 +136,7 @@ def paste_overlay_onto_background(
     img_output_path = Path(image_target_dir) / f"{overlay_path.stem}{background_path.suffix}"
     label_output_path = Path(label_target_dir) / f"{overlay_path.stem}.txt"
     try:
-        composite_image.save(img_output_path)
+        _save_composite(composite_image, img_output_path)
         saved_paths.append(img_output_path)
         with open(label_output_path, "w", encoding="utf-8") as f:
             f.write(yolo_label_str)
@@ -131,14 +155,16 @@ def paste_overlay_onto_background(
 
 def _overlays_batch(arg_tuples, output_dirs: List[Path], threads: int = 1, yolo_class_id: int = 0,
                     scale_min: float = 0.15, scale_max: float = 0.30, tight_bbox: bool = False,
-                    alpha_min: int = 1, **options: Any) -> List:
+                    alpha_min: int = 1, device_jpeg: bool = False, **options: Any) -> List:
     """Batched paste_overlay_onto_background ('modulo' pairs): decode on host
     threads, the per-item draws (uniform ratio, then two randint) in pair
     order, ONE batched LANCZOS H + V + paste launch set for the chunk
     (batch_ops.overlays), encode + label on host threads.  Messages and
     None results as in the per-file path.  ``tight_bbox``: the boxes come
     from one more batched launch over the chunk's resized overlays
-    (ipp_alpha_bbox_min)."""
+    (ipp_alpha_bbox_min).  ``device_jpeg``: the composites whose output
+    suffix is ``.jpg`` / ``.jpeg`` are encoded on the device in the same chunk
+    and only their files' bytes come back."""
     image_target_dir, label_target_dir = utils._validate_dirs(output_dirs, nb_dirs=2)
 
     def load(args):
@@ -161,7 +187,7 @@ def _overlays_batch(arg_tuples, output_dirs: List[Path], threads: int = 1, yolo_
         return None
 
     def compute(items, args):
-        plans, ovs, bgs, sizes, pos = [], [], [], [], []
+        plans, ovs, bgs, sizes, pos, jpeg = [], [], [], [], [], []
         for item, a in zip(items, args):
             if item is None:
                 plans.append(None)
@@ -191,16 +217,17 @@ def _overlays_batch(arg_tuples, output_dirs: List[Path], threads: int = 1, yolo_
             bgs.append(bg)
             sizes.append((new_w, new_h))
             pos.append((pos_x, pos_y))
+            jpeg.append(device_jpeg and _is_jpeg(a[1]))
         if tight_bbox:
             try:
-                comps, boxes = BO.overlays(ovs, bgs, sizes, pos, bbox_alpha_min=alpha_min) if ovs else ([], [])
+                comps, boxes = BO.overlays(ovs, bgs, sizes, pos, bbox_alpha_min=alpha_min, jpeg=jpeg) if ovs else ([], [])
             except ValueError as ve:   # (alpha_min out of range: every pair fails as in the per-file path)
                 for p, a in zip(plans, args):
                     if p is not None:
                         print(f"Erreur de valeur [{a[0].name} + {a[1].name}]: {ve}")
                 return [None] * len(plans)
         else:
-            comps = BO.overlays(ovs, bgs, sizes, pos) if ovs else []
+            comps = BO.overlays(ovs, bgs, sizes, pos, jpeg=jpeg) if ovs else []
             boxes = [(0, 0, w, h) for w, h in sizes]
         return [None if p is None else (comps[p[0]], p, boxes[p[0]]) for p in plans]
 
@@ -215,7 +242,7 @@ def _overlays_batch(arg_tuples, output_dirs: List[Path], threads: int = 1, yolo_
         img_output_path = Path(image_target_dir) / f"{overlay_path.stem}{background_path.suffix}"
         label_output_path = Path(label_target_dir) / f"{overlay_path.stem}.txt"
         try:
-            Image.fromarray(comp, "RGB").save(img_output_path)
+            _save_composite(comp, img_output_path)
             saved_paths.append(img_output_path)
             with open(label_output_path, "w", encoding="utf-8") as f:
                 f.write(yolo_label_str)

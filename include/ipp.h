@@ -1234,6 +1234,95 @@ int ipp_box_pass(const uint8_t* src, uint8_t* dst, const ipp_enhance_desc* descs
                  int32_t final_dst, void* stream);
 
 /* ------------------------------------------------------------------------ */
+/* Baseline JPEG of RGB composites, encoded on the device                     */
+/* ------------------------------------------------------------------------ */
+/* The entropy-coded data of the file Pillow 12.2.0 (libjpeg-turbo 3.1) writes
+ * for Image.fromarray(a).save(path, quality=q[, subsampling=0]) of an 8-bit
+ * RGB image: baseline sequential, the Annex K Huffman tables, one scan, no
+ * restart markers.  The header (SOI, APP0 JFIF, DQT x 2, SOF0, DHT x 4, SOS)
+ * and the EOI are the host's (image_processor_pipeline_amd/jpeg.py).  This
+ * project's normative definition, in exact integers (tests/jpeg_refs.py is
+ * its restatement, held to the installed Pillow byte for byte):
+ *
+ * TABLES.  Quality q in 1..100 scales the two Annex K.1/K.2 tables t by s =
+ * 5000 / q (q < 50) or 200 - 2q: (t·s + 50) / 100 clamped to 1..255.  The
+ * caller passes the 2 x 64 results (luma, chroma; row-major, not zigzag).
+ * COLOUR (jccolor.c, 16-bit fixed point, arithmetic >> 16):
+ *   Y  = ( 19595 R + 38470 G +  7471 B + 32768) >> 16
+ *   Cb = (-11059 R - 21709 G + 32768 B + 128·65536 + 32767) >> 16
+ *   Cr = ( 32768 R - 27439 G -  5329 B + 128·65536 + 32767) >> 16
+ * SAMPLING.  IPP_JPEG_444: three full-resolution components, MCU = 8 x 8 px,
+ * blocks Y Cb Cr.  IPP_JPEG_420 (Pillow's default): Cb and Cr halved both
+ * ways, MCU = 16 x 16 px, blocks Y00 Y01 Y10 Y11 Cb Cr.  A chroma sample is
+ * (a + b + c + d + bias) >> 2 over its 2 x 2 converted pixels, bias 1 for an
+ * even chroma column and 2 for an odd one.
+ * EDGES, two kinds.  (1) Replication: a component has ⌈size / 8⌉ blocks each
+ * way (size = w, h for full resolution; ⌈w / 2⌉, ⌈h / 2⌉ for 4:2:0 chroma).
+ * Full-resolution samples past the image repeat its last column and row.  For
+ * 4:2:0 chroma the order matters, and is libjpeg's: pixel columns past w
+ * repeat the last one *before* the downsample (so the bias still alternates);
+ * pixel rows are repeated only to an even count (row 2cy + 1 = h reads row
+ * h - 1); chroma rows past ⌈h / 2⌉ repeat the last *chroma* row — which, for
+ * an even h, is not the downsample of a repeated pixel row.  (2) Dummy blocks:
+ * a 4:2:0 luma block of an MCU that lies past the luma grid (w mod 16 in
+ * 1..8: Y01, Y11; h mod 16 in 1..8: Y10, Y11) is not made of pixels: its AC
+ * terms are 0 and its DC is the DC of the block before it in the MCU; in a
+ * dummy bottom row both blocks take Y01's (jccoefct.c).
+ * TRANSFORM (jfdctint.c "islow", CONST_BITS 13, PASS1_BITS 2, int32) of the
+ * samples - 128, rows then columns; the result is 8 x the DCT.
+ * QUANTISATION.  coef / (8·q), halves away from zero: sign · ((|coef| + 4q)
+ * / 8q).  (The kernels divide by the reciprocal floor(2^26 / 8q) + 1, exact
+ * for every operand below 2^26 / 8q, so below 2^15; |coef| <= 8·1024 plus the
+ * passes' rounding.)
+ * CODING.  Zigzag order; DC as the difference to the previous block of the
+ * same component in the scan (0 for the first; dummy blocks count), category
+ * = bit length of |v|, magnitude bits v (v >= 0) or v - 1 (v < 0); AC as
+ * (run << 4 | category) with 0xF0 for each 16 zeros before a nonzero term and
+ * 0x00 (EOB) when the block ends in zeros.  Bits are MSB first; the last byte
+ * is filled with 1-bits; every 0xFF byte, that one included, is followed by a
+ * 0x00 (counted in the sizes below).
+ *
+ * ipp_jpeg_encode: in = n_images x h x w x 3 contiguous uint8 RGB (what the V
+ * launches leave).  Image i's data go to slots + i·pitch16(capacity), where
+ * pitch16 rounds up to 16 B; hdr (device int32[n_images][IPP_JPEG_HDR])
+ * receives {bytes, status}.  status 0: exactly `bytes` bytes were written to
+ * the slot and nothing else of it.  status IPP_JPEG_OVERFLOW: the data are
+ * longer than capacity, NO byte of the slot was written, and `bytes` is the
+ * length found so far (the stuffed length, or the unstuffed one where that
+ * alone exceeds capacity), saturated to 2^31 - 1.  Whether an image fits is
+ * known after the scans and before any write to its slot.  Every header word
+ * is written.  qtab: HOST uint16[2][64], read before the call returns.
+ * ipp_jpeg_pack, after it on the same stream: copies image i's `bytes` bytes
+ * to out + offsets[i] (device int64[n_images], computed by the caller from
+ * the copied-back headers) for every image with status 0; writes nothing for
+ * the others and nothing else.
+ * No float anywhere.  The only atomic is an integer OR that merges the two
+ * words a block's bits may share with its neighbours' in the zeroed unstuffed
+ * stream: the result does not depend on any order.
+ * scratch: device, 16-B aligned, ipp_jpeg_scratch_bytes(...) bytes, each part
+ * rounded up to 256 B: per image and block 64 int16 coefficients (zigzag) and
+ * a uint64 (AC bit length, then bit offset); per image a 16-B record, the
+ * unstuffed stream (pitch16(capacity) + 16 B) and a uint32 per 4096 B of it.
+ * Blocks per image: 6·⌈w / 16⌉·⌈h / 16⌉ or 3·⌈w / 8⌉·⌈h / 8⌉.
+ * IPP_E_ARG, before any launch: a NULL pointer; scratch or slots not 16-B,
+ * offsets not 8-B, hdr not 4-B aligned; w or h outside 1..IPP_JPEG_MAX_SIDE;
+ * another sampling; capacity outside 1..IPP_JPEG_MAX_CAPACITY; a table entry
+ * outside 1..255; n_images negative or > 65535 (the grid).  n_images == 0 is
+ * IPP_OK, launches and writes nothing. */
+#define IPP_JPEG_420 0
+#define IPP_JPEG_444 1
+#define IPP_JPEG_HDR 2
+#define IPP_JPEG_OVERFLOW 1
+#define IPP_JPEG_MAX_SIDE 16384
+#define IPP_JPEG_MAX_CAPACITY 2147483632 /* 2^31 - 16: sizes fit the int32 headers */
+int64_t ipp_jpeg_scratch_bytes(int32_t n_images, int32_t w, int32_t h, int32_t sampling, int64_t capacity);
+int ipp_jpeg_encode(const uint8_t* in, int32_t n_images, int32_t w, int32_t h, int32_t sampling,
+                    const uint16_t* qtab, uint8_t* scratch, uint8_t* slots, int64_t capacity, int32_t* hdr,
+                    void* stream);
+int ipp_jpeg_pack(const uint8_t* slots, int64_t capacity, const int32_t* hdr, int32_t n_images,
+                  const int64_t* offsets, uint8_t* out, void* stream);
+
+/* ------------------------------------------------------------------------ */
 /* Measurement helper (the copy-kernel ceiling of the box).     */
 /* ------------------------------------------------------------------------ */
 /* dst[0, nbytes) = src[0, nbytes) with 16-B non-temporal loads/stores; both
