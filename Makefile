@@ -8,7 +8,7 @@ SRCS := $(CSRC)/ipp_gather.hip $(CSRC)/ipp_hsv.hip $(CSRC)/ipp_resample.hip $(CS
         $(CSRC)/ipp_pipe_vblend.hip $(CSRC)/ipp_ccl.hip $(CSRC)/ipp_util.hip $(CSRC)/ipp_bilinear.hip \
         $(CSRC)/ipp_enhance.hip $(CSRC)/ipp_taps.hip $(CSRC)/ipp_label.hip $(CSRC)/ipp_contour.hip \
         $(CSRC)/ipp_simplify.hip $(CSRC)/ipp_obb.hip $(CSRC)/ipp_rle.hip $(CSRC)/ipp_feed.hip \
-        $(CSRC)/ipp_feed_resize.hip $(CSRC)/ipp_jpeg.hip
+        $(CSRC)/ipp_feed_resize.hip $(CSRC)/ipp_jpeg.hip $(CSRC)/ipp_jpeg_decode.hip
 HOST_SRCS := $(CSRC)/ipp_host.cpp $(CSRC)/ipp_plan.cpp
 HDRS := include/ipp.h $(wildcard $(CSRC)/*.h)
 OBJDIR := build/obj

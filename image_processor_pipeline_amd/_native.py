@@ -133,6 +133,18 @@ IPP_JPEG_HDR = 2                    # int32 words {bytes, status} of one ipp_jpe
 IPP_JPEG_OVERFLOW = 1               # status: the data are longer than capacity, nothing of the slot was written (ipp.h)
 IPP_JPEG_MAX_SIDE = 16384
 IPP_JPEG_MAX_CAPACITY = (1 << 31) - 16
+IPP_JPEGD_STAT = 4                  # int32 words {status, rounds, subsequences, marker status} per image of ipp_jpeg_decode (ipp.h)
+IPP_JPEGD_STATUS = {1: "a marker other than RSTn inside the entropy-coded data", 2: "RSTn markers out of order",
+                    3: "the wrong number of restart intervals", 4: "data that end in 0xFF", 5: "a code in no Huffman table",
+                    6: "a run past coefficient 63", 7: "a restart interval that ends early or with blocks missing"}
+IPP_JPEGD_MAX_SPAN = 1 << 30
+(IPP_JPEGD_BAD_MARKER, IPP_JPEGD_WRONG_RST, IPP_JPEGD_SEG_COUNT, IPP_JPEGD_TRUNCATED, IPP_JPEGD_BAD_CODE, IPP_JPEGD_RUN,
+ IPP_JPEGD_SEG_BLOCKS) = range(1, 8)
+JPEGD_DESC = np.dtype([
+    ("span_off", _I8), ("out_off", _I8), ("coef_off", _I8), ("sub_off", _I8), ("seg_off", _I8), ("span_len", _I4),
+    ("w", _I4), ("h", _I4), ("sampling", _I4), ("restart", _I4), ("out_pitch", _I4), ("qt", _I4, (3,)),
+    ("dc", _I4, (3,)), ("ac", _I4, (3,)), ("pad_", _I4),
+], align=True)
 IPP_RESAMPLE = dict(box=0, bilinear=1, hamming=2, bicubic=3, lanczos=4)   # ipp_plan_resample's filter codes (ipp.h)
 PT = dict(coef_words=0, tmp_bytes=1, max_out_w=2, max_rows=3, max_ov_w=4, max_ov_h=5, algo_h=6, algo_v=7,
           copy_bytes=8, max_tiles=9, err_item=10, err_code=11, copy_reads=12)
@@ -191,6 +203,8 @@ SIGNATURES = {
     "ipp_jpeg_scratch_bytes": (_L, [_I, _I, _I, _I, _L]),
     "ipp_jpeg_encode": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _L, _P, _P]),
     "ipp_jpeg_pack": (_I, [_P, _L, _P, _I, _P, _P, _P]),
+    "ipp_jpeg_decode_scratch_bytes": (_L, [_P, _I]),
+    "ipp_jpeg_decode": (_I, [_P, _L, _P, _P, _I, _P, _I, _P, _I, _P, _L, _P, _L, _P, _P]),
     "ipp_plan_lanczos": (_L, [_I, _D, _D, _I, _P, _L]),
     "ipp_plan_resample": (_L, [_I, _I, _D, _D, _I, _P, _L]),
     "ipp_plan_lanczos_ksize": (_I, [_D, _D, _I]),

@@ -34,6 +34,28 @@ def _pack(imgs: Sequence[np.ndarray], align: int = 16) -> Tuple[torch.Tensor, Li
     return host.to(_rt.device(), non_blocking=True), offs
 
 
+def _pack_mixed(imgs: Sequence, align: int = 16) -> Tuple[torch.Tensor, List[int]]:
+    """_pack for a list that may hold device tensors (backgrounds decoded on
+    the device) beside host arrays: the arrays go up in one copy, the tensors
+    are copied in on the device."""
+    if not any(isinstance(im, torch.Tensor) for im in imgs):
+        return _pack(imgs, align)
+    offs, total = [], 0
+    for im in imgs:
+        offs.append(total)
+        total += (int(np.prod(im.shape)) + align - 1) // align * align
+    host = torch.empty(max(total, align), dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+    hv = host.numpy()
+    for im, o in zip(imgs, offs):
+        if not isinstance(im, torch.Tensor):
+            hv[o:o + im.nbytes] = np.ascontiguousarray(im).reshape(-1).view(np.uint8)
+    buf = host.to(_rt.device(), non_blocking=True)
+    for im, o in zip(imgs, offs):
+        if isinstance(im, torch.Tensor):
+            buf[o:o + im.numel()].copy_(im.reshape(-1))
+    return buf, offs
+
+
 def _unpack(buf: torch.Tensor, offs: Sequence[int], shapes: Sequence[Tuple[int, ...]]) -> List[np.ndarray]:
     host = buf.cpu().numpy()
     return [host[o:o + int(np.prod(s))].reshape(s).copy() for o, s in zip(offs, shapes)]
@@ -135,7 +157,8 @@ def overlays(ovs: Sequence[np.ndarray], bgs: Sequence[np.ndarray], sizes: Sequen
              jpeg: Optional[Sequence[bool]] = None):
     """overlays.py:129-139 for a chunk: LANCZOS resize of each RGBA overlay
     to sizes[i] = (w, h) (RGBa round trip) and paste onto its RGB background
-    at pos[i] — ipp_lanczos_h + ipp_lanczos_v + ipp_paste_blend, one launch
+    at pos[i] (a background may be a device tensor (h, w, 3) uint8, as
+    jpeg.JpegDecoder leaves it) — ipp_lanczos_h + ipp_lanczos_v + ipp_paste_blend, one launch
     each for the items resized on both axes; one-axis and identity resizes
     (rare) take the per-image device path.  Returns the composites; with
     ``bbox_alpha_min`` (1..255) it returns (composites, boxes): boxes[i] =
@@ -162,12 +185,12 @@ def overlays(ovs: Sequence[np.ndarray], bgs: Sequence[np.ndarray], sizes: Sequen
         rs = resize_lanczos_rgba(_rt.h2d(ovs[i]), *sizes[i])
         if tight:
             boxes[i] = alpha_bbox_min([rs], bbox_alpha_min)[0]
-        comp = paste_blend(_rt.h2d(bgs[i]), rs, *pos[i])
+        comp = paste_blend(bgs[i] if isinstance(bgs[i], torch.Tensor) else _rt.h2d(bgs[i]), rs, *pos[i])
         res[i] = encode_grouped([comp])[0] if as_jpeg[i] else _rt.d2h(comp)
     if not both:
         return (res, boxes) if tight else res
     ov_buf, ooffs = _pack([ovs[i] for i in both])
-    bg_buf, boffs = _pack([bgs[i] for i in both])
+    bg_buf, boffs = _pack_mixed([bgs[i] for i in both])
     dev = ov_buf.device
     hd = np.zeros(len(both), N.RESAMPLE_DESC)
     vd = np.zeros(len(both), N.RESAMPLE_DESC)
@@ -203,7 +226,7 @@ def overlays(ovs: Sequence[np.ndarray], bgs: Sequence[np.ndarray], sizes: Sequen
         vd[k]["src_off"], vd[k]["dst_off"] = toffs[k], roffs[k]
     tmp = torch.empty(ttotal, dtype=torch.uint8, device=dev)
     rsb = torch.empty(rtotal, dtype=torch.uint8, device=dev)
-    out_shapes = [bgs[i].shape for i in both]
+    out_shapes = [tuple(bgs[i].shape) for i in both]
     coffs, ctotal = _layout(out_shapes)
     out = torch.empty(ctotal, dtype=torch.uint8, device=dev)
     for k, i in enumerate(both):

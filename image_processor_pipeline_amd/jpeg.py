@@ -10,12 +10,18 @@ the streams, and one more copy brings back exactly the files' bytes.
 
 Out of scope, refused by name: "4:2:2" and other samplings, greyscale and RGBA
 inputs, optimised Huffman tables, progressive files, restart markers, EXIF /
-ICC / dpi / comments, images of different sizes in one call, decoding.
+ICC / dpi / comments, images of different sizes in one call.
+
+The other way, ``parse_jpeg`` walks a file's markers (plain Python too) and
+``JpegDecoder`` decodes baseline files on the device to the pixels
+``Image.open(f).convert("RGB")`` gives (ipp.h: ipp_jpeg_decode); progressive,
+greyscale, CMYK, "4:2:2", 12-bit and multi-scan files are refused by name.
 """
 from __future__ import annotations
 
 from concurrent.futures import ThreadPoolExecutor
-from typing import List, Optional, Sequence, Tuple
+from dataclasses import dataclass
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -246,3 +252,312 @@ def encode_grouped(images: Sequence, quality: int = 75, subsampling: str = "4:2:
         for i, data in zip(idx, files):
             out[i] = data
     return out
+
+
+# ---- decoding ----------------------------------------------------------------
+@dataclass
+class JpegInfo:
+    """What parse_jpeg finds in a baseline file."""
+    w: int
+    h: int
+    subsampling: str                      # "4:2:0" or "4:4:4"
+    qt: Tuple[int, int, int]              # per component (Y, Cb, Cr): quantisation table id (SOF0)
+    dc: Tuple[int, int, int]              # DC Huffman table id (SOS)
+    ac: Tuple[int, int, int]              # AC Huffman table id (SOS)
+    qtables: Dict[int, np.ndarray]        # id -> 64 uint16, natural (row-major) order
+    htables: Dict[Tuple[int, int], Tuple[bytes, bytes]]   # (class 0 DC / 1 AC, id) -> (BITS, HUFFVAL)
+    restart_interval: int                 # MCUs, 0 for none
+    span: Tuple[int, int]                 # [start, end) of the entropy-coded data in the file
+
+
+_SOF_NAMES = {0xC1: "extended sequential (SOF1)", 0xC2: "progressive (SOF2)", 0xC3: "lossless (SOF3)",
+              0xC5: "differential sequential (SOF5)", 0xC6: "differential progressive (SOF6)",
+              0xC7: "differential lossless (SOF7)", 0xC9: "arithmetic coding (SOF9)",
+              0xCA: "progressive arithmetic coding (SOF10)", 0xCB: "lossless arithmetic coding (SOF11)",
+              0xCD: "differential arithmetic coding (SOF13)", 0xCE: "differential progressive arithmetic coding (SOF14)",
+              0xCF: "differential lossless arithmetic coding (SOF15)"}
+
+
+def parse_jpeg(data: bytes) -> JpegInfo:
+    """Walks the markers of a JPEG file; plain Python, no imaging library.
+    ValueError names what is out of scope for the device decoder: anything but
+    a baseline (SOF0) 8-bit YCbCr file sampled "4:2:0" or "4:4:4" with one
+    interleaved scan — or what is wrong with the header."""
+    data = bytes(data)
+    n = len(data)
+    if n < 4 or data[:2] != b"\xff\xd8":
+        raise ValueError("not a JPEG file (no SOI marker)" if n >= 2 else "truncated header: the file ends before SOI")
+    qtables: Dict[int, np.ndarray] = {}
+    htables: Dict[Tuple[int, int], Tuple[bytes, bytes]] = {}
+    restart, sof, adobe = 0, None, None
+    at = 2
+    while True:
+        if at + 4 > n:
+            raise ValueError("truncated header: the file ends before the scan (SOS)")
+        if data[at] != 0xFF:
+            raise ValueError(f"malformed header: no marker at byte {at}")
+        m = data[at + 1]
+        if m == 0xFF:               # fill byte
+            at += 1
+            continue
+        if m == 0xD8 or m == 0x01 or 0xD0 <= m <= 0xD7:
+            at += 2
+            continue
+        if m == 0xD9:
+            raise ValueError("truncated header: EOI before any scan")
+        ln = int.from_bytes(data[at + 2:at + 4], "big")
+        if ln < 2 or at + 2 + ln > n:
+            raise ValueError(f"truncated header: segment 0xFF{m:02X} runs past the end of the file")
+        body = data[at + 4:at + 2 + ln]
+        at += 2 + ln
+        if m == 0xDB:
+            k = 0
+            while k < len(body):
+                pq, tq = body[k] >> 4, body[k] & 15
+                if pq != 0:
+                    raise ValueError("16-bit quantisation tables are out of scope (baseline tables are 8-bit)")
+                if tq > 3 or k + 65 > len(body):
+                    raise ValueError("malformed header: bad DQT segment")
+                t = np.zeros(64, np.uint16)
+                for z in range(64):
+                    t[_ZIGZAG[z]] = body[k + 1 + z]
+                qtables[tq] = t
+                k += 65
+        elif m == 0xC4:
+            k = 0
+            while k < len(body):
+                tc, th = body[k] >> 4, body[k] & 15
+                if tc > 1 or th > 3 or k + 17 > len(body):
+                    raise ValueError("malformed header: bad DHT segment")
+                bits = body[k + 1:k + 17]
+                nv = sum(bits)
+                if nv > 256 or k + 17 + nv > len(body):
+                    raise ValueError("malformed header: bad DHT segment")
+                code = 0
+                for ln_ in range(16):
+                    code = (code + bits[ln_]) << 1
+                    if code > (2 << ln_ << 1):
+                        raise ValueError("malformed header: a DHT table that is no prefix code")
+                htables[(tc, th)] = (bytes(bits), bytes(body[k + 17:k + 17 + nv]))
+                k += 17 + nv
+        elif m == 0xC0:
+            if sof is not None:
+                raise ValueError("more than one frame header (SOF0) is out of scope")
+            sof = body
+        elif m in _SOF_NAMES:
+            raise ValueError(f"{_SOF_NAMES[m]} files are out of scope: the device decodes baseline (SOF0) only")
+        elif m == 0xCC:
+            raise ValueError("arithmetic coding (DAC) is out of scope")
+        elif m == 0xDD:
+            if len(body) != 2:
+                raise ValueError("malformed header: bad DRI segment")
+            restart = int.from_bytes(body, "big")
+        elif m == 0xEE and body[:5] == b"Adobe" and len(body) >= 12:
+            adobe = body[11]
+        elif m == 0xDA:
+            sos = body
+            break
+        # APPn, COM and anything else with a length: skipped
+    if sof is None:
+        raise ValueError("malformed header: a scan (SOS) before any frame header (SOF0)")
+    if len(sof) < 6:
+        raise ValueError("truncated header: short SOF0 segment")
+    if sof[0] != 8:
+        raise ValueError(f"{sof[0]}-bit precision is out of scope: the device decodes 8-bit files (12-bit is refused)")
+    h, w, nc = int.from_bytes(sof[1:3], "big"), int.from_bytes(sof[3:5], "big"), sof[5]
+    if nc == 1:
+        raise ValueError("greyscale files are out of scope: the device decodes three-component YCbCr")
+    if nc == 4:
+        raise ValueError("CMYK / four-component files are out of scope: the device decodes three-component YCbCr")
+    if nc != 3 or len(sof) < 6 + 3 * nc:
+        raise ValueError(f"{nc}-component files are out of scope: the device decodes three-component YCbCr")
+    if adobe is not None and adobe != 1:
+        raise ValueError(f"an Adobe APP14 colour transform of {adobe} (RGB- or CMYK-coded data) is out of scope")
+    comps = [(sof[6 + 3 * i], sof[7 + 3 * i] >> 4, sof[7 + 3 * i] & 15, sof[8 + 3 * i]) for i in range(3)]
+    if adobe is None and [c[0] for c in comps] == [ord("R"), ord("G"), ord("B")]:
+        raise ValueError("RGB-coded JPEG (component ids R, G, B) is out of scope")
+    samp = tuple((c[1], c[2]) for c in comps)
+    if samp == ((2, 2), (1, 1), (1, 1)):
+        subsampling = "4:2:0"
+    elif samp == ((1, 1), (1, 1), (1, 1)):
+        subsampling = "4:4:4"
+    else:
+        name = {((2, 1), (1, 1), (1, 1)): '"4:2:2"', ((1, 2), (1, 1), (1, 1)): '"4:4:0"',
+                ((4, 1), (1, 1), (1, 1)): '"4:1:1"'}.get(samp, "this")
+        raise ValueError(f"{name} sampling {samp} is out of scope: the device decodes \"4:2:0\" and \"4:4:4\"")
+    if not (1 <= w <= N.IPP_JPEG_MAX_SIDE and 1 <= h <= N.IPP_JPEG_MAX_SIDE):
+        raise ValueError(f"image size {w}x{h} outside 1..{N.IPP_JPEG_MAX_SIDE} (IPP_JPEG_MAX_SIDE)")
+    if len(sos) < 1 or sos[0] != 3 or len(sos) < 10:
+        raise ValueError("more than one scan (a scan that does not hold all three components) is out of scope")
+    sel = {sos[1 + 2 * i]: (sos[2 + 2 * i] >> 4, sos[2 + 2 * i] & 15) for i in range(3)}
+    if [sos[1 + 2 * i] for i in range(3)] != [c[0] for c in comps]:
+        raise ValueError("a scan whose components are not the frame's, in order, is out of scope")
+    if (sos[7], sos[8], sos[9]) != (0, 63, 0):
+        raise ValueError("progressive scan parameters (spectral selection / approximation) are out of scope")
+    qt = tuple(c[3] for c in comps)
+    dc = tuple(sel[c[0]][0] for c in comps)
+    ac = tuple(sel[c[0]][1] for c in comps)
+    for i in range(3):
+        if qt[i] not in qtables or (0, dc[i]) not in htables or (1, ac[i]) not in htables:
+            raise ValueError("malformed header: a component names a table the file does not define")
+    # the span ends at the first marker that is neither stuffing nor RSTn (the EOI), or with the file
+    end = at
+    while True:
+        k = data.find(b"\xff", end)
+        if k < 0 or k + 1 >= n:
+            end = n
+            break
+        nx = data[k + 1]
+        if nx == 0 or 0xD0 <= nx <= 0xD7:
+            end = k + 2
+            continue
+        if nx == 0xFF:
+            end = k + 1
+            continue
+        end = k
+        if nx != 0xD9:
+            raise ValueError("more than one scan (a marker other than EOI after the first scan) is out of scope")
+        break
+    if end - at > N.IPP_JPEGD_MAX_SPAN:
+        raise ValueError(f"entropy-coded data over {N.IPP_JPEGD_MAX_SPAN} bytes are out of scope")
+    return JpegInfo(w, h, subsampling, qt, dc, ac, qtables, htables, restart, (at, end))
+
+
+class JpegDecoder:
+    """Decodes baseline JPEG files on ``device`` to the RGB pixels
+    ``np.asarray(Image.open(f).convert("RGB"))`` gives (ipp.h states the rule
+    under ipp_jpeg_decode).  One pinned staging buffer and one copy up of the
+    files' entropy-coded spans, descriptors and tables; the kernels; one copy
+    back of the status words.  ``last_stats`` keeps them, (n, 4) int32
+    {status, rounds, subsequences, marker status}: the rounds the slowest
+    restart interval of each file took to synchronise and the most
+    subsequences one of its intervals has."""
+
+    def __init__(self, device):
+        import torch
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError(f"JpegDecoder runs on a ROCm device, got {self.device}")
+        self.lib = N.load()
+        self.last_stats = np.zeros((0, N.IPP_JPEGD_STAT), np.int32)
+        self._stage = None        # pinned staging buffer, kept and grown: pinning is a slow, synchronising call
+        self._scratch = None      # device scratch, kept and grown
+
+    def _grown(self, buf, nbytes: int, **kw):
+        import torch
+        if buf is None or buf.numel() < nbytes:
+            buf = torch.empty(max(16, nbytes + nbytes // 4), dtype=torch.uint8, **kw)
+            if "device" not in kw:
+                buf = buf.pin_memory()
+        return buf
+
+    def decode_some(self, datas: Sequence[bytes], parsed: Optional[Sequence] = None
+                    ) -> Tuple[List, List[Optional[str]]]:
+        """(images, reasons): per file its (h, w, 3) uint8 tensor on the device
+        and None, or None and why it was refused — by parse_jpeg (out of
+        scope) or by the device (a malformed stream; nothing of it was
+        written).  The accepted files cost one call whatever the others are;
+        the caller sends the refused ones another way.  The tensors are views
+        of one allocation per call.  ``parsed[i]``: what parse_jpeg returned
+        or raised for file i, where the caller has called it already (on its
+        own threads, say)."""
+        import torch
+        n_all = len(datas)
+        images: List = [None] * n_all
+        reasons: List[Optional[str]] = [None] * n_all
+        infos, idx = [], []
+        for i, data in enumerate(datas):
+            try:
+                f = parsed[i] if parsed is not None else parse_jpeg(data)
+                if isinstance(f, Exception):
+                    raise f
+                infos.append(f)
+                idx.append(i)
+            except ValueError as e:
+                reasons[i] = str(e)
+        n = len(idx)
+        self.last_stats = np.zeros((n_all, N.IPP_JPEGD_STAT), np.int32)
+        if n == 0:
+            return images, reasons
+        descs = np.zeros(n, N.JPEGD_DESC)
+        qtabs, htabs, qid, hid = [], [], {}, {}
+
+        def intern(store, ids, key, make):
+            if key not in ids:
+                ids[key] = len(store)
+                store.append(make())
+            return ids[key]
+
+        def htab(spec):
+            t = np.zeros(16 + 256, np.uint8)
+            t[:16] = np.frombuffer(spec[0], np.uint8)
+            t[16:16 + len(spec[1])] = np.frombuffer(spec[1], np.uint8)
+            return t
+        up16 = lambda v: (v + 15) // 16 * 16
+        span_at = out_at = 0
+        for k, f in enumerate(infos):
+            d = descs[k]
+            d["span_off"], d["span_len"] = span_at, f.span[1] - f.span[0]
+            span_at += up16(int(d["span_len"]))
+            d["w"], d["h"], d["sampling"], d["restart"] = f.w, f.h, SAMPLINGS[f.subsampling], f.restart_interval
+            d["out_off"], d["out_pitch"] = out_at, 3 * f.w
+            out_at += up16(3 * f.w * f.h)
+            for c in range(3):
+                d["qt"][c] = intern(qtabs, qid, f.qtables[f.qt[c]].tobytes(), lambda: f.qtables[f.qt[c]])
+                d["dc"][c] = intern(htabs, hid, (0,) + f.htables[(0, f.dc[c])], lambda: htab(f.htables[(0, f.dc[c])]))
+                d["ac"][c] = intern(htabs, hid, (1,) + f.htables[(1, f.ac[c])], lambda: htab(f.htables[(1, f.ac[c])]))
+        nb = self.lib.ipp_jpeg_decode_scratch_bytes(descs.ctypes.data, n)
+        if nb < 0:
+            raise N.NativeError(f"ipp_jpeg_decode_scratch_bytes failed with code {nb}")
+        # the staging buffer: spans, descriptors, quantisation tables, Huffman tables
+        data_bytes = max(span_at, 16)
+        o_desc = up16(data_bytes)
+        o_q = up16(o_desc + descs.nbytes)
+        o_h = up16(o_q + 128 * len(qtabs))
+        total = up16(o_h + (16 + 256) * len(htabs))
+        self._stage = self._grown(self._stage, total)
+        host = self._stage.numpy()
+        for d, i, f in zip(descs, idx, infos):
+            host[int(d["span_off"]):int(d["span_off"]) + int(d["span_len"])] = np.frombuffer(
+                datas[i], np.uint8, int(d["span_len"]), f.span[0])
+        host[o_desc:o_desc + descs.nbytes] = descs.view(np.uint8).reshape(-1)
+        host[o_q:o_q + 128 * len(qtabs)] = np.stack(qtabs).astype(np.uint16).view(np.uint8).reshape(-1)
+        host[o_h:o_h + 272 * len(htabs)] = np.stack(htabs).reshape(-1)
+        dev = self._stage[:total].to(self.device, non_blocking=True)
+        self._scratch = self._grown(self._scratch, int(nb), device=self.device)
+        out = torch.empty(max(out_at, 16), dtype=torch.uint8, device=self.device)
+        stat = torch.empty(n * N.IPP_JPEGD_STAT, dtype=torch.int32, device=self.device)
+        st = torch.cuda.current_stream(self.device).cuda_stream
+        p = dev.data_ptr()
+        N.check(self.lib.ipp_jpeg_decode(p, data_bytes, host.ctypes.data + o_desc, p + o_desc, n, p + o_q, len(qtabs),
+                                         p + o_h, len(htabs), self._scratch.data_ptr(), int(nb), out.data_ptr(), out_at,
+                                         stat.data_ptr(), st), "ipp_jpeg_decode")
+        stats = stat.cpu().numpy().reshape(n, N.IPP_JPEGD_STAT)      # synchronises: the staging buffer is free again
+        for k, (i, d, f) in enumerate(zip(idx, descs, infos)):
+            self.last_stats[i] = stats[k]
+            if stats[k, 0] != 0:
+                reasons[i] = f"malformed JPEG data ({N.IPP_JPEGD_STATUS.get(int(stats[k, 0]), 'unknown')})"
+            else:
+                images[i] = out[int(d["out_off"]):int(d["out_off"]) + 3 * f.w * f.h].view(f.h, f.w, 3)
+        return images, reasons
+
+    def decode(self, datas: Sequence[bytes], names: Optional[Sequence[str]] = None) -> List:
+        """One (h, w, 3) uint8 tensor on the device per file; sizes, samplings
+        and tables may differ.  ValueError names (``names[i]``, else the
+        index) every file parse_jpeg refuses or whose stream the device found
+        malformed: nothing is returned for them (decode_some returns the
+        others)."""
+        images, reasons = self.decode_some(datas)
+        bad = [i for i, r in enumerate(reasons) if r is not None]
+        if bad:
+            label = lambda i: str(names[i]) if names is not None else f"image {i}"
+            raise ValueError("; ".join(f"{label(i)}: {reasons[i]}" for i in bad) + " (nothing was decoded for them)")
+        return images
+
+    def decode_batch(self, datas: Sequence[bytes]):
+        """(n, h, w, 3) where every file has the same size."""
+        import torch
+        imgs = self.decode(datas)
+        if len({tuple(im.shape) for im in imgs}) > 1:
+            raise ValueError("decode_batch needs files of one size; use decode for mixed sizes")
+        return torch.stack(imgs) if imgs else torch.empty((0, 0, 0, 3), dtype=torch.uint8, device=self.device)

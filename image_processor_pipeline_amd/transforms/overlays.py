@@ -24,7 +24,7 @@ from .. import _rt
 from .. import batch_ops as BO
 from .. import device as D
 from .. import geometry as G
-from ..jpeg import encode_grouped
+from ..jpeg import JpegDecoder, encode_grouped, parse_jpeg
 from ..labels_math import xyxy2xywhn
 from ..utils import utils
 
@@ -55,6 +55,47 @@ def _is_jpeg(path: Path) -> bool:
     return path.suffix.lower() in (".jpg", ".jpeg")
 
 
+_DECODER = None
+
+
+def _read_jpeg(path: Path):
+    """(bytes, JpegInfo) of a file the device decoder takes, None for one
+    jpeg.parse_jpeg refuses (progressive, greyscale, CMYK, "4:2:2", ...):
+    the file read and the marker walk, fit for a host thread.  OSError as
+    ``open`` raises it."""
+    data = Path(path).read_bytes()
+    try:
+        return data, parse_jpeg(data)
+    except ValueError:
+        return None
+
+
+def _device_backgrounds(paths: List[Path], jobs: Optional[List] = None) -> List:
+    """The files ``paths`` decoded on the device (jpeg.JpegDecoder: the pixels
+    ``Image.open(p).convert("RGB")`` gives), one call for all of them: per
+    path a device tensor (h, w, 3), or None — a file that cannot be read, one
+    parse_jpeg refuses, or one whose stream the device finds malformed.  A
+    None takes the Pillow path, messages and all.  ``jobs[i]``: what
+    _read_jpeg returned for paths[i], where it has been called already."""
+    global _DECODER
+    if jobs is None:
+        jobs = []
+        for p in paths:
+            try:
+                jobs.append(_read_jpeg(p) if _is_jpeg(p) else None)
+            except OSError:
+                jobs.append(None)
+    out: List = [None] * len(paths)
+    idx = [i for i, j in enumerate(jobs) if j is not None]
+    if idx:
+        if _DECODER is None:
+            _DECODER = JpegDecoder(_rt.device())
+        images = _DECODER.decode_some([jobs[i][0] for i in idx], parsed=[jobs[i][1] for i in idx])[0]
+        for i, im in zip(idx, images):
+            out[i] = im
+    return out
+
+
 def _save_composite(comp, path: Path) -> None:
     """overlays.py:169 — or the bytes of the file, where the device encoded it."""
     if isinstance(comp, bytes):
@@ -77,9 +118,16 @@ def paste_overlay_onto_background(
     tight_bbox: bool = False,
     alpha_min: int = 1,
     device_jpeg: bool = False,
+    device_decode: bool = False,
     **options: Any,
 ) -> Optional[List[Path]]:
-    """``device_jpeg`` (not in the reference): where the output suffix is
+    """``device_decode`` (not in the reference): a ``.jpg`` / ``.jpeg``
+    background that jpeg.parse_jpeg accepts (baseline, 4:2:0 or 4:4:4) is
+    decoded on the device (jpeg.JpegDecoder: the pixels ``Image.open`` gives)
+    and its pixels never cross the bus; any other file, and one the device
+    finds malformed, is opened by Pillow as before.  The outputs are the same
+    either way.
+    ``device_jpeg`` (not in the reference): where the output suffix is
     ``.jpg`` / ``.jpeg`` the composite is encoded on the device (jpeg.py: the
     same bytes ``save`` writes) and only the file's bytes are copied back; any
     other suffix is saved on the host as before.
@@ -94,7 +142,8 @@ def paste_overlay_onto_background(
         overlay = Image.open(overlay_path)
         if overlay.mode != "RGBA":
             overlay = overlay.convert("RGBA")
-        background = Image.open(background_path).convert("RGB")
+        bg_dev = _device_backgrounds([background_path])[0] if device_decode else None
+        background = None if bg_dev is not None else Image.open(background_path).convert("RGB")
     except FileNotFoundError as fnf:
         print(f"Erreur {names}: Fichier non trouvé: {fnf}")
         return None
@@ -109,7 +158,7 @@ def paste_overlay_onto_background(
         return None
 
     try:
-        bw, bh = background.size
+        bw, bh = background.size if bg_dev is None else (int(bg_dev.shape[1]), int(bg_dev.shape[0]))
         target_ratio = random.uniform(scale_min, scale_max)
         if overlay.height == 0:
             raise ValueError(f"dimensions de l'overlay {overlay_path.name} invalides ({overlay.width}x{overlay.height}).")
@@ -118,7 +167,7 @@ def paste_overlay_onto_background(
         resized = D.resize_lanczos_rgba(ov_dev, new_w, new_h)
         pos_x = random.randint(0, bw - new_w)
         pos_y = random.randint(0, bh - new_h)
-        comp = D.paste_blend(_rt.h2d(np.asarray(background)), resized, pos_x, pos_y)
+        comp = D.paste_blend(bg_dev if bg_dev is not None else _rt.h2d(np.asarray(background)), resized, pos_x, pos_y)
         if device_jpeg and _is_jpeg(background_path):
             composite_image = encode_grouped([comp])[0]
         else:
@@ -155,7 +204,7 @@ def paste_overlay_onto_background(
 
 def _overlays_batch(arg_tuples, output_dirs: List[Path], threads: int = 1, yolo_class_id: int = 0,
                     scale_min: float = 0.15, scale_max: float = 0.30, tight_bbox: bool = False,
-                    alpha_min: int = 1, device_jpeg: bool = False, **options: Any) -> List:
+                    alpha_min: int = 1, device_jpeg: bool = False, device_decode: bool = False, **options: Any) -> List:
     """Batched paste_overlay_onto_background ('modulo' pairs): decode on host
     threads, the per-item draws (uniform ratio, then two randint) in pair
     order, ONE batched LANCZOS H + V + paste launch set for the chunk
@@ -164,16 +213,29 @@ def _overlays_batch(arg_tuples, output_dirs: List[Path], threads: int = 1, yolo_
     from one more batched launch over the chunk's resized overlays
     (ipp_alpha_bbox_min).  ``device_jpeg``: the composites whose output
     suffix is ``.jpg`` / ``.jpeg`` are encoded on the device in the same chunk
-    and only their files' bytes come back."""
+    and only their files' bytes come back.  ``device_decode``: the chunk's
+    ``.jpg`` / ``.jpeg`` backgrounds that jpeg.parse_jpeg accepts are decoded
+    on the device in one call (jpeg.JpegDecoder) and stay there; the host
+    threads read their bytes and walk their markers.  A file parse_jpeg
+    refuses is opened by Pillow on its thread as before, one the device finds
+    malformed after the call."""
     image_target_dir, label_target_dir = utils._validate_dirs(output_dirs, nb_dirs=2)
 
-    def load(args):
+    def load(args, defer: Optional[bool] = None):
+        """(overlay pixels, background pixels); with ``defer`` a background
+        the device decoder takes is left as (path, _read_jpeg's result), for
+        compute to decode on the device."""
         overlay_path, background_path = args[0], args[1]
+        if defer is None:
+            defer = device_decode and _is_jpeg(background_path)
         names = f"[{overlay_path.name} + {background_path.name}]"
         try:
             overlay = Image.open(overlay_path)
             if overlay.mode != "RGBA":
                 overlay = overlay.convert("RGBA")
+            job = _read_jpeg(background_path) if defer else None     # a missing file fails here, as Image.open would
+            if job is not None:
+                return np.asarray(overlay), (background_path, job)
             background = Image.open(background_path).convert("RGB")
             return np.asarray(overlay), np.asarray(background)
         except FileNotFoundError as fnf:
@@ -188,6 +250,15 @@ def _overlays_batch(arg_tuples, output_dirs: List[Path], threads: int = 1, yolo_
 
     def compute(items, args):
         plans, ovs, bgs, sizes, pos, jpeg = [], [], [], [], [], []
+        if device_decode:
+            items = list(items)
+            todo = [k for k, it in enumerate(items) if it is not None and isinstance(it[1], tuple)]
+            decoded = _device_backgrounds([items[k][1][0] for k in todo], [items[k][1][1] for k in todo])
+            for k, im in zip(todo, decoded):
+                if im is None:                         # malformed: Pillow, with its messages
+                    items[k] = load(args[k], defer=False)
+                else:
+                    items[k] = (items[k][0], im)
         for item, a in zip(items, args):
             if item is None:
                 plans.append(None)

@@ -1323,6 +1323,120 @@ int ipp_jpeg_pack(const uint8_t* slots, int64_t capacity, const int32_t* hdr, in
                   const int64_t* offsets, uint8_t* out, void* stream);
 
 /* ------------------------------------------------------------------------ */
+/* Baseline JPEG files decoded on the device                                  */
+/* ------------------------------------------------------------------------ */
+/* The RGB pixels np.asarray(Image.open(f).convert("RGB")) gives with Pillow
+ * 12.2.0 (libjpeg-turbo 3.1) for a baseline file: 8 bit, three components
+ * YCbCr sampled 2x2/1x1/1x1 (IPP_JPEG_420) or 1x1/1x1/1x1 (IPP_JPEG_444), one
+ * interleaved scan, Huffman coded, with or without restart markers.  The host
+ * (jpeg.py parse_jpeg) walks the markers and refuses everything else by name;
+ * the device decodes the entropy-coded span.  This project's normative
+ * definition, in exact integers (tests/jpeg_decode_refs.py is its restatement,
+ * held to the installed Pillow value for value; Pillow is the judge):
+ *
+ * CODING, undone.  Blocks in scan order as for the encoder above; in each, a
+ * DC symbol (category s <= 11, then s magnitude bits: v, or v - 2^s + 1 where
+ * v < 2^(s-1)) added to the previous DC of the component (0 at the start of the
+ * scan and after every RSTn), then AC symbols (run << 4 | s): 0x00 ends the
+ * block, 0xF0 skips 16 terms, else skip `run` and read a term of s <= 10 bits;
+ * zigzag position k of the block is natural position zz[k].  The codes are
+ * those of the file's own DHT tables (BITS, HUFFVAL; Annex C).  A 0x00 after a
+ * 0xFF is no data.  With a restart interval of r MCUs, every r MCUs the stream
+ * is padded to a byte and RSTn (n counting 0..7 and again) follows.
+ * DEQUANTISE.  coefficient · table entry (the file's DQT, 8 bit), natural order.
+ * INVERSE TRANSFORM (jidctint.c "islow", CONST_BITS 13, PASS1_BITS 2, int32),
+ * columns first, then rows.  Of c0..c7:
+ *   z1 = (c2 + c6)·4433, t2 = z1 - c6·15137, t3 = z1 + c2·6270
+ *   t0 = (c0 + c4) << 13, t1 = (c0 - c4) << 13
+ *   t10, t13, t11, t12 = t0 + t3, t0 - t3, t1 + t2, t1 - t2
+ *   a0..a3 = c7, c5, c3, c1;  z1 = a0 + a3, z2 = a1 + a2, z3 = a0 + a2,
+ *   z4 = a1 + a3, z5 = (z3 + z4)·9633
+ *   a0 *= 2446, a1 *= 16819, a2 *= 25172, a3 *= 12299
+ *   z1 *= -7373, z2 *= -20995, z3 = z3·(-16069) + z5, z4 = z4·(-3196) + z5
+ *   a0 += z1 + z3, a1 += z2 + z4, a2 += z2 + z3, a3 += z1 + z4
+ *   outputs 0..7 = t10 + a3, t11 + a2, t12 + a1, t13 + a0, t13 - a0, t12 - a1,
+ *   t11 - a2, t10 - a3, each (x + 2^(s-1)) >> s with s = 11 for the columns and
+ *   18 for the rows (arithmetic shift).  Then + 128, clamped to 0..255.
+ *   libjpeg masks the sample before its limit table, so one outside -384..639
+ *   before the clamp would wrap there.  No file an encoder writes reaches that
+ *   range; such files are outside this contract and nothing is tested there.
+ * UPSAMPLE, 4:2:0 only (jdsample.c).  A chroma plane is its real extent of
+ * ⌈w / 2⌉ x ⌈h / 2⌉ samples; what was decoded past it is never read.  Where
+ * ⌈w / 2⌉ > 2, the "fancy" triangle filter: for output row y, s[x] =
+ * 3·near[x] + far[x] with near = chroma row y >> 1 and far the row above it
+ * (y even) or below it (y odd), the edge row repeated at the top and bottom;
+ * output column 2x = (3·s[x] + s[x-1] + 8) >> 4, column 2x + 1 = (3·s[x] +
+ * s[x+1] + 7) >> 4, s repeating its edge at both ends.  Where ⌈w / 2⌉ <= 2
+ * (w <= 4) libjpeg replicates instead: pixel (x, y) takes chroma (x >> 1,
+ * y >> 1).  Cropped to w x h.
+ * COLOUR (jdcolor.c), cb and cr less 128, arithmetic shifts, clamped to 0..255:
+ *   R = Y + (( 91881·cr + 32768) >> 16)
+ *   G = Y + ((-22554·cb - 46802·cr + 32768) >> 16)
+ *   B = Y + ((116130·cb + 32768) >> 16)
+ * No float anywhere.
+ *
+ * ipp_jpeg_decode: image i's entropy-coded bytes (after the SOS header, up to
+ * the EOI or the end of the file) are data[span_off, span_off + span_len); no
+ * byte outside the span is read; its
+ * pixels go to out + out_off, rows out_pitch (>= 3w) bytes apart, 3w bytes of
+ * each written and nothing else.  qtabs: device uint16[n_qtabs][64], natural
+ * order; htabs: device uint8[n_htabs][16 + 256], BITS then HUFFVAL; qt / dc /
+ * ac: per component (Y, Cb, Cr) the index of its table.  restart: the DRI
+ * interval in MCUs, 0 for none.  Sizes, samplings and tables may differ from
+ * image to image.  descs_host and descs hold the same n_images descriptors in
+ * host and in device memory (one staging buffer and its copy): the host's are
+ * checked before any launch, the kernels read the device's.
+ * stat: device int32[n_images][IPP_JPEGD_STAT] = {status, rounds, subsequences,
+ * marker status}; every word is written.  status 0: the image's pixels are
+ * all written.  Nonzero: the stream is malformed and NO byte of the image's
+ * output is written — IPP_JPEGD_BAD_MARKER (a marker other than RSTn, or fill
+ * bytes, inside the span), _WRONG_RST (RSTn out of order), _SEG_COUNT (not
+ * ⌈MCUs / restart⌉ segments), _TRUNCATED (the span ends in 0xFF), _BAD_CODE (a
+ * code in no table, or a category or EOB run baseline does not have), _RUN (a
+ * run past coefficient 63), _SEG_BLOCKS (a segment that ends early, inside a
+ * block or an MCU, with blocks missing or left over, or with a byte or more
+ * unread).  Several faults: the largest code.  rounds / subsequences: the most
+ * synchronisation rounds any segment of the image took and the most
+ * subsequences (of IPP_JPEGD_SUBSEQ bytes) any segment has — the decoder
+ * repeats rounds until no lane's start state changes, however many that takes.
+ * scratch: device, 16-B aligned; ipp_jpeg_decode_scratch_bytes fills the HOST
+ * descriptors' coef_off / sub_off / seg_off (per image, each rounded up to
+ * 256 B: 128 B per block; 24 B per span_len / IPP_JPEGD_SUBSEQ + segments + 1;
+ * 8 B per segment) and returns the total, or IPP_E_ARG for a bad shape.
+ * IPP_E_ARG, before any launch: a NULL pointer; scratch not 16-B, descs not
+ * 8-B, stat not 4-B, qtabs not 2-B aligned; n_images negative or > 65535;
+ * n_qtabs or n_htabs < 1; a negative size; per image: w or h outside
+ * 1..IPP_JPEG_MAX_SIDE, another sampling, restart outside 0..65535, span_len
+ * outside 0..IPP_JPEGD_MAX_SPAN, a span outside data, a table index outside
+ * its array, out_pitch < 3w, an output outside out, scratch offsets other than
+ * ipp_jpeg_decode_scratch_bytes assigns, or their total over scratch_bytes.
+ * n_images == 0 is IPP_OK, launches and writes nothing. */
+#define IPP_JPEGD_STAT 4
+#define IPP_JPEGD_BAD_MARKER 1
+#define IPP_JPEGD_WRONG_RST 2
+#define IPP_JPEGD_SEG_COUNT 3
+#define IPP_JPEGD_TRUNCATED 4
+#define IPP_JPEGD_BAD_CODE 5
+#define IPP_JPEGD_RUN 6
+#define IPP_JPEGD_SEG_BLOCKS 7
+#define IPP_JPEGD_MAX_SPAN 1073741824 /* 2^30 */
+typedef struct ipp_jpegd_desc {
+    int64_t span_off;                  /* entropy-coded bytes in data             */
+    int64_t out_off;                   /* first pixel in out                      */
+    int64_t coef_off, sub_off, seg_off; /* scratch parts (ipp_jpeg_decode_scratch_bytes) */
+    int32_t span_len;
+    int32_t w, h, sampling, restart;
+    int32_t out_pitch;
+    int32_t qt[3], dc[3], ac[3];
+    int32_t pad_;
+} ipp_jpegd_desc;
+int64_t ipp_jpeg_decode_scratch_bytes(ipp_jpegd_desc* descs, int32_t n_images);
+int ipp_jpeg_decode(const uint8_t* data, int64_t data_bytes, const ipp_jpegd_desc* descs_host,
+                    const ipp_jpegd_desc* descs, int32_t n_images, const uint16_t* qtabs, int32_t n_qtabs,
+                    const uint8_t* htabs, int32_t n_htabs, uint8_t* scratch, int64_t scratch_bytes,
+                    uint8_t* out, int64_t out_bytes, int32_t* stat, void* stream);
+
+/* ------------------------------------------------------------------------ */
 /* Measurement helper (the copy-kernel ceiling of the box).     */
 /* ------------------------------------------------------------------------ */
 /* dst[0, nbytes) = src[0, nbytes) with 16-B non-temporal loads/stores; both
