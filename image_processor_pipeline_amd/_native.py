@@ -200,6 +200,9 @@ SIGNATURES = {
     "ipp_scene_feed_resize": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "ipp_scene_feed_resize_lds": (_L, [_I, _I, _I, _I, _I, _I, _I, _P]),
     "ipp_scene_feed_index_map_sampled": (_I, [_P, _L, _I, _I, _P, _I, _I, _P, _P, _I, _I, _P, _L, _P]),
+    "ipp_scene_feed_letterbox": (_I, [_P, _P, _P, _P, _P] + [_I] * 14 + [_P]),
+    "ipp_scene_feed_targets_letterbox": (_I, [_P, _P, _P] + [_I] * 12 + [_P, _P, _P, _P]),
+    "ipp_scene_feed_index_map_letterbox": (_I, [_P, _L, _I, _I, _P, _I, _I, _P, _P] + [_I] * 6 + [_P, _L, _P]),
     "ipp_jpeg_scratch_bytes": (_L, [_I, _I, _I, _I, _L]),
     "ipp_jpeg_encode": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _L, _P, _P]),
     "ipp_jpeg_pack": (_I, [_P, _L, _P, _I, _P, _P, _P]),

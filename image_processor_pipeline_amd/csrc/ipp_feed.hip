@@ -18,6 +18,8 @@
 //                      `slot`, then scans the S·K overlays in scene, layer
 //                      order in chunks of 1024 with a carried prefix and
 //                      stores the kept rows compacted.
+//   k_letterbox_targets   the same scan with the rows moved and scaled into a
+//                      letterbox rectangle (targets_scan<true>).
 //   k_feed_index_map   visibility map -> per-pixel row index within the
 //                      scene's run of targets, through a 256-entry table per
 //                      scene in LDS; 16-B loads and stores.
@@ -145,17 +147,25 @@ __device__ __forceinline__ uint32_t wave_rank(bool flag, uint32_t& total) {
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));  // set flags below the lane
 }
 
+// The rectangle of a letterboxed batch (ipp.h: ipp_scene_feed_targets_letterbox).
+struct Letterbox {
+    int32_t new_w, new_h, left, top, out_w, out_h;
+};
+
 // `slot` doubles as the inverse of the descriptor permutation until the sweep
 // replaces each word by its answer: word q = scene·per_scene + layer first
 // holds the highest descriptor that scene_layer maps there (an integer max:
 // the same whatever order the lanes arrive in), or -1.  The words are read
 // back with agent-scope loads, which are served by the L2 the atomics ran in.
-__global__ __launch_bounds__(kScanThreads) void k_feed_targets(const int32_t* __restrict__ rows,
-                                                               const int32_t* __restrict__ scene_layer,
-                                                               const int32_t* __restrict__ class_ids, int n,
-                                                               int n_scenes, int per_scene, int bg_w, int bg_h,
-                                                               int min_q, float* __restrict__ targets,
-                                                               int32_t* __restrict__ count, int32_t* slot) {
+// targets_scan is the whole of both kernels; only ROW differs: with LB each of
+// the four numbers is an exact int64 numerator over an exact int64 denominator
+// (both below 2^49, exact in float64), ONE correctly rounded float64 division
+// and ONE round-to-nearest conversion to float32.
+template <bool LB>
+__device__ __forceinline__ void targets_scan(const int32_t* __restrict__ rows, const int32_t* __restrict__ scene_layer,
+                                             const int32_t* __restrict__ class_ids, int n, int n_scenes, int per_scene,
+                                             int bg_w, int bg_h, int min_q, const Letterbox& lb,
+                                             float* __restrict__ targets, int32_t* __restrict__ count, int32_t* slot) {
     __shared__ uint32_t s_wave[kScanWaves];
     const int tid = (int)threadIdx.x, wave = tid >> 6;
     const int total = n_scenes * per_scene;
@@ -196,10 +206,20 @@ __global__ __launch_bounds__(kScanThreads) void k_feed_targets(const int32_t* __
                 float* t = targets + 6 * (int64_t)pos;
                 t[0] = (float)(q / per_scene);
                 t[1] = (float)(class_ids ? class_ids[d] : 0);
-                t[2] = __fdiv_rn((float)(x0 + x1), fw2);
-                t[3] = __fdiv_rn((float)(y0 + y1), fh2);
-                t[4] = __fdiv_rn((float)(x1 - x0), fw);
-                t[5] = __fdiv_rn((float)(y1 - y0), fh);
+                if (LB) {
+                    const int64_t dx = (int64_t)bg_w * lb.out_w, dy = (int64_t)bg_h * lb.out_h;
+                    const int64_t cx = (int64_t)(x0 + x1) * lb.new_w + 2 * (int64_t)lb.left * bg_w;
+                    const int64_t cy = (int64_t)(y0 + y1) * lb.new_h + 2 * (int64_t)lb.top * bg_h;
+                    t[2] = __double2float_rn(__ddiv_rn((double)cx, (double)(2 * dx)));
+                    t[3] = __double2float_rn(__ddiv_rn((double)cy, (double)(2 * dy)));
+                    t[4] = __double2float_rn(__ddiv_rn((double)((int64_t)(x1 - x0) * lb.new_w), (double)dx));
+                    t[5] = __double2float_rn(__ddiv_rn((double)((int64_t)(y1 - y0) * lb.new_h), (double)dy));
+                } else {
+                    t[2] = __fdiv_rn((float)(x0 + x1), fw2);
+                    t[3] = __fdiv_rn((float)(y0 + y1), fh2);
+                    t[4] = __fdiv_rn((float)(x1 - x0), fw);
+                    t[5] = __fdiv_rn((float)(y1 - y0), fh);
+                }
             }
         }
         base += all;
@@ -207,6 +227,26 @@ __global__ __launch_bounds__(kScanThreads) void k_feed_targets(const int32_t* __
     }
     if (tid == 0) *count = (int32_t)base;
     for (int64_t e = 6 * (int64_t)base + tid; e < 6 * (int64_t)total; e += kScanThreads) targets[e] = -1.0f;
+}
+
+__global__ __launch_bounds__(kScanThreads) void k_feed_targets(const int32_t* __restrict__ rows,
+                                                               const int32_t* __restrict__ scene_layer,
+                                                               const int32_t* __restrict__ class_ids, int n,
+                                                               int n_scenes, int per_scene, int bg_w, int bg_h,
+                                                               int min_q, float* __restrict__ targets,
+                                                               int32_t* __restrict__ count, int32_t* slot) {
+    targets_scan<false>(rows, scene_layer, class_ids, n, n_scenes, per_scene, bg_w, bg_h, min_q, Letterbox{}, targets,
+                        count, slot);
+}
+
+__global__ __launch_bounds__(kScanThreads) void k_letterbox_targets(const int32_t* __restrict__ rows,
+                                                                    const int32_t* __restrict__ scene_layer,
+                                                                    const int32_t* __restrict__ class_ids, int n,
+                                                                    int n_scenes, int per_scene, int bg_w, int bg_h,
+                                                                    int min_q, Letterbox lb,
+                                                                    float* __restrict__ targets,
+                                                                    int32_t* __restrict__ count, int32_t* slot) {
+    targets_scan<true>(rows, scene_layer, class_ids, n, n_scenes, per_scene, bg_w, bg_h, min_q, lb, targets, count, slot);
 }
 
 // The table of scene s: entry v is 0 when v has no kept layer's bit, else 1 +
@@ -283,20 +323,45 @@ extern "C" int ipp_scene_feed_images(const uint8_t* in, void* out, const void* l
     return IPP_OK;
 }
 
+// What both targets entries refuse.
+static bool targets_args_ok(const int32_t* rows, const int32_t* scene_layer, const int32_t* class_ids, int32_t n_images,
+                            int32_t n_scenes, int32_t per_scene, int32_t bg_w, int32_t bg_h, int32_t min_q,
+                            const float* targets, const int32_t* count, const int32_t* slot) {
+    if (!rows || !scene_layer || !targets || !count || !slot) return false;
+    if (n_images < 0 || n_images > IPP_FEED_MAX_TARGETS || n_scenes < 1 || per_scene < 1) return false;
+    if ((int64_t)n_scenes * per_scene > IPP_FEED_MAX_TARGETS) return false;
+    if (bg_w < 1 || bg_h < 1 || bg_w > IPP_FEED_MAX_SIDE || bg_h > IPP_FEED_MAX_SIDE) return false;
+    if (min_q < 0 || min_q > 65536) return false;
+    return ((reinterpret_cast<uintptr_t>(rows) | reinterpret_cast<uintptr_t>(scene_layer) |
+             reinterpret_cast<uintptr_t>(class_ids) | reinterpret_cast<uintptr_t>(targets) |
+             reinterpret_cast<uintptr_t>(count) | reinterpret_cast<uintptr_t>(slot)) & 3u) == 0;
+}
+
 extern "C" int ipp_scene_feed_targets(const int32_t* rows, const int32_t* scene_layer, const int32_t* class_ids,
                                       int32_t n_images, int32_t n_scenes, int32_t per_scene, int32_t bg_w, int32_t bg_h,
                                       int32_t min_q, float* targets, int32_t* count, int32_t* slot, void* stream) {
-    if (!rows || !scene_layer || !targets || !count || !slot) return IPP_E_ARG;
-    if (n_images < 0 || n_images > IPP_FEED_MAX_TARGETS || n_scenes < 1 || per_scene < 1) return IPP_E_ARG;
-    if ((int64_t)n_scenes * per_scene > IPP_FEED_MAX_TARGETS) return IPP_E_ARG;
-    if (bg_w < 1 || bg_h < 1 || bg_w > IPP_FEED_MAX_SIDE || bg_h > IPP_FEED_MAX_SIDE) return IPP_E_ARG;
-    if (min_q < 0 || min_q > 65536) return IPP_E_ARG;
-    if (((reinterpret_cast<uintptr_t>(rows) | reinterpret_cast<uintptr_t>(scene_layer) |
-          reinterpret_cast<uintptr_t>(class_ids) | reinterpret_cast<uintptr_t>(targets) |
-          reinterpret_cast<uintptr_t>(count) | reinterpret_cast<uintptr_t>(slot)) & 3u) != 0)
+    if (!targets_args_ok(rows, scene_layer, class_ids, n_images, n_scenes, per_scene, bg_w, bg_h, min_q, targets, count, slot))
         return IPP_E_ARG;
     hipLaunchKernelGGL(k_feed_targets, dim3(1), dim3(kScanThreads), 0, (hipStream_t)stream, rows, scene_layer, class_ids,
                        n_images, n_scenes, per_scene, bg_w, bg_h, min_q, targets, count, slot);
+    IPP_CHECK_LAUNCH();
+    return IPP_OK;
+}
+
+extern "C" int ipp_scene_feed_targets_letterbox(const int32_t* rows, const int32_t* scene_layer,
+                                                const int32_t* class_ids, int32_t n_images, int32_t n_scenes,
+                                                int32_t per_scene, int32_t bg_w, int32_t bg_h, int32_t min_q,
+                                                int32_t new_w, int32_t new_h, int32_t left, int32_t top, int32_t out_w,
+                                                int32_t out_h, float* targets, int32_t* count, int32_t* slot,
+                                                void* stream) {
+    if (!targets_args_ok(rows, scene_layer, class_ids, n_images, n_scenes, per_scene, bg_w, bg_h, min_q, targets, count, slot))
+        return IPP_E_ARG;
+    if (out_w < 1 || out_h < 1 || out_w > IPP_FEED_MAX_SIDE || out_h > IPP_FEED_MAX_SIDE) return IPP_E_ARG;
+    if (new_w < 1 || new_h < 1 || left < 0 || top < 0 || (int64_t)left + new_w > out_w || (int64_t)top + new_h > out_h)
+        return IPP_E_ARG;
+    const Letterbox lb = {new_w, new_h, left, top, out_w, out_h};
+    hipLaunchKernelGGL(k_letterbox_targets, dim3(1), dim3(kScanThreads), 0, (hipStream_t)stream, rows, scene_layer,
+                       class_ids, n_images, n_scenes, per_scene, bg_w, bg_h, min_q, lb, targets, count, slot);
     IPP_CHECK_LAUNCH();
     return IPP_OK;
 }

@@ -41,10 +41,10 @@ from . import geometry as G
 from .device import SYM_FLIP, _stream, _to_dev
 from .device import check_alpha_min as _check_alpha_min
 from .jpeg import JpegEncoder, jpeg_header, jpeg_tables  # noqa: F401  (the device JPEG encoder, jpeg.py)
-from .labels_fmt import (FEED_RESAMPLE, feed_lut, instance_ids, min_visible_q, obb_corners, obb_label,  # noqa: F401
-                         rle_counts_from_string, rle_counts_string, rle_decode, scene_amodal_annotations,
-                         scene_coco_annotations, scene_contour_capacity, scene_instance_masks, scene_labels,
-                         scene_map_pitch, scene_obb_labels, scene_seg_labels, seg_label, simplify_tolerance,
+from .labels_fmt import (FEED_RESAMPLE, Letterbox, feed_lut, instance_ids, letterbox_geometry,  # noqa: F401
+                         min_visible_q, obb_corners, obb_label, rle_counts_from_string, rle_counts_string,
+                         rle_decode, scene_amodal_annotations, scene_coco_annotations, scene_contour_capacity,
+                         scene_instance_masks, scene_labels, scene_map_pitch, scene_obb_labels, scene_seg_labels, seg_label, simplify_tolerance,
                          xyxy2xywhn, yolo_label, yolo_labels)
 
 ALL_SYMS = ("o", "h", "v", "hv")

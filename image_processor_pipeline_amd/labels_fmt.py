@@ -11,12 +11,13 @@ writes the COCO annotations of ``SceneRunner.scene_rles``' run-length encodings,
 / ``rle_counts_from_string`` are the COCO API's compressed ``counts`` string and ``rle_decode``
 reads a mask back; ``scene_amodal_annotations`` writes the amodal ones (full and visible mask, occluders)
 of ``SceneRunner.scene_amodal_rles``.  ``feed_lut`` tabulates the normalisation of ``SceneRunner.feed``'s
-images and ``FEED_RESAMPLE`` names the filters of its ``size``.  ``fused`` re-exports it all.
+images, ``FEED_RESAMPLE`` names the filters of its ``size`` and ``letterbox_geometry`` states where its
+``letterbox`` puts a composite.  ``fused`` re-exports it all.
 """
 from __future__ import annotations
 
 import math
-from typing import List, Optional, Tuple
+from typing import List, NamedTuple, Optional, Tuple
 
 import numpy as np
 
@@ -146,6 +147,66 @@ def feed_lut(mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0), dtype=None, scale: float
     v = np.arange(256, dtype=np.float64) * float(scale)
     table = np.stack([(v - mean[c]) / std[c] for c in range(3)])
     return torch.tensor(table, dtype=torch.float64).to(dtype)
+
+
+class Letterbox(NamedTuple):
+    """The canvas and the rectangle of a letterboxed batch (``letterbox_geometry``)."""
+    out_h: int
+    out_w: int
+    new_h: int
+    new_w: int
+    top: int
+    left: int
+
+
+def _round_half_even_div(n: int, c: int) -> int:
+    """n / c rounded half to even, in integers (Python's ``round`` of the exact quotient)."""
+    q, rem = divmod(n, c)
+    return q + 1 if 2 * rem > c or (2 * rem == c and q & 1) else q
+
+
+def letterbox_geometry(bg_hw, size, scaleup: bool = True, center: bool = True, stride=None) -> Letterbox:
+    """Where ``SceneRunner.feed(size=..., letterbox=True)`` puts a bg_h x bg_w
+    composite in an out_h x out_w canvas (include/ipp.h states the rule): the
+    usual LetterBox, r = min(out_h / bg_h, out_w / bg_w) (min(r, 1) without
+    ``scaleup``), in exact integers.  The limiting axis (the smaller ratio, by
+    cross-multiplication; both on a tie) takes its canvas extent, the other
+    one a·b / c rounded half to even and at least 1; ``center`` puts the
+    rectangle at (dh // 2, dw // 2), else at (0, 0).  ``stride`` = s, an int
+    >= 1, is the minimal rectangle: the canvas shrinks to new + (out - new) %
+    s per axis before the offsets are taken; its (out_h, out_w) are what to
+    pass as ``size`` to get that canvas.  ``bg_hw`` = (bg_h, bg_w); ``size`` =
+    (out_h, out_w) or one int.  ValueError: sizes that are not positive ints,
+    out_h·out_w >= 2^28, a side above IPP_FEED_MAX_SIDE, a stride that is not
+    an int >= 1, flags that are not bools."""
+    def is_int(v):
+        return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+
+    if is_int(size):
+        size = (size, size)
+    for name, v in (("bg_hw", bg_hw), ("size", size)):
+        if not (isinstance(v, (tuple, list)) and len(v) == 2 and all(is_int(x) and x >= 1 for x in v)):
+            raise ValueError(f"letterbox_geometry: {name} {v!r}: two ints >= 1 expected")
+        if max(v) > N.IPP_FEED_MAX_SIDE:
+            raise ValueError(f"letterbox_geometry: {name} {v!r}: no side may exceed {N.IPP_FEED_MAX_SIDE}")
+    for name, v in (("scaleup", scaleup), ("center", center)):
+        if not isinstance(v, (bool, np.bool_)):
+            raise ValueError(f"letterbox_geometry: {name} {v!r}: a bool")
+    if stride is not None and not (is_int(stride) and stride >= 1):
+        raise ValueError(f"letterbox_geometry: stride {stride!r}: an int >= 1 or None")
+    (bg_h, bg_w), (out_h, out_w) = (int(v) for v in bg_hw), (int(v) for v in size)
+    if out_h * out_w >= 1 << 28:
+        raise ValueError(f"letterbox_geometry: size {size!r}: out_h*out_w must stay below 2^28")
+    if not scaleup and out_h >= bg_h and out_w >= bg_w:
+        new_h, new_w = bg_h, bg_w
+    else:
+        by_h, by_w = out_h * bg_w, out_w * bg_h          # r_h < r_w  <=>  out_h·bg_w < out_w·bg_h
+        new_h = out_h if by_h <= by_w else max(_round_half_even_div(bg_h * out_w, bg_w), 1)
+        new_w = out_w if by_w <= by_h else max(_round_half_even_div(bg_w * out_h, bg_h), 1)
+    if stride is not None:
+        out_h, out_w = new_h + (out_h - new_h) % int(stride), new_w + (out_w - new_w) % int(stride)
+    top, left = ((out_h - new_h) // 2, (out_w - new_w) // 2) if center else (0, 0)
+    return Letterbox(out_h, out_w, new_h, new_w, top, left)
 
 
 def scene_map_pitch(bg_w: int) -> int:

@@ -34,9 +34,9 @@ from .device import _stream, _to_dev, exclusive_offsets
 from .device import check_alpha_min as _check_alpha_min
 from .fused import (ItemParams, PipeConfig, PipePlan, _launch_hpass_bgcopy, _launch_vblend_bands, _Runner,
                     draw_params, plan_pipe)
-from .labels_fmt import (FEED_RESAMPLE, feed_lut, min_visible_q, scene_amodal_annotations, scene_coco_annotations,
-                         scene_contour_capacity, scene_labels, scene_map_pitch, scene_obb_labels, scene_seg_labels,
-                         simplify_tolerance)
+from .labels_fmt import (FEED_RESAMPLE, Letterbox, feed_lut, letterbox_geometry, min_visible_q,  # noqa: F401
+                         scene_amodal_annotations, scene_coco_annotations, scene_contour_capacity, scene_labels,
+                         scene_map_pitch, scene_obb_labels, scene_seg_labels, simplify_tolerance)
 
 
 def draw_scene_params(n_scenes_global: int, stop_scene: int, per_scene: int, src_hw: Tuple[int, int],
@@ -145,7 +145,8 @@ def _check_level(name: str, v) -> int:
 
 class SceneFeed(NamedTuple):
     """What ``SceneRunner.feed`` leaves on the device (include/ipp.h states the rules)."""
-    images: torch.Tensor                 # (S, 3, bg_h, bg_w) of the table's dtype; (S, 3, out_h, out_w) with size
+    images: torch.Tensor                 # (S, 3, bg_h, bg_w) of the table's dtype; (S, 3, out_h, out_w) with size (with
+    #                                      letterbox the canvas of letterbox_geometry((bg_h, bg_w), size, scaleup, center))
     targets: torch.Tensor                # (S·K, 6) float32 (scene, class, cx, cy, w, h); unused rows all -1
     count: torch.Tensor                  # (1,) int32: the rows in use
     slot: torch.Tensor                   # (S, K) int32: each overlay's row of targets, or -1
@@ -815,7 +816,8 @@ class SceneRunner(_Runner):
     def feed(self, out: torch.Tensor, lut: Optional[torch.Tensor] = None, mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0),
              dtype: torch.dtype = torch.float16, bgr: bool = False, class_ids=0, alpha_min: int = 1,
              cover_min: int = 128, min_visible: float = 0.0, index_map: bool = False,
-             images: Optional[torch.Tensor] = None, size=None, resample: str = "bilinear") -> SceneFeed:
+             images: Optional[torch.Tensor] = None, size=None, resample: str = "bilinear", letterbox: bool = False,
+             pad_value: int = 114, scaleup: bool = True, center: bool = True) -> SceneFeed:
         """The training batch of the composites `out` of the last ``run``, left
         on the device (include/ipp.h: ipp_scene_feed_images, _targets,
         _index_map): a ``SceneFeed`` of
@@ -864,16 +866,39 @@ class SceneRunner(_Runner):
         (a few tens of KB per distinct size, never evicted: a loop that draws
         a new size per batch keeps one entry per size it has seen).  A
         filter window above ``IPP_FEED_RESIZE_MAX_KSIZE`` source pixels (a
-        reduction beyond 21x for lanczos, 63x for bilinear) is a ValueError."""
+        reduction beyond 21x for lanczos, 63x for bilinear) is a ValueError.
+
+        ``letterbox=True`` (it needs ``size``) keeps the aspect instead
+        (include/ipp.h: ipp_scene_feed_letterbox, _targets_letterbox,
+        _index_map_letterbox).  With (out_h, out_w, new_h, new_w, top, left) =
+        ``letterbox_geometry((bg_h, bg_w), size, scaleup, center)`` — the
+        geometry is that call's result, ``SceneFeed`` keeps its five fields —
+        every composite is resized to (new_h, new_w) as above and sits at
+        (top, left) of ``images`` (S, 3, out_h, out_w); everywhere else
+        ``images[s, c]`` is ``lut[c][pad_value]`` (an int in 0..255, YOLO's 114
+        by default), all in one launch.  The targets follow the rectangle: cx =
+        ((x0 + x1)·new_w + 2·left·bg_w) / (2·bg_w·out_w), w = (x1 - x0)·new_w /
+        (bg_w·out_w), cy and h alike, exact integers divided once in float64
+        and rounded once to float32 (not the one float32 division of the plain
+        feed: the two can differ in the last bit even where the rectangle is the
+        canvas); count and slot are unchanged.  ``index_map`` is (S, out_h,
+        out_w): the NEAREST resize to (new_h, new_w) at (top, left), 0 around
+        it.  The minimal rectangle of a stride is reached by passing
+        ``letterbox_geometry(..., stride=s)``'s (out_h, out_w) as ``size``.  The
+        taps and the NEAREST tables are those of the inner size, shared with a
+        plain stretch to it."""
         if not self._hpass_done:
             raise ValueError("SceneRunner.feed: no run has filled the composites and the scratch on this runner")
         return self._feed_launch(*self._feed_args("feed", out, lut, mean, std, dtype, bgr, class_ids, alpha_min,
-                                                  cover_min, min_visible, index_map, images, size, resample))
+                                                  cover_min, min_visible, index_map, images, size, resample,
+                                                  letterbox, pad_value, scaleup, center))
 
-    def _feed_resize(self, who: str, size, resample, index_map: bool):
-        """(out_h, out_w, ksize_x, ksize_y, taps_x, taps_y, xtab, ytab) of ``feed(size=...)``: the device taps of
-        one (size, resample) and, with `index_map` only (None otherwise), the NEAREST tables of the size, each built
-        and uploaded once.  ValueError for what the entries would refuse."""
+    def _feed_resize(self, who: str, size, resample, index_map: bool, box=None):
+        """(out_h, out_w, ksize_x, ksize_y, taps_x, taps_y, xtab, ytab, box) of ``feed(size=...)``: the device taps
+        of one (size, resample) and, with `index_map` only (None otherwise), the NEAREST tables of the size, each
+        built and uploaded once.  With `box` = (pad_value, scaleup, center) of a letterboxed feed, the taps and
+        tables are those of the rectangle and the last element is (``letterbox_geometry``'s result, pad_value),
+        None otherwise.  ValueError for what the entries would refuse."""
         if isinstance(size, (int, np.integer)) and not isinstance(size, (bool, np.bool_)):
             size = (size, size)
         ok = isinstance(size, (tuple, list)) and len(size) == 2 and all(
@@ -882,9 +907,12 @@ class SceneRunner(_Runner):
             raise ValueError(f"{who}: size {size!r}: (out_h, out_w) or one int, each >= 1, out_h*out_w < 2^28")
         if not isinstance(resample, str) or resample not in FEED_RESAMPLE:
             raise ValueError(f"{who}: resample {resample!r}: one of {', '.join(FEED_RESAMPLE)}")
-        oh, ow = int(size[0]), int(size[1])
-        key, near = ("resize", oh, ow, resample), ("nearest", oh, ow)
         p = self.plan.pipe
+        oh, ow = int(size[0]), int(size[1])
+        if box is not None:
+            geo = letterbox_geometry((p.bg_h, p.bg_w), (oh, ow), box[1], box[2])
+            oh, ow, box = geo.new_h, geo.new_w, (geo, box[0])
+        key, near = ("resize", oh, ow, resample), ("nearest", oh, ow)
         if key not in self._feed_cache:
             if p.bg_w * p.bg_h >= 1 << 28:
                 raise ValueError(f"{who}: a {p.bg_w}x{p.bg_h} background: bg_w*bg_h must stay below 2^28")
@@ -900,18 +928,25 @@ class SceneRunner(_Runner):
         if index_map and near not in self._feed_cache:
             self._feed_cache[near] = tuple(_to_dev(G.nearest_table(n_in, n_out), self.device).view(torch.int32)
                                            for n_in, n_out in ((p.bg_w, ow), (p.bg_h, oh)))
-        return self._feed_cache[key] + (self._feed_cache[near] if index_map else (None, None))
+        return self._feed_cache[key] + (self._feed_cache[near] if index_map else (None, None)) + (box,)
 
     def _feed_args(self, caller: str, out, lut, mean, std, dtype, bgr, class_ids, alpha_min, cover_min, min_visible,
-                   index_map, images, size=None, resample="bilinear"):
+                   index_map, images, size=None, resample="bilinear", letterbox=False, pad_value=114, scaleup=True,
+                   center=True):
         """Everything ``feed`` refuses with ValueError, before any launch, and the uploads: the arguments of
         ``_feed_launch``."""
         who = f"SceneRunner.{caller}"
         alpha_min, cover_min = _check_level("alpha_min", alpha_min), _check_level("cover_min", cover_min)
         min_q = min_visible_q(min_visible)
-        for name, v in (("bgr", bgr), ("index_map", index_map)):
+        for name, v in (("bgr", bgr), ("index_map", index_map), ("letterbox", letterbox), ("scaleup", scaleup),
+                        ("center", center)):
             if not isinstance(v, (bool, np.bool_)):
                 raise ValueError(f"{who}: {name} {v!r}: a bool")
+        if isinstance(pad_value, (bool, np.bool_)) or not isinstance(pad_value, (int, np.integer)) or \
+                not 0 <= pad_value <= 255:
+            raise ValueError(f"{who}: pad_value {pad_value!r}: an int in 0..255")
+        if letterbox and size is None:
+            raise ValueError(f"{who}: letterbox=True needs size, the canvas (out_h, out_w)")
         p, S = self.plan.pipe, self.plan.n_scenes
 
         def on_device(t):
@@ -931,8 +966,14 @@ class SceneRunner(_Runner):
             self._feed_cache = {}
         table = self._feed_lut(lut, mean, std, dtype)
         classes = self._feed_classes(class_ids)
-        resize = None if size is None else self._feed_resize(who, size, resample, bool(index_map))
-        shape = (S, 3, p.bg_h, p.bg_w) if resize is None else (S, 3, resize[0], resize[1])
+        resize = None if size is None else self._feed_resize(
+            who, size, resample, bool(index_map), (int(pad_value), bool(scaleup), bool(center)) if letterbox else None)
+        if resize is None:
+            shape = (S, 3, p.bg_h, p.bg_w)
+        elif resize[8] is None:
+            shape = (S, 3, resize[0], resize[1])
+        else:
+            shape = (S, 3, resize[8][0].out_h, resize[8][0].out_w)
         if images is None:
             images = torch.empty(shape, dtype=table.dtype, device=self.device)
         elif not on_device(images) or images.dtype != table.dtype or tuple(images.shape) != shape or \
@@ -943,7 +984,7 @@ class SceneRunner(_Runner):
     def _feed_launch(self, caller: str, out, table, bgr: bool, classes, alpha_min: int, cover_min: int, min_q: int,
                      index_map: bool, images, resize=None) -> SceneFeed:
         """The launches of ``feed``: the box or the map launch, then the two or three feed entries (with `resize`,
-        ``_feed_resize``'s tables, the resizing ones)."""
+        ``_feed_resize``'s tables, the resizing ones, or the letterboxing ones where it names a rectangle)."""
         p, S, K = self.plan.pipe, self.plan.n_scenes, self.plan.per_scene
         st, lib = _stream(self.device), self.lib
         buf = None
@@ -955,23 +996,43 @@ class SceneRunner(_Runner):
             N.check(lib.ipp_scene_feed_images(out.data_ptr(), images.data_ptr(), table.data_ptr(), S, p.bg_w, p.bg_h,
                                               table.element_size(), int(bgr), st), "ipp_scene_feed_images")
         else:
-            oh, ow, kx, ky, taps_x, taps_y, xtab, ytab = resize
+            oh, ow, kx, ky, taps_x, taps_y, xtab, ytab, box = resize
+        if resize is not None and box is None:
             N.check(lib.ipp_scene_feed_resize(out.data_ptr(), images.data_ptr(), table.data_ptr(), taps_x.data_ptr(),
                                               taps_y.data_ptr(), S, p.bg_w, p.bg_h, ow, oh, kx, ky,
                                               table.element_size(), int(bgr), st), "ipp_scene_feed_resize")
+        elif resize is not None:
+            geo, pad = box
+            rect = (geo.new_w, geo.new_h, geo.left, geo.top, geo.out_w, geo.out_h)
+            N.check(lib.ipp_scene_feed_letterbox(out.data_ptr(), images.data_ptr(), table.data_ptr(), taps_x.data_ptr(),
+                                                 taps_y.data_ptr(), S, p.bg_w, p.bg_h, *rect, kx, ky, pad,
+                                                 table.element_size(), int(bgr), st), "ipp_scene_feed_letterbox")
         targets = torch.empty((S * K, 6), dtype=torch.float32, device=self.device)
         count = torch.empty(1, dtype=torch.int32, device=self.device)
         slot = torch.empty((S, K), dtype=torch.int32, device=self.device)
-        N.check(lib.ipp_scene_feed_targets(rows.data_ptr(), self._scene_layer.data_ptr(),
-                                           classes.data_ptr() if classes is not None else None, S * K, S, K, p.bg_w,
-                                           p.bg_h, min_q, targets.data_ptr(), count.data_ptr(), slot.data_ptr(), st),
-                "ipp_scene_feed_targets")
+        ids = classes.data_ptr() if classes is not None else None
+        if resize is None or box is None:
+            N.check(lib.ipp_scene_feed_targets(rows.data_ptr(), self._scene_layer.data_ptr(), ids, S * K, S, K, p.bg_w,
+                                               p.bg_h, min_q, targets.data_ptr(), count.data_ptr(), slot.data_ptr(),
+                                               st), "ipp_scene_feed_targets")
+        else:
+            N.check(lib.ipp_scene_feed_targets_letterbox(rows.data_ptr(), self._scene_layer.data_ptr(), ids, S * K, S, K,
+                                                         p.bg_w, p.bg_h, min_q, *rect, targets.data_ptr(),
+                                                         count.data_ptr(), slot.data_ptr(), st),
+                    "ipp_scene_feed_targets_letterbox")
         idx = None
         if index_map and resize is None:
             ibuf = torch.empty_like(buf)
             N.check(lib.ipp_scene_feed_index_map(buf.data_ptr(), buf.shape[2], p.bg_w, p.bg_h, slot.data_ptr(), S, K,
                                                  ibuf.data_ptr(), st), "ipp_scene_feed_index_map")
             idx = ibuf[:, :, :p.bg_w]
+        elif index_map and box is not None:
+            ibuf = torch.empty((S, geo.out_h, (geo.out_w + 15) // 16 * 16), dtype=torch.uint8, device=self.device)
+            N.check(lib.ipp_scene_feed_index_map_letterbox(buf.data_ptr(), buf.shape[2], p.bg_w, p.bg_h, slot.data_ptr(),
+                                                           S, K, xtab.data_ptr(), ytab.data_ptr(), *rect,
+                                                           ibuf.data_ptr(), ibuf.shape[2], st),
+                    "ipp_scene_feed_index_map_letterbox")
+            idx = ibuf[:, :, :geo.out_w]
         elif index_map:
             ibuf = torch.empty((S, oh, (ow + 15) // 16 * 16), dtype=torch.uint8, device=self.device)
             N.check(lib.ipp_scene_feed_index_map_sampled(buf.data_ptr(), buf.shape[2], p.bg_w, p.bg_h, slot.data_ptr(),
@@ -985,7 +1046,8 @@ class SceneRunner(_Runner):
                  mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0), dtype: torch.dtype = torch.float16, bgr: bool = False,
                  class_ids=0, alpha_min: int = 1, cover_min: int = 128, min_visible: float = 0.0,
                  index_map: bool = False, images: Optional[torch.Tensor] = None, cull: bool = False,
-                 min_pixels: int = 1, size=None, resample: str = "bilinear") -> SceneFeed:
+                 min_pixels: int = 1, size=None, resample: str = "bilinear", letterbox: bool = False,
+                 pad_value: int = 114, scaleup: bool = True, center: bool = True) -> SceneFeed:
         """``run`` followed by ``feed`` (same arguments), all on the current
         stream and without a copy back.  With ``cull`` the run is
         ``run_culled``'s — the H launches, ipp_pipe_scene_cull with
@@ -1000,7 +1062,7 @@ class SceneRunner(_Runner):
             min_q, min_pixels = self._check_cull("run_feed", min_visible, min_pixels)
         self._check("run_feed", src, bgs, out)
         args = self._feed_args("run_feed", out, lut, mean, std, dtype, bgr, class_ids, alpha_min, cover_min,
-                               min_visible, index_map, images, size, resample)
+                               min_visible, index_map, images, size, resample, letterbox, pad_value, scaleup, center)
         self._launch_h(src, bgs, out)
         if cull:
             self._launch_cull("run_feed", args[5], args[6], min_q, min_pixels)

@@ -971,6 +971,107 @@ int ipp_scene_feed_index_map_sampled(const uint8_t* map, int64_t map_pitch, int3
                                      int32_t per_scene, const int32_t* xtab, const int32_t* ytab,
                                      int32_t out_w, int32_t out_h, uint8_t* out, int64_t out_pitch,
                                      void* stream);
+/* The same batch letterboxed: the composites resized with their aspect kept
+ * into a rectangle of new_w x new_h at (left, top) of an out_w x out_h canvas,
+ * the rest of the canvas a pad value, and the targets and the index map moved
+ * and scaled to match.
+ *
+ * THE GEOMETRY is host arithmetic in exact integers (labels_fmt.
+ * letterbox_geometry(bg_hw, size, scaleup, center, stride)); the entries take
+ * any rectangle inside the canvas.  It is the usual LetterBox rule, r =
+ * min(out_h / bg_h, out_w / bg_w), with min(r, 1) when scaleup is false:
+ *   LIMITING AXIS: the one with the smaller ratio, compared by cross-
+ *     multiplication (out_h·bg_w against out_w·bg_h); on a tie both are.  A
+ *     limiting axis takes its canvas extent exactly.  With scaleup false and
+ *     r >= 1 (out_h >= bg_h and out_w >= bg_w) both keep the background's.
+ *   OTHER AXIS: a·b / c rounded half to even, a = its background extent, b =
+ *     the limiting axis' canvas extent, c = the limiting axis' background
+ *     extent: q, rem = divmod(a·b, c), plus one where 2·rem > c, or 2·rem == c
+ *     and q is odd (Python's round); at least 1.
+ *   STRIDE s >= 1 (the minimal rectangle): with dw = out_w - new_w, dh = out_h
+ *     - new_h the canvas shrinks to out_w = new_w + dw % s, out_h = new_h +
+ *     dh % s before the offsets are taken.
+ *   OFFSETS: center: left = dw / 2, top = dh / 2, rounded down (what round(dw
+ *     / 2 - 0.1) gives); else left = top = 0.
+ *   The shrunken canvas passed back as the size gives the same rectangle
+ *   unless the other axis' extent was rounded DOWN and its remainder dw % s
+ *   (dh % s) is 0: then that axis fills the new canvas, becomes the limiting
+ *   one, and the formerly limiting extent is computed anew (it can come out
+ *   smaller by the rounding; the rectangle still fits the canvas).
+ *
+ * ipp_scene_feed_letterbox: in, lut, elem_size, bgr as for
+ * ipp_scene_feed_resize; taps_x, taps_y: ipp_plan_resample's tables for (bg_w
+ * -> new_w) and (bg_h -> new_h) with ksize_x and ksize_y, or geometry.
+ * identity_taps for an axis whose sizes are equal; out = n_scenes x 3 x out_h x
+ * out_w contiguous elements; pad in 0..255.  With r the H FIRST, THEN V integer
+ * result of ipp_scene_feed_resize taken for (new_w, new_h):
+ *   out[s][c][y][x] = lut[c][ r[y - top][x - left][ch(c)] ]   for left <= x <
+ *                     left + new_w and top <= y < top + new_h,
+ *   out[s][c][y][x] = lut[c][pad]                             everywhere else.
+ * The table's words are copied; no float arithmetic runs.  ONE launch covers
+ * the canvas: one workgroup of 256 threads per (scene, tile of tw x th canvas
+ * elements), every element of out written exactly once and none outside it.
+ * The part of a tile inside the rectangle is a run of at most tw x th resized
+ * outputs, and the bound of ipp_scene_feed_resize holds for a run wherever it
+ * starts, so the tile and the LDS bytes are those of the rectangle:
+ * ipp_scene_feed_resize_lds(bg_w, bg_h, new_w, new_h, ksize_x, ksize_y,
+ * elem_size, tile) states both, within IPP_FEED_RESIZE_LDS_BYTES.  A workgroup
+ * whose tile lies wholly in the pad reads nothing of `in` and stages nothing;
+ * pad elements go in 16-B stores at the 16-B boundaries of their plane row,
+ * element by element before the first and behind the last.  As there, nothing
+ * is assumed of the alignment of `in`, every window is clamped to the staged
+ * span, and no byte outside the n_scenes·bg_h·bg_w·3 of `in` is read whatever
+ * the tables hold.
+ * IPP_E_ARG, before any launch: everything ipp_scene_feed_resize refuses, with
+ * new_w, new_h in the place of out_w, out_h; new_w or new_h < 1, left or top <
+ * 0, left + new_w > out_w, top + new_h > out_h; pad outside 0..255; out_w·out_h
+ * >= 2^28; n_scenes·tiles >= 2^31 - 1 (the grid, tiles of the canvas).
+ *
+ * ipp_scene_feed_targets_letterbox: ipp_scene_feed_targets — DESCRIPTOR, KEPT,
+ * ORDER, slot, count and the -1 rows exactly as there, by the same code — with
+ * another ROW.  From the integer row (x0, y0, x1, y1):
+ *   cx = f32( f64((x0 + x1)·new_w + 2·left·bg_w) / f64(2·bg_w·out_w) )
+ *   w  = f32( f64((x1 - x0)·new_w) / f64(bg_w·out_w) )
+ *   cy and h alike with y, new_h, top, bg_h and out_h.
+ * Numerators and denominators are int64 products; with every side <=
+ * IPP_FEED_MAX_SIDE = 2^23 they stay below 2^49 and are exact in float64.  Then
+ * ONE correctly rounded float64 division and ONE round-to-nearest conversion
+ * to float32 (the file is built without fast-math or reciprocal flags).  This
+ * is NOT ipp_scene_feed_targets' single float32 division: even with the
+ * rectangle equal to the canvas (new = out = bg, left = top = 0 included) the
+ * two may differ in the last bit, since a float64 quotient rounded again to
+ * float32 is not always the correctly rounded float32 quotient.  Nothing
+ * depends on an order; there is no float atomic.
+ * IPP_E_ARG, before any launch: what ipp_scene_feed_targets refuses; out_w or
+ * out_h outside 1..IPP_FEED_MAX_SIDE; new_w or new_h < 1, left or top < 0, left
+ * + new_w > out_w, top + new_h > out_h.
+ *
+ * ipp_scene_feed_index_map_letterbox: ipp_scene_feed_index_map_sampled with
+ * xtab, ytab of new_w and new_h entries (geometry.nearest_table(bg, new)),
+ * placed at (left, top):
+ *   out[s][y][x] = f(map[s][ytab[y - top]][xtab[x - left]])  inside the rectangle,
+ *   out[s][y][x] = 0  in the pad and in columns [out_w, out_pitch),
+ * in n_scenes slots of out_h rows of out_pitch bytes, every byte of which is
+ * written, in 16-B stores.  The map is read at the sampled positions only.
+ * IPP_E_ARG, before any launch: what ipp_scene_feed_index_map_sampled refuses,
+ * and the rectangle checks above. */
+int ipp_scene_feed_letterbox(const uint8_t* in, void* out, const void* lut, const int32_t* taps_x,
+                             const int32_t* taps_y, int32_t n_scenes, int32_t bg_w, int32_t bg_h,
+                             int32_t new_w, int32_t new_h, int32_t left, int32_t top, int32_t out_w,
+                             int32_t out_h, int32_t ksize_x, int32_t ksize_y, int32_t pad,
+                             int32_t elem_size, int32_t bgr, void* stream);
+int ipp_scene_feed_targets_letterbox(const int32_t* rows, const int32_t* scene_layer,
+                                     const int32_t* class_ids /* may be NULL */, int32_t n_images,
+                                     int32_t n_scenes, int32_t per_scene, int32_t bg_w, int32_t bg_h,
+                                     int32_t min_q, int32_t new_w, int32_t new_h, int32_t left,
+                                     int32_t top, int32_t out_w, int32_t out_h, float* targets,
+                                     int32_t* count, int32_t* slot, void* stream);
+int ipp_scene_feed_index_map_letterbox(const uint8_t* map, int64_t map_pitch, int32_t bg_w,
+                                       int32_t bg_h, const int32_t* slot, int32_t n_scenes,
+                                       int32_t per_scene, const int32_t* xtab, const int32_t* ytab,
+                                       int32_t new_w, int32_t new_h, int32_t left, int32_t top,
+                                       int32_t out_w, int32_t out_h, uint8_t* out, int64_t out_pitch,
+                                       void* stream);
 
 /* ------------------------------------------------------------------------ */
 /* K10-K13: pixels_isolés.keep_largest_component                             */
